@@ -1,12 +1,20 @@
 """Benchmark of the hot path: AV Efficient Conformer training step (forward + 6 CTC losses + backward + gradient all-reduce + Adam)
 on synthetic LRS2-shaped batches: B=32 per GPU, audio 63 840 samples (400 mel frames), video 100x88x88, 20 labels.
 
-    python bench.py [--gpus N --steps K --warmup W]          (N>1: one rank per GPU over RCCL -- started by torch.distributed.run, or by bench.py itself
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                                                             (N>1: one rank per GPU over RCCL -- started by torch.distributed.run, or by bench.py itself
                                                               when it is run as plain `python bench.py --gpus N`)
 
-Prints ONE JSON line (rank 0): whole-job utterances/s, plus `roofline` (one row per kernel instance of the MFMA product / convolution families: what a launch computes
-comes from an eager, event-bracketed leg run AFTER the timed region -- events cannot be recorded inside the timed hipGraph --, how long it takes inside the replayed step
-from the committed rocprofv3 summary of this command, `roofline.timing_source`) and `cpu_baseline` (the CPU oracle on the host cores, bounded sample)."""
+Prints ONE JSON line (rank 0): whole-job utterances/s and `ms_per_step`, the time of one of the K timed steps.  A plain run sets up, warms up, times the K steps
+and prints that line, nothing else.  `--full` adds what takes runs of its own: `roofline` (one row per kernel instance of the MFMA product / convolution families:
+what a launch computes comes from an eager, event-bracketed leg run AFTER the timed region -- events cannot be recorded inside the timed hipGraph --, how long it
+takes inside the replayed step from the committed rocprofv3 summary of this command, `roofline.timing_source`), the eager step times and `cpu_baseline` (the CPU
+oracle on the host cores, bounded sample).
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).  The last two timed steps start from the initial weights
+and optimizer state, restored outside the timed region: the kernels sum with fp32 atomics in an order that differs from run to run, and in bf16 that rounding
+grows with every training step, while two steps from a fixed state differ only by it.  The inputs, the initial weights and the dropout seeds are fixed, so two
+builds run with the same arguments can be compared output for output."""
 import argparse
 import json
 import os
@@ -169,6 +177,37 @@ def rows_from_graph_trace(roof, peak):
     return roof
 
 
+def initial_state(model):
+    """copies of what a training step changes (master weights, BatchNorm buffers), taken before the first step"""
+    return model.arena.master.clone(), [b.detach().clone() for b in model.buffers()]
+
+
+def restore_state(model, state):
+    """back to the initial weights, BatchNorm buffers and (zero) Adam moments, in place: the captured graph keeps its addresses"""
+    master, bufs = state
+    model.arena.master.copy_(master)
+    for b, v in zip(model.buffers(), bufs):
+        b.copy_(v)
+    model.optimizer._flat["exp_avg"].zero_()
+    model.optimizer._flat["exp_avg_sq"].zero_()
+    model.arena.mark_dirty()
+    torch.cuda.synchronize()
+
+
+def dump_outputs(out_dir, model, losses):
+    """What the last timed step handed back: its losses (float64 scalars; they follow the forward pass of the weights that the step before updated, so they
+    depend on one whole backward pass and Adam update as well) and the BatchNorm running statistics.  The gradients are not handed back (the Adam kernel clears
+    them), and the updated weights are not written: Adam's first update is lr x sign(gradient), so wherever the gradient is rounding noise around zero (biases in
+    front of a BatchNorm or a softmax, which do not change the output) a rounding difference flips a whole update."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.array(float(v.detach()), dtype=np.float64))          # loss, loss_<output>
+    sd = model.state_dict()
+    bn = [sd[k].detach().float().flatten() for k in sd if k.endswith(("running_mean", "running_var"))]
+    np.save(os.path.join(out_dir, "bn_running_stats.npy"), torch.cat(bn).cpu().numpy())
+
+
 def spawn_ranks(n):
     """Re-run this command under torch.distributed.run with `n` ranks on this node (free rendezvous port on 127.0.0.1); rank 0 prints the JSON line."""
     import socket
@@ -192,12 +231,18 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--fp8", action="store_true", help="e4m3 operands for the eligible forward Linear products on top of bf16 (BASELINE config 5's arithmetic; DESIGN.md section 15)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the roofline / eager-step leg and the CPU baseline after the timed steps (runs of their own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the roofline / eager-step leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--eager", action="store_true", help="do not capture the step into a hipGraph")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU multi-process debugging)")
     ap.add_argument("--share-gpu", action="store_true", help="debug: every rank uses cuda:0 (with --backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    kernel_timing = args.full and not args.no_kernel_timing
+    cpu_leg = args.full and not args.no_cpu_baseline
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")       # (before the HIP runtime starts) dmabuf IPC: RCCL and the peer exchange buffers need it on this driver
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -240,6 +285,7 @@ def main():
     else:
         world_dist = False
     inputs, targets = synthetic_batch(args.batch, device, seed=rank)
+    state0 = initial_state(model) if args.dump_outputs else None
     precision = torch.bfloat16 if args.dtype == "bf16" else torch.float32
 
     def barrier():
@@ -285,12 +331,28 @@ def main():
     for _ in range(args.warmup):
         last = run_step()
     barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        last = run_step()
-    barrier()
-    elapsed = time.perf_counter() - t0
-    if not args.no_kernel_timing:
+
+    def timed(n):
+        t0 = time.perf_counter()
+        out = None
+        for _ in range(n):
+            out = run_step()
+        barrier()
+        return time.perf_counter() - t0, out
+
+    if args.dump_outputs:
+        # the last two timed steps start from the initial state (module docstring); the restore itself is not timed
+        tail = min(args.steps, 2)
+        elapsed, last = timed(args.steps - tail)
+        restore_state(model, state0)
+        barrier()
+        t_tail, last = timed(tail)
+        elapsed += t_tail
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, last)
+    else:
+        elapsed, last = timed(args.steps)
+    if kernel_timing:
         # roofline leg: the same step, eagerly, with HIP events around every GEMM-family launch (events cannot be recorded inside a graph).
         # Every rank runs it (the step contains collectives); only rank 0 records events.
         # The audio branch's second stream is switched off for this leg, so that an event pair brackets exactly one kernel.
@@ -328,7 +390,7 @@ def main():
         utt = world * args.batch * args.steps
         value = utt / elapsed
         peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_F32_TFLOPS
-        roof = ops.KERNEL_TIMER.summary(peak, steps=timed_steps) if not args.no_kernel_timing else None
+        roof = ops.KERNEL_TIMER.summary(peak, steps=timed_steps) if kernel_timing else None
         if roof is not None and args.dtype == "bf16" and args.batch == 32 and use_graph and world == 1:
             roof = rows_from_graph_trace(roof, peak)
         if roof is not None and args.dtype == "bf16" and args.batch == 32:
@@ -345,8 +407,8 @@ def main():
                                    "batch %d/GPU, audio 63840 samples (400 mel frames), video 100x88x88, 20 labels; dropout 0.1 + SpecAugment on" % args.batch,
                        "global_batch": world * args.batch, "parallelism": "dp%d" % world, "hipgraph": bool(use_graph), "step_path": step_path, "fallback": fallback, "syncbn_exchange": ("peer-write kernels over xGMI" if (world > 1 and peer.active() is not None) else ("torch.distributed" if world > 1 else None)), "params": 61738836, "loss": round(loss, 4),
                        "model_mfma_util": round(value * GFLOP_PER_UTT / 1e3 / peak, 5),
-                       "eager_instrumented_ms_per_step": (round(eager_ms, 2) if not args.no_kernel_timing else None),
-                       "eager_two_stream_ms_per_step": (round(eager2_ms, 2) if not args.no_kernel_timing else None),
+                       "eager_instrumented_ms_per_step": (round(eager_ms, 2) if kernel_timing else None),
+                       "eager_two_stream_ms_per_step": (round(eager2_ms, 2) if kernel_timing else None),
                        "notes": "parity: every module against fixtures generated from the reference (tests/golden); the mel front-end is pinned to a restatement of "
                                 "torchaudio's documented MelSpectrogram defaults only (torchaudio is not part of /root/reference: tests/golden/ref_shims.py). "
                                 "bf16 gradient parity (tests/test_gpu_round2.py, test_gpu_round4.py: every gradient tensor of the timed B=32 graph against the oracle) is enforced as "
@@ -355,7 +417,7 @@ def main():
                                 "the eager leg (7 launches) and by stream in the graph (8)"},
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_leg:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if world > 1 or single_dist:

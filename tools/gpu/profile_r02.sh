@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02
 # 1. default bench line (the driver's command)
-python bench.py 2>$O/bench_default.err | grep "^{" > $O/r02_bench_line.json
+python bench.py --full 2>$O/bench_default.err | grep "^{" > $O/r02_bench_line.json
 # 2. kernel trace + stats of the graph-replayed step
 ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o r02 -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timing > $O/prof_bench.log 2>&1 )
 find /tmp/prof -name "*kernel_stats.csv" -exec cp {} $O/r02_kernel_stats.csv \;

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03
 if [ "${1:-all}" = "all" ] || [ "$1" = "bench" ]; then
-python bench.py 2>$O/bench_default.err | grep "^{" > $O/r03_bench_line.json
+python bench.py --full 2>$O/bench_default.err | grep "^{" > $O/r03_bench_line.json
 fi
 # kernel trace + stats of the graph-replayed step (1 eager warm-up step + 4 replays = 5 steps traced; model set-up copies included)
 ( cd /tmp && rm -rf /tmp/prof && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o r03 -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timing > $O/prof_bench.log 2>&1 )

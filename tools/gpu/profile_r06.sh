@@ -21,7 +21,7 @@ python tools/roofline_table.py $O/r06_kernel_stats_final.csv $O/r06_pmc_traffic.
 AVEC_STAMPS=1 timeout 600 python tools/step_stamps.py 2>&1 | grep -v amdgpu > $O/r06_step_stamps.txt
 python tools/block_trace.py 32 100 256 2>&1 | grep -v amdgpu > $O/r06_block_trace.txt
 # the default bench line last (it reads the PMC summary copied above)
-python bench.py 2>$O/bench_default.err | grep "^{" > $O/r06_bench_line.json
+python bench.py --full 2>$O/bench_default.err | grep "^{" > $O/r06_bench_line.json
 python -c "import json; d=json.loads(open('$O/r06_bench_line.json').read().strip().splitlines()[-1]); print('STEP', d['ms_per_step'], d['value'], d['config'].get('eager_two_stream_ms_per_step'), d['roofline']['frac'] if d.get('roofline') else None)"
 if [ "$MODE" = "all" ]; then
 : > $O/r06_variants.txt
