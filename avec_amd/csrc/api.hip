@@ -23,6 +23,7 @@ extern "C" int avec_struct_size(int which) {
   switch (which) {
     case 0: return (int)sizeof(avec_rows_t); case 1: return (int)sizeof(avec_epilogue_t); case 2: return (int)sizeof(avec_attn_t); case 3: return (int)sizeof(avec_tn_item_t);
     case 4: return (int)sizeof(avec_tn_batched_t); case 5: return (int)sizeof(avec_ln_item_t); case 6: return (int)sizeof(avec_fp8_item_t); case 7: return (int)sizeof(avec_wgrad3x3_item_t);
+    case 8: return (int)sizeof(avec_ngram_t);
     default: return -1;
   }
 }

@@ -80,8 +80,14 @@ class WgradItem(ctypes.Structure):
                 ("W", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
+class NGram(ctypes.Structure):
+    """avec_ngram_t (avec_amd/ngram.py fills it)"""
+    _fields_ = [("order", ctypes.c_int), ("V", ctypes.c_int), ("unigram", ctypes.c_void_p), ("ctx_cap", ctypes.c_longlong), ("ctx_key", ctypes.c_void_p),
+                ("ctx_bo", ctypes.c_void_p), ("ctx_off", ctypes.c_void_p), ("ctx_cnt", ctypes.c_void_p), ("cont_tok", ctypes.c_void_p), ("cont_lp", ctypes.c_void_p)]
+
+
 TN_GROUP_MAX, LN_GROUP_MAX, WGRAD_GROUP_MAX = 32, 40, 16
-ABI_STRUCTS = (Rows, Epilogue, Attn, TnItem, TnBatched, LnItem, Fp8Item, WgradItem)      # index = `which` of avec_struct_size
+ABI_STRUCTS = (Rows, Epilogue, Attn, TnItem, TnBatched, LnItem, Fp8Item, WgradItem, NGram)      # index = `which` of avec_struct_size
 
 
 def _ctype(decl):

@@ -1903,3 +1903,39 @@ def argmax_rows(logits):
     out = torch.empty(lead, dtype=torch.int64, device=lg.device)
     lib.argmax_rows(lg.data_ptr(), out.data_ptr(), out.numel(), V, rt.stream())
     return out
+
+
+def ctc_beam_search(logits, lengths, beam, tmp=1.0, lm=None, alpha=0.6, beta=1.0):
+    """CTC prefix beam search (blank 0) of logits [B, T, V] with lengths [B], optionally fused with an n-gram LM (avec_amd.ngram.NGramLM):
+    one launch for the whole batch.  Returns tokens [B, beam, T] int32, out_len [B, beam] int32, score [B, beam] (ranking score, best first) and
+    ctc_logp [B, beam]; empty slots have score -inf and length 0.  alpha / beta are ignored without an LM."""
+    B, T, V = logits.shape
+    lg = _f32c(logits)
+    dev = lg.device
+    lens = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    st = rt.stream()
+    ws = torch.empty(lib.raw("avec_ctc_beam_workspace_bytes")(B, T, beam), dtype=torch.uint8, device=dev)
+    tokens = torch.empty(B, beam, T, dtype=torch.int32, device=dev)
+    out_len = torch.empty(B, beam, dtype=torch.int32, device=dev)
+    score = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    ctc_logp = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    use_lm = lm is not None and lm.usable
+    lm_arg = _byref(lm.device_struct(dev)) if use_lm else None
+    oov = lm.oov_logprob if use_lm else 0.0
+    lib.ctc_beam_search(lg.data_ptr(), lens.data_ptr(), B, T, V, beam, 1.0 / tmp, lm_arg, alpha if use_lm else 0.0, beta if use_lm else 0.0, oov,
+                        ws.data_ptr(), ws.numel(), tokens.data_ptr(), out_len.data_ptr(), score.data_ptr(), ctc_logp.data_ptr(), st)
+    return tokens, out_len, score, ctc_logp
+
+
+def ngram_rows(lm, contexts):
+    """ln P(. | ctx) [n, V] on the device for a list of token histories (oldest first, -1 = <s>): avec_ngram_rows"""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n, L = len(contexts), max(1, max((len(c) for c in contexts), default=1))
+    ctx = torch.zeros(n, L, dtype=torch.int32)
+    for i, c in enumerate(contexts):
+        if len(c):
+            ctx[i, :len(c)] = torch.tensor(list(c), dtype=torch.int32)
+    ctx, clen = ctx.to(dev), torch.tensor([len(c) for c in contexts], dtype=torch.int32, device=dev)
+    rows = torch.empty(n, lm.V, dtype=torch.float32, device=dev)
+    lib.ngram_rows(_byref(lm.device_struct(dev)), ctx.data_ptr(), clen.data_ptr(), n, L, lm.oov_logprob, rows.data_ptr(), rt.stream())
+    return rows

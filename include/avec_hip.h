@@ -39,7 +39,7 @@ extern "C" {
 int avec_version(void);
 /* sizeof() of the structs that cross this boundary, as THIS library was compiled: a binding compares them with its own declarations at load time, so that a header / .so
  * pair that drifted apart fails loudly instead of reading past a shorter struct.  which: 0 avec_rows_t, 1 avec_epilogue_t, 2 avec_attn_t, 3 avec_tn_item_t,
- * 4 avec_tn_batched_t, 5 avec_ln_item_t, 6 avec_fp8_item_t, 7 avec_wgrad3x3_item_t; -1 for an unknown index. */
+ * 4 avec_tn_batched_t, 5 avec_ln_item_t, 6 avec_fp8_item_t, 7 avec_wgrad3x3_item_t, 8 avec_ngram_t; -1 for an unknown index. */
 int avec_struct_size(int which);
 const char* avec_last_error(void);
 /* the kernel instance chosen by the last GEMM-family entry point called on this thread ("gemm_nt_glds_kernel<bf16,64,64,0,4,0,128>" ...): measurement aid, bench.py's roofline rows */
@@ -421,6 +421,40 @@ int avec_softmax_ce(const float* logits, const long long* targets, long long ign
 int avec_len_affine(const long long* in, long long* out, int n, long long sub, long long div, long long add, hipStream_t stream);
 /* CTCGreedySearchDecoder argmax (nnet/decoders.py:97-120) */
 int avec_argmax_rows(const float* x, long long* out, long long M, int V, hipStream_t stream);
+
+/* ---- CTC prefix beam search with n-gram LM fusion (CTCBeamSearchDecoder, nnet/decoders.py:175-257: ctcdecode + KenLM) ------------------------------
+ * An n-gram LM as device tables (avec_amd/ngram.py builds them from an ARPA file).  Token k is the ARPA word chr(k + ngram_offset); every value is a
+ * NATURAL log.  A context is a tuple of at most order-1 tokens, oldest first, where token -1 is <s>; it is packed 16 bits per token (code = token + 1,
+ * 0xFFFF for <s>; token j of the tuple at bits [16j, 16j+16) of the 128-bit key {lo: tokens 0-3, hi: tokens 4-6}) and found by linear probing from
+ * slot mix64(lo * 0x9E3779B97F4A7C15 ^ hi * 0xC2B2AE3D27D4EB4F) & (ctx_cap - 1), mix64 = the splitmix64 finaliser; an all-zero key is an empty slot.
+ * A context entry holds its backoff and the continuations (token, ln p) of the n-grams it starts, sorted by token.  ln P(. | ctx) is built as a row:
+ * the unigram row, then for each longer suffix of ctx that is in the table: + its backoff, then its continuations overwrite.  unigram[c] = -INFINITY
+ * marks a token that is not an LM word: its term is exactly oov_logprob in every context. */
+typedef struct avec_ngram {
+  int order;                          /* 1..8 */
+  int V;                              /* length of `unigram` (the vocabulary the table was built for) */
+  const float* unigram;               /* [V] */
+  long long ctx_cap;                  /* slots of the context table, a power of two (load <= 0.5) */
+  const unsigned long long* ctx_key;  /* [ctx_cap][2] {lo, hi} */
+  const float* ctx_bo;                /* [ctx_cap] */
+  const int* ctx_off;                 /* [ctx_cap] first continuation */
+  const int* ctx_cnt;                 /* [ctx_cap] number of continuations */
+  const int* cont_tok;                /* [n_cont] */
+  const float* cont_lp;               /* [n_cont] */
+} avec_ngram_t;
+/* bytes of the backpointer workspace avec_ctc_beam_search needs: [B][T][W] int32 */
+long long avec_ctc_beam_workspace_bytes(int B, int T, int W);
+/* Prefix beam search over logits [B][T][V] fp32 (lengths int64, clamped to [0, T]), blank = 0, per frame logp = log_softmax(logits * inv_tmp); one
+ * workgroup per utterance, the frame loop inside the kernel.  lm = NULL decodes without an LM; otherwise an extension by c adds
+ * alpha * ln P(c | last order-1 tokens of <s> prefix) + beta to the prefix's LM score.  Per utterance the W best prefixes by
+ * score = ln(p_blank + p_nonblank) + LM score, best first; ties go to the lower candidate index (stays: slot i; extension (slot i, token c): W + i*V + c).
+ * Outputs: tokens [B][W][T] int32 (zero past out_len), out_len [B][W] int32, score [B][W], ctc_logp [B][W] = ln(p_blank + p_nonblank); empty slots:
+ * score = ctc_logp = -inf, out_len = 0.  Limits: W <= 64, V <= 1024, order <= 8.  workspace: avec_ctc_beam_workspace_bytes. */
+int avec_ctc_beam_search(const float* logits, const long long* lengths, int B, int T, int V, int W, float inv_tmp, const avec_ngram_t* lm, float alpha, float beta,
+                         float oov_logprob, void* workspace, long long workspace_bytes, int* tokens, int* out_len, float* score, float* ctc_logp, hipStream_t stream);
+/* rows[i][c] = ln P(c | ctx_i) as the beam search sees it: ctx [n][max_len] int32 tokens oldest first (-1 = <s>), ctx_len [n]; only the last order-1
+ * tokens of a context are used.  Test and documentation aid for the table layout above. */
+int avec_ngram_rows(const avec_ngram_t* lm, const int* ctx, const int* ctx_len, int n, int max_len, float oov_logprob, float* rows, hipStream_t stream);
 /* optimizers.Adam.step (nnet/optimizers.py:71-75) over flat arenas; state_dev = {step, lr} */
 int avec_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
                    float weight_decay, float grad_scale, int zero_grad, long long n, hipStream_t stream);

@@ -1,0 +1,37 @@
+"""tests/configs/av_synthetic.py with the decoder the reference's LRS2/3 configs use (configs/LRS23/AV/EffConfInterCTC.py:39-46,64): CTCBeamSearchDecoder
+with beam_size 16 fused with a seeded random 6-gram ARPA file (written to $AVEC_TEST_ARPA, or to a temporary directory).  Used by tests/test_gpu_ctc_beam.py
+through main.py -m evaluation."""
+import os
+import sys
+import tempfile
+
+import nnet
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ctc_beam_oracle  # noqa: E402
+
+ngram_path = os.environ.get("AVEC_TEST_ARPA") or os.path.join(tempfile.mkdtemp(), "6gram_synthetic.arpa")
+if not os.path.exists(ngram_path):
+    ctc_beam_oracle.write_random_arpa(ngram_path, V=256, order=6, n_per_order=2000, seed=6, extras=False)
+
+vocab_size = 256
+loss_weights = {"v_ctc_2": 0.5 / 3, "v_ctc_5": 0.5 / 3, "a_ctc_7": 0.5 / 3, "a_ctc_10": 0.5 / 3, "f_ctc_1": 0.5 / 3, "outputs": 0.5}
+
+batch_size = 4
+accumulated_steps = 1
+eval_training = False
+precision = torch.bfloat16
+epochs = 1
+recompute_metrics = True          # evaluation: the word error rate of the whole set from the gathered hypotheses (nnet/model.py:899-931), not the mean of per-batch rates
+callback_path = os.environ.get("AVEC_TEST_CALLBACKS", os.path.join(tempfile.gettempdir(), "avec_callbacks", "av_synthetic_beam"))
+
+model = nnet.AudioVisualEfficientConformerInterCTC(vocab_size=vocab_size, v_interctc_blocks=[3, 6], a_interctc_blocks=[8, 11], f_interctc_blocks=[2])
+model.compile(losses=nnet.CTCLoss(zero_infinity=True, assert_shorter=False),
+              decoders={"outputs": nnet.CTCBeamSearchDecoder(beam_size=16, ngram_path=ngram_path, ngram_alpha=0.6, ngram_beta=1.0, ngram_offset=100)}, metrics={"outputs": nnet.WordErrorRate()}, loss_weights=loss_weights)
+
+collate_fn = nnet.CollateFn(inputs_params=[{"axis": 0, "padding": True}, {"axis": 3}, {"axis": 1, "padding": True}, {"axis": 4}],
+                            targets_params=({"axis": 2, "padding": True}, {"axis": 5}))
+training_dataset = nnet.datasets.LRS(batch_size=batch_size, collate_fn=collate_fn, version="LRS2", mode="pretrain+train+val", video_max_length=100,
+                                     align=True, num_synthetic=12, seed=0)
+evaluation_dataset = [nnet.datasets.LRS(batch_size=batch_size, collate_fn=collate_fn, version="LRS2", mode="test", num_synthetic=8, seed=1)]
