@@ -119,6 +119,8 @@ __device__ __forceinline__ float drop_scale(const unsigned long long* rng, uint3
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float swishf_(float x) { return x * sigmoidf_(x); }
 __device__ __forceinline__ float dswishf_(float x) { float s = sigmoidf_(x); return s * (1.f + x * (1.f - s)); }
+// nn.GELU() default: x * Phi(x) with the exact erf form (the Transformer LM's feed-forward, forward only)
+__device__ __forceinline__ float geluf_(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 // ---- host-side error plumbing (api.hip) ----
 extern "C" const char* avec_last_error();

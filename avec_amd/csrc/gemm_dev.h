@@ -136,7 +136,7 @@ struct Epi {
   void* out; long long ldo; int out_f32;
   void* out_pre; long long ldpre;
   const float* bias;
-  int act;                         // 0 none, 1 swish, 2 relu (forward activation)
+  int act;                         // 0 none, 1 swish, 2 relu, 3 gelu (exact erf form; forward activation)
   float drop_p; const unsigned long long* rng; unsigned stream;
   const void* res; long long ldres; float alpha; int res_act;
   const void* dact_z; long long ldz; int dact;   // multiply by act'(z) (1 swish, 2 relu)
@@ -294,7 +294,7 @@ __device__ __forceinline__ void nt_epilogue(const GemmArgs& g, f32x16 (&acc)[MT]
 #pragma unroll
         for (int c = 0; c < 4; ++c) v[c] += bias4[c];
         if (e.out_pre) st4<T>((T*)e.out_pre + row * e.ldpre + col, v);
-        if (e.act == 1) { for (int c = 0; c < 4; ++c) v[c] = swishf_(v[c]); } else if (e.act == 2) { for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f); }
+        if (e.act == 1) { for (int c = 0; c < 4; ++c) v[c] = swishf_(v[c]); } else if (e.act == 2) { for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f); } else if (e.act == 3) { for (int c = 0; c < 4; ++c) v[c] = geluf_(v[c]); }
         if (e.drop_p > 0.f) {
           const unsigned long long i0 = (unsigned long long)row * g.N + col;
           if (!(g.N & 1)) { float ds[4]; drop4(dk, i0, ds); for (int c = 0; c < 4; ++c) v[c] *= ds[c]; }
@@ -359,7 +359,7 @@ __device__ __forceinline__ void nt_epilogue(const GemmArgs& g, f32x16 (&acc)[MT]
 #pragma unroll
         for (int c = 0; c < 4; ++c) v[c] += bias4[c];
         if (e.out_pre) st4<T>((T*)e.out_pre + row * e.ldpre + col, v);
-        if (e.act == 1) { for (int c = 0; c < 4; ++c) v[c] = swishf_(v[c]); } else if (e.act == 2) { for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f); }
+        if (e.act == 1) { for (int c = 0; c < 4; ++c) v[c] = swishf_(v[c]); } else if (e.act == 2) { for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], 0.f); } else if (e.act == 3) { for (int c = 0; c < 4; ++c) v[c] = geluf_(v[c]); }
         if (e.drop_p > 0.f) {
           const unsigned long long i0 = (unsigned long long)row * g.N + col;
           if (!(g.N & 1)) { float ds[4]; drop4(dk, i0, ds); for (int c = 0; c < 4; ++c) v[c] *= ds[c]; }      // (col % 4 == 0: the index is even)
@@ -388,7 +388,7 @@ __device__ __forceinline__ void nt_epilogue(const GemmArgs& g, f32x16 (&acc)[MT]
         if (col + c >= g.N) { v[c] = 0.f; continue; }
         float x = v[c] + bias4[c];
         if (e.out_pre) stf((T*)e.out_pre + row * e.ldpre + col + c, x);
-        if (e.act == 1) x = swishf_(x); else if (e.act == 2) x = fmaxf(x, 0.f);
+        if (e.act == 1) x = swishf_(x); else if (e.act == 2) x = fmaxf(x, 0.f); else if (e.act == 3) x = geluf_(x);
         if (e.drop_p > 0.f) x *= drop_one(dk, (unsigned long long)row * g.N + col + c);
         if (e.dact) {
           const float z = ldf((const T*)e.dact_z + row * e.ldz + col + c);
@@ -615,6 +615,9 @@ __device__ __forceinline__ void plain_epilogue_tr(const GemmArgs& g, const f32x1
     } else if (e.act == 2) {
 #pragma unroll
       for (int c = 0; c < 8; ++c) w[c] = fmaxf(w[c], 0.f);
+    } else if (e.act == 3) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) w[c] = geluf_(w[c]);
     }
     if (e.drop_p > 0.f) {                     // (N is even: the pair hashes of nt_epilogue's drop4)
       const unsigned long long i0 = (unsigned long long)row * g.N + col[k];

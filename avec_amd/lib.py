@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("AVEC_LIB_PATH") or os.path.join(_HERE, "libavec_hip.s
 
 F32, BF16 = 0, 1
 ROWS_PLAIN, ROWS_CONV_FWD, ROWS_CONV_BWD, ROWS_STEM3D = 0, 1, 2, 3
-ACT_NONE, ACT_SWISH, ACT_RELU = 0, 1, 2
+ACT_NONE, ACT_SWISH, ACT_RELU, ACT_GELU = 0, 1, 2, 3
 
 
 class Rows(ctypes.Structure):

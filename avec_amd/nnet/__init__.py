@@ -1,6 +1,6 @@
 """`nnet`: host-side mirror of the reference's nnet API surface for the AV Efficient Conformer hot path, executing on MI355X through
 libavec_hip.so.  Flat namespace like the reference's nnet/__init__.py:19-49."""
-from . import (activations, attentions, blocks, collate_fn, datasets, decoders, embeddings, initializations, layers, losses, metrics, model, models_zoo,
+from . import (activations, attentions, blocks, collate_fn, datasets, decoders, embeddings, initializations, layers, losses, metrics, model, models, models_zoo,
                module, modules, networks, normalizations, optimizers, preprocessing, schedulers, transforms)
 from .activations import *      # noqa: F401,F403
 from .attentions import *       # noqa: F401,F403
@@ -13,6 +13,7 @@ from .layers import *           # noqa: F401,F403
 from .losses import *           # noqa: F401,F403
 from .metrics import *          # noqa: F401,F403
 from .model import Model
+from .models import *          # noqa: F401,F403
 from .models_zoo import *       # noqa: F401,F403
 from .module import Module
 from .modules import *          # noqa: F401,F403

@@ -36,6 +36,15 @@ class Swish(_FusedOnly):
     act_id = 1
 
 
+class GELU(nn.Module):
+    """nn.GELU() (exact erf form): the Transformer LM's feed-forward activation.  It exists as a GEMM epilogue only (avec_epilogue_t.act = 3, forward / inference);
+    there is no stand-alone kernel, so calling the module on its own is an error rather than an eager fallback."""
+    fused_act = 3
+
+    def forward(self, x):
+        raise NotImplementedError("GELU runs as the epilogue of the feed-forward module's first product (FeedForwardModule, eval mode); it has no stand-alone HIP kernel")
+
+
 class GLU(_FusedOnly):
     act_id = 3
 
@@ -44,4 +53,4 @@ class GLU(_FusedOnly):
         self.dim = dim
 
 
-act_dict = {None: Identity, "Identity": Identity, "ReLU": ReLU, "Swish": Swish, "GLU": GLU}
+act_dict = {None: Identity, "Identity": Identity, "ReLU": ReLU, "Swish": Swish, "GLU": GLU, "GELU": GELU}

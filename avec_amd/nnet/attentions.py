@@ -14,7 +14,9 @@ class MultiHeadAttention(nn.Module):
     def __init__(self, dim_model, num_heads, attn_drop_rate, weight_init="scaled_uniform", bias_init="zeros", output_proj=True, dim_kv=None):
         super().__init__()
         assert dim_kv in (None, dim_model) and output_proj, "cross-attention / projection-free variants are not on the hot path"
-        assert attn_drop_rate == 0, "attention-probability dropout is 0 in every shipped config (nnet/networks.py:326,451,527)"
+        # the plain class is the Transformer LM's attention (inference only): GPT constructs it with attn_drop_rate 0.1, which is accepted and never applied
+        assert attn_drop_rate == 0 or type(self) is MultiHeadAttention, "attention-probability dropout is 0 in every shipped config (nnet/networks.py:326,451,527)"
+        self.attn_drop_rate = attn_drop_rate
         self.num_heads, self.dim_model, self.dim_head = num_heads, dim_model, dim_model // num_heads
         self.output_proj, self.dim_kv = output_proj, dim_model
         self.dropout = nn.Identity()
@@ -36,8 +38,25 @@ class MultiHeadAttention(nn.Module):
                 self.value_layer.weight, self.value_layer.bias, self.output_layer.weight, self.output_layer.bias,
                 self.pos_layer.weight, self.pos_layer.bias)
 
+    def _plain(self, x, ln, mask, residual):
+        """The class on its own (no pos_layer): softmax(Q K^T / sqrt(d) + causal) V, nnet/attentions.py:89-138 under Mask(right_context=0).  Inference only; head
+        width 64 only (ops.causal_attention raises NotImplementedError otherwise); the mask must be a CausalMask (a dense mask tensor is never read)."""
+        if not isinstance(mask, CausalMask):
+            raise NotImplementedError("plain MultiHeadAttention on the HIP path is causal self-attention: pass attentions.CausalMask(lengths) "
+                                      "(what networks.Transformer makes of Mask(right_context=0)); got %s" % type(mask).__name__)
+        if self.training:
+            raise RuntimeError("plain MultiHeadAttention (the Transformer LM's attention) is an inference path: call .eval() first (training the LM is out of scope)")
+        B, T, D = x.shape
+        x2 = x.float().reshape(B * T, D).contiguous()
+        if ln is None:                       # bare layer: the input itself is projected, nothing is added back
+            raise NotImplementedError("plain MultiHeadAttention runs inside AttentionModule (pre-norm + residual), as TransformerBlock uses it")
+        assert residual, "TransformerBlock's attention module adds its residual (nnet/blocks.py:174-179)"
+        return ops.lm_attention_module(x2, B, T, ln, self, mask.lengths).view(B, T, D)
+
     def fused(self, x, ln, mask, lengths, drop_p, sid, residual):
         """y = [x +] Drop(attention(LN(x)))  -- called by AttentionModule; `lengths` (B,) is the fast path for key-padding masks."""
+        if not hasattr(self, "pos_layer"):
+            return self._plain(x, ln, mask, residual)
         if lengths is not None:
             lengths = lengths.to(device=x.device, dtype=torch.int64).contiguous()
             mask = None
@@ -180,6 +199,14 @@ class GroupedRelPosMultiHeadSelfAttention(RelPosMultiHeadSelfAttention):
                          group_size=group_size)
 
 
+class CausalMask:
+    """What networks.Transformer hands its blocks for Mask(right_context=0) without a left limit: causality is computed from the indices inside the attention
+    kernel, so no (B, 1, T, T) tensor exists; `lengths` (optional, (B,)) only lets the kernel skip rows that are never scored."""
+
+    def __init__(self, lengths=None):
+        self.lengths = lengths
+
+
 class Mask(nn.Module):
     """Binary mask, 1 = keep (nnet/attentions.py:656-733).  Without context limits it only encodes key padding and the conformer stack hands the lengths straight
     to the attention kernels (no (B,1,T,T) tensor, no per-sample host loop).  With left_context / right_context (streaming) the band
@@ -217,5 +244,5 @@ class Mask(nn.Module):
         return m[:, None] if self.unsqueeze_head else m
 
 
-att_dict = {"RelPos1dMultiHeadAttention": RelPos1dMultiHeadAttention, "RelPosPatch1dMultiHeadAttention": RelPosPatch1dMultiHeadAttention,
+att_dict = {"MultiHeadAttention": MultiHeadAttention, "RelPos1dMultiHeadAttention": RelPos1dMultiHeadAttention, "RelPosPatch1dMultiHeadAttention": RelPosPatch1dMultiHeadAttention,
             "RelPosMultiHeadSelfAttention": RelPosMultiHeadSelfAttention, "GroupedRelPosMultiHeadSelfAttention": GroupedRelPosMultiHeadSelfAttention}

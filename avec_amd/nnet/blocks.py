@@ -68,4 +68,20 @@ class ConformerBlock(nn.Module):
         return x
 
 
-block_dict = {"ConformerBlock": ConformerBlock}
+class TransformerBlock(nn.Module):
+    """nnet/blocks.py:168-206, pre-norm:  x += MHSA(LN(x));  x += FFN(LN(x)).  Inference only (the Transformer LM of the beam rescorer)."""
+
+    def __init__(self, dim_model, att_params, ff_ratio=4, drop_rate=0.1, inner_dropout=False, act_fun="GELU", weight_init="normal_02", bias_init="zeros", post_norm=False):
+        super().__init__()
+        assert not post_norm, "post-norm Transformer blocks are not on this path (GPT is pre-norm, nnet/networks.py:150)"
+        self.self_att_module = modules.AttentionModule(dim_model=dim_model, att_params=att_params, drop_rate=drop_rate, residual=True)
+        self.ff_module = modules.FeedForwardModule(dim_model=dim_model, dim_ffn=dim_model * ff_ratio, drop_rate=drop_rate, act_fun=act_fun, inner_dropout=inner_dropout,
+                                                   weight_init=weight_init, bias_init=bias_init)
+        self.post_norm = nn.Identity()
+
+    def forward(self, x, mask=None):
+        x = self.self_att_module(x, mask=mask)
+        return self.ff_module.residual_forward(x, 1.0)
+
+
+block_dict = {"ConformerBlock": ConformerBlock, "TransformerBlock": TransformerBlock}

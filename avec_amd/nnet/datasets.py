@@ -42,3 +42,18 @@ class MultiDataset(torch.utils.data.ConcatDataset):
     def __init__(self, batch_size, collate_fn, datasets, shuffle=True):
         super().__init__(datasets)
         self.batch_size, self.collate_fn, self.shuffle = batch_size, collate_fn, shuffle
+
+
+class CorpusLM(torch.utils.data.Dataset):
+    """nnet/datasets.py CorpusLM as far as an LM config needs it to import: holds its arguments (corpus and tokenizer paths, batch size, collate function) and
+    nothing more -- the text corpora are not shipped and there is no LM training loop here."""
+
+    def __init__(self, batch_size=None, collate_fn=None, tokenizer_path=None, corpus_path=None, max_length=None, shuffle=True, **kwargs):
+        self.batch_size, self.collate_fn, self.tokenizer_path, self.corpus_path = batch_size, collate_fn, tokenizer_path, corpus_path
+        self.max_length, self.shuffle, self.kwargs = max_length, shuffle, kwargs
+
+    def __len__(self):
+        return 0
+
+    def __getitem__(self, n):
+        raise IndexError("nnet.datasets.CorpusLM holds its arguments only")

@@ -1,6 +1,9 @@
 """Decoders (nnet/decoders.py).  Greedy CTC: device argmax (HIP) + exact integer collapse.  Beam search: the CTC prefix beam search with n-gram LM
-fusion of avec_amd/csrc/ctc_beam.hip (in place of `ctcdecode` + KenLM); the GPT rescoring pass stays out of scope."""
+fusion of avec_amd/csrc/ctc_beam.hip (in place of `ctcdecode` + KenLM), then the Transformer-LM (GPT) rescoring of the beams (avec_amd/csrc/lm.hip): all
+hypotheses of a batch in one scoring pass."""
+import importlib.util
 import os
+import sys
 import warnings
 
 import torch
@@ -50,7 +53,16 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
     The ranking score is ln P_ctc(prefix) + the summed LM terms (higher is better), and a token that is not an LM word costs ln P = -1000.  ctcdecode's
     own score convention and OOV constant cannot be checked against here (ctcdecode and kenlm are not available), so they are not claimed.
     A missing or empty ARPA file means beam search without an LM (warned).  test_time_aug: logits [B, Naug, T, V], lengths [B, Naug]; per utterance
-    the augmentation whose best beam scores highest (ties: the lower index).  neural_config_path (GPT rescoring) is not imported: out of scope."""
+    the augmentation whose best beam scores highest (ties: the lower index).
+    Neural rescoring (nnet/decoders.py:156-162,208-242): when `neural_config_path` names an existing config file and `os.path.join(config.callback_path,
+    neural_checkpoint)` exists, the config is imported, its `model` (anything with `score(ids, lengths)` and `load(path)`; nnet.GPT in the shipped configs) loads the
+    checkpoint and is put in eval mode.  Every non-empty beam slot then becomes [sos] + retokenise(tokens) + [eos] (retokenise = neural tokenizer over the decoder
+    tokenizer's text; the identity when both are the same file or the decoder has no tokenizer), all B * Naug * W of them are scored in ONE pass, and per utterance
+        total = beam_score - neural_alpha * nll_sum + neural_beta * neural_beta * (tokens + 1)
+    is maximised over the Naug * W slots (first maximum; empty slots never win).  This is the reference's `beam_scores + alpha * nll - beta * (beta * len)` under argmin
+    with the sign of the beam score flipped to this repository's higher-is-better convention; beta enters SQUARED there (neural_lengths is already beta * len when it is
+    multiplied by beta again) and that is kept.  Otherwise (no such file, no checkpoint) one UserWarning says that there is no neural rescoring, nothing is imported,
+    and the n-gram winner is returned as before."""
 
     _warned_neural = False
 
@@ -63,9 +75,70 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
         if not ngram_path or not os.path.exists(ngram_path):
             warnings.warn("CTCBeamSearchDecoder: n-gram LM %r not found: beam search without an LM" % (ngram_path,))
             self.ngram_path = None
-        if neural_config_path is not None and not CTCBeamSearchDecoder._warned_neural:
+        self.neural_alpha, self.neural_beta = neural_alpha, neural_beta
+        object.__setattr__(self, "neural_rescorer", None)      # (kept out of the module tree: not a state_dict entry of whatever owns the decoder)
+        self.neural_tokenizer, self.last_totals = None, None
+        if neural_config_path is not None and not self._load_neural(neural_config_path, neural_checkpoint, tokenizer_path) and not CTCBeamSearchDecoder._warned_neural:
             CTCBeamSearchDecoder._warned_neural = True
-            warnings.warn("CTCBeamSearchDecoder: neural rescoring (%s) is out of scope: n-gram beam search only" % neural_config_path)
+            warnings.warn("CTCBeamSearchDecoder: no neural rescoring: config %s or its checkpoint %r not found: n-gram beam search only" % (neural_config_path, neural_checkpoint))
+
+    def _load_neural(self, config_path, checkpoint, tokenizer_path):
+        """import the LM config as the reference does (nnet/decoders.py:156-162) and load its checkpoint; False when either file is missing (nothing imported then)"""
+        if not os.path.isfile(config_path) or checkpoint is None:
+            return False
+        name = config_path.replace(".py", "").replace("/", ".").strip(".")
+        spec = importlib.util.spec_from_file_location(name, config_path)
+        cfg = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(cfg)
+        ckpt = os.path.join(cfg.callback_path, checkpoint)
+        if not os.path.isfile(ckpt):
+            return False
+        sys.modules[name] = cfg
+        model = cfg.model
+        if not (hasattr(model, "score") and hasattr(model, "load")):
+            raise TypeError("CTCBeamSearchDecoder: the neural config's `model` (%s) needs score(ids, lengths) and load(path)" % type(model).__name__)
+        model.load(ckpt, load_optimizer=False)
+        model.requires_grad_(False)
+        model.eval()
+        object.__setattr__(self, "neural_rescorer", model)
+        self.neural_pad_token, self.neural_sos_token, self.neural_eos_token = int(cfg.pad_token), int(cfg.sos_token), int(cfg.eos_token)
+        lm_tok = getattr(cfg, "tokenizer_path", None)
+        same = self.tokenizer is None or lm_tok is None or (tokenizer_path is not None and os.path.exists(lm_tok) and os.path.samefile(lm_tok, tokenizer_path))
+        if not same:
+            import sentencepiece as spm
+            self.neural_tokenizer = spm.SentencePieceProcessor(lm_tok)
+        return True
+
+    def _neural_ids(self, hyps):
+        """token lists of the decoder -> token lists of the LM, for the whole batch at once (host work on short strings)"""
+        if self.neural_tokenizer is None:
+            return hyps
+        return self.neural_tokenizer.encode(self.tokenizer.decode(hyps))
+
+    def _rescore(self, tokens, out_len, score, B, naug):
+        """tokens [S, W, T], out_len [S, W], score [S, W] of ops.ctc_beam_search (S = B * naug) -> per utterance the winning token list"""
+        S, W, T = tokens.shape
+        tok, ol, alive = tokens.cpu(), out_len.cpu().tolist(), (score > float("-inf")).cpu().tolist()
+        slots = [(s, w) for s in range(S) for w in range(W) if alive[s][w]]
+        hyps = self._neural_ids([tok[s, w, :ol[s][w]].tolist() for s, w in slots])
+        Lmax = 2 + max((len(h) for h in hyps), default=0)
+        ids = torch.full((S * W, Lmax), self.neural_pad_token, dtype=torch.int64)
+        lens = torch.zeros(S * W, dtype=torch.int64)                         # 0 = empty slot
+        for (s, w), h in zip(slots, hyps):
+            row = [self.neural_sos_token] + list(h) + [self.neural_eos_token]
+            ids[s * W + w, :len(row)] = torch.tensor(row, dtype=torch.int64)
+            lens[s * W + w] = len(row)
+        lm = self.neural_rescorer
+        dev = score.device
+        if next(lm.parameters()).device != dev:
+            lm.to(dev)
+        best, total, _ = ops.lm_rescore(lm, ids.to(dev), lens.to(dev), score.reshape(-1), self.neural_alpha, self.neural_beta, B)
+        self.last_totals = total                                             # [B, naug * W], stays on the device (tests read it)
+        out = []
+        for b, k in enumerate(best.cpu().tolist()):
+            s, w = b * naug + k // W, k % W
+            out.append(tok[s, w, :ol[s][w]].tolist())
+        return out
 
     def lm(self, vocab_size):
         if vocab_size not in self._lm:
@@ -81,6 +154,8 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
             B, naug = logits.shape[0], 1
         tokens, out_len, score, _ = ops.ctc_beam_search(logits, logits_len, self.beam_size, self.ngram_tmp, self.lm(logits.shape[-1]), self.ngram_alpha,
                                                         self.ngram_beta)
+        if self.neural_rescorer is not None:
+            return self._rescore(tokens, out_len, score, B, naug)
         T = tokens.shape[-1]
         tok0, len0 = tokens[:, 0].reshape(B, naug, T).cpu(), out_len[:, 0].reshape(B, naug).cpu()
         best = score[:, 0].reshape(B, naug).cpu().argmax(dim=1)        # the first maximum: ties go to the lower augmentation index

@@ -1,8 +1,50 @@
 """Relative sinusoidal positional encoding (nnet/embeddings.py:101-158).  The reference keeps a (1, 2*max_len-1, D) table per attention layer
 (24 copies, re-broadcast by DDP every step); here the 2T-1 rows needed are generated once per (T, D) and cached (ops.rel_pos_table)."""
+import torch
 import torch.nn as nn
 
 from .. import ops
+
+
+class SinPosEmbedding(nn.Module):
+    """nnet/embeddings.py:20-44: the absolute sinusoid table, built on the host in fp32 exactly as there (sin on even, cos on odd channels), a non-persistent
+    buffer (1, num_embeddings, dim_emb) -- so it is not a state_dict key.  The Transformer LM adds it inside the embedding kernel (ops.embed_pos); forward() is the
+    stand-alone form of the reference API."""
+
+    def __init__(self, num_embeddings, dim_emb):
+        super().__init__()
+        self.num_embeddings, self.dim_emb = num_embeddings, dim_emb
+        pos_encoding = torch.zeros(num_embeddings, dim_emb)
+        pos = torch.arange(0, num_embeddings, dtype=torch.float).unsqueeze(1)
+        i = torch.arange(0, dim_emb // 2, dtype=torch.float).unsqueeze(0)
+        angles = pos / 10000 ** (2 * i / dim_emb)
+        pos_encoding[:, 0::2] = angles.sin()
+        pos_encoding[:, 1::2] = angles.cos()
+        self.register_buffer("pos_encoding", pos_encoding.unsqueeze(0), persistent=False)
+
+    def table(self):
+        """(num_embeddings, dim_emb) fp32 rows"""
+        return self.pos_encoding[0]
+
+    def forward(self, x):
+        return x + self.pos_encoding[:, :x.shape[1]]
+
+
+class PosEmbedding1d(nn.Module):
+    """nnet/embeddings.py:46-62: learned positions, parameter `pos_encoding` (num_embeddings, dim_emb), zero-initialised"""
+
+    def __init__(self, num_embeddings, dim_emb):
+        super().__init__()
+        self.num_embeddings = (num_embeddings,) if isinstance(num_embeddings, int) else tuple(num_embeddings)
+        self.dim_emb = dim_emb
+        self.pos_encoding = nn.Parameter(torch.zeros(self.num_embeddings + (dim_emb,)))
+
+    def table(self):
+        return self.pos_encoding
+
+    def forward(self, x):
+        assert x.dim() == 3, "input must be (Batch, Length, Features)"
+        return x + self.pos_encoding[:x.shape[-2]]
 
 
 class RelativeSinusoidalPositionalEncoding(nn.Module):

@@ -65,7 +65,8 @@ class FeedForwardModule(nn.Module):
 
     def __init__(self, dim_model, dim_ffn, drop_rate, act_fun, inner_dropout, prenorm=True, weight_init="default", bias_init="default"):
         super().__init__()
-        assert prenorm and act_fun == "Swish", "hot-path FFN is pre-norm + Swish (nnet/blocks.py:229-236)"
+        assert prenorm and act_fun in ("Swish", "GELU"), "hot-path FFN is pre-norm + Swish (nnet/blocks.py:229-236), or pre-norm + GELU in eval mode (the Transformer LM)"
+        self.act_fun = act_fun
         self.layers = nn.Sequential(
             nn.LayerNorm(dim_model, eps=1e-6),
             layers.Linear(dim_model, dim_ffn, weight_init=weight_init, bias_init=bias_init),
@@ -79,6 +80,12 @@ class FeedForwardModule(nn.Module):
     def residual_forward(self, x, alpha):
         """x + alpha * FFN(x) in one fused sequence (the macaron half-step of nnet/blocks.py:292,301)."""
         ln, l1, l2 = self.layers[0], self.layers[1], self.layers[4]
+        if self.act_fun == "GELU":           # forward only: the GELU epilogue has no derivative kernel
+            if self.training:
+                raise RuntimeError("FeedForwardModule(act_fun='GELU') is an inference path: call .eval() first (training the LM is out of scope)")
+            assert alpha == 1.0
+            shp = x.shape
+            return ops.lm_ffn_module(x.float().reshape(-1, shp[-1]).contiguous(), ln, l1, l2).view(shp)
         p = self.drop_rate if self.training else 0.0
         assert self.inner_dropout or p == 0.0
         return ops.FeedForwardFn.apply(x, ln.weight, ln.bias, l1.weight, l1.bias, l2.weight, l2.bias, ln.eps, alpha, p, self.sid1, self.sid2)
@@ -102,6 +109,8 @@ class AttentionModule(nn.Module):
     def forward(self, x, x_cross=None, mask=None, add_residual=None):
         assert x_cross is None, "cross-attention is not on the hot path"
         lengths = None
+        if isinstance(mask, attentions.CausalMask):       # the Transformer LM's plain attention
+            return self.attention.fused(x, self.norm, mask, None, 0.0, self.sid, self.residual if add_residual is None else add_residual)
         if isinstance(mask, LengthMask):
             lengths, mask = mask.lengths, None
         p = self.dropout.p if self.training else 0.0

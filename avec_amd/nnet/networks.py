@@ -42,6 +42,44 @@ class ResNet(nn.Module):
         return self.forward_nhwc(x.permute(0, 2, 3, 1).to(rt.act_dtype()).contiguous())
 
 
+class Transformer(nn.Module):
+    """nnet/networks.py:148-200: positional embedding -> (dropout) -> pre-norm TransformerBlocks -> final nn.LayerNorm (torch default eps 1e-5, unlike the 1e-6 of
+    the modules' own norms).  Inference only, causal: `mask` must be attentions.Mask(right_context=0) with no left limit -- it is never materialised, the attention
+    kernel computes causality from the indices."""
+
+    def __init__(self, dim_model, num_blocks, att_params={"class": "MultiHeadAttention", "params": {"num_heads": 4, "weight_init": "normal_02", "bias_init": "zeros"}},
+                 ff_ratio=4, emb_drop_rate=0.1, drop_rate=0.1, act_fun="GELU", pos_embedding=None, mask=None, inner_dropout=False, weight_init="normal_02",
+                 bias_init="zeros", post_norm=False):
+        super().__init__()
+        assert not post_norm, "post-norm Transformers are not on this path"
+        if not (isinstance(mask, attentions.Mask) and mask.right_context == 0 and mask.left_context is None and not mask.mask_start):
+            raise NotImplementedError("networks.Transformer on the HIP path is the causal LM stack: mask=attentions.Mask(right_context=0)")
+        self.pos_embedding = pos_embedding
+        self.dropout = nn.Dropout(p=emb_drop_rate)
+        self.mask = mask
+        self.blocks = nn.ModuleList([blocks.TransformerBlock(dim_model=dim_model, ff_ratio=ff_ratio, att_params=att_params, drop_rate=drop_rate, inner_dropout=inner_dropout,
+                                                             act_fun=act_fun, weight_init=weight_init, bias_init=bias_init, post_norm=post_norm) for _ in range(num_blocks)])
+        self.layernorm = nn.LayerNorm(normalized_shape=dim_model)
+
+    def forward_rows(self, x, lengths=None, embedded=False):
+        """x (B, T, D) fp32 -> final-LayerNorm rows [B * T, D] in the compute dtype (what the head consumes).  embedded: the positions are already in x."""
+        if self.training:
+            raise RuntimeError("networks.Transformer is an inference path: call .eval() first (training the LM is out of scope)")
+        ops._inference_only("networks.Transformer", x)
+        if self.pos_embedding is not None and not embedded:
+            x = self.pos_embedding(x)
+        B, T, D = x.shape
+        mask = attentions.CausalMask(lengths)
+        for block in self.blocks:
+            x = block(x, mask=mask)
+        ln = self.layernorm
+        return ops.layernorm_fwd(x.reshape(B * T, D), ln.weight, ln.bias, B * T, D, False, ln.eps)[0]
+
+    def forward(self, x, lengths=None):
+        B, T, D = x.shape
+        return self.forward_rows(x, lengths).float().view(B, T, D)
+
+
 class ConformerInterCTC(nn.Module):
     """nnet/networks.py:202-307"""
 

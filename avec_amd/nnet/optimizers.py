@@ -99,4 +99,25 @@ class Adam(optim.Adam):
                     self.state[p]["exp_avg_sq"].copy_(st["exp_avg_sq"])
 
 
-optim_dict = {"Adam": Adam}
+class AdamW(optim.AdamW):
+    """nnet/optimizers.py AdamW as far as an LM config needs it to import: holds its arguments (parameter groups, betas, eps, the lr or its scheduler) and nothing
+    more -- there is no HIP AdamW step and no LM training loop here; step() says so."""
+
+    def __init__(self, params, lr=0.001, betas=(0.9, 0.999), eps=1e-08, weight_decay=0.01, amsgrad=False):
+        super().__init__(params=params, lr=0.0, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
+        self.scheduler = lr if isinstance(lr, schedulers.Scheduler) else schedulers.ConstantScheduler(val=lr)
+
+    def step(self, closure=None):
+        raise NotImplementedError("nnet.AdamW holds its arguments only: training the Transformer LM is out of scope on this path")
+
+
+def get_decay_param_groups(model, weight_decay=0.1):
+    """nnet/optimizers.py: weights of Linear layers decay, everything else (biases, norms, embeddings) does not.  Holds the split; nothing steps it here."""
+    decay, no_decay = [], []
+    for m in model.modules():
+        for name, p in m.named_parameters(recurse=False):
+            (decay if isinstance(m, torch.nn.Linear) and name == "weight" else no_decay).append(p)
+    return [{"params": decay, "weight_decay": weight_decay}, {"params": no_decay, "weight_decay": 0.0}]
+
+
+optim_dict = {"Adam": Adam, "AdamW": AdamW}

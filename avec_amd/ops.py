@@ -10,7 +10,7 @@ import torch
 
 from . import fp8
 from . import runtime as rt
-from .lib import (ACT_NONE, ACT_RELU, ACT_SWISH, BF16, LN_GROUP_MAX, ROWS_CONV_BWD, ROWS_CONV_FWD, ROWS_PLAIN, ROWS_STEM3D, TN_GROUP_MAX, WGRAD_GROUP_MAX, Attn, Epilogue, LnItem, Rows, TnBatched, TnItem,
+from .lib import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_SWISH, BF16, LN_GROUP_MAX, ROWS_CONV_BWD, ROWS_CONV_FWD, ROWS_PLAIN, ROWS_STEM3D, TN_GROUP_MAX, WGRAD_GROUP_MAX, Attn, Epilogue, LnItem, Rows, TnBatched, TnItem,
                   WgradItem, lib)
 
 _byref = ctypes.byref
@@ -1939,3 +1939,127 @@ def ngram_rows(lm, contexts):
     rows = torch.empty(n, lm.V, dtype=torch.float32, device=dev)
     lib.ngram_rows(_byref(lm.device_struct(dev)), ctx.data_ptr(), clen.data_ptr(), n, L, lm.oov_logprob, rows.data_ptr(), rt.stream())
     return rows
+
+
+# ============================================================================================
+# Transformer-LM (GPT) rescoring of the beam -- csrc/lm.hip.  Inference only: no autograd Functions, no backward kernels.
+# ============================================================================================
+CAUSAL_HEAD_DIM = 64
+
+
+def _inference_only(what, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError("%s is an inference path (it has no backward kernels): call it under torch.no_grad(), or with inputs and parameters that do not "
+                           "require grad -- a graph-less result would silently train nothing" % what)
+
+
+def embed_pos(ids, weight, pos, out_f32=True):
+    """x[n, t] = weight[ids[n, t]] + pos[t]: nn.Embedding followed by SinPosEmbedding / PosEmbedding1d (pos: [>= L, D] or [1, >= L, D], fp32) in one launch.
+    ids [N, L] integer -> [N, L, D] fp32 (the residual stream) or, with out_f32=False, the compute dtype."""
+    _inference_only("ops.embed_pos", weight, pos)
+    rt.require_gpu(weight)
+    N, L = ids.shape
+    V, D = weight.shape
+    pos = pos.reshape(-1, D)
+    if pos.shape[0] < L:
+        raise ValueError("ops.embed_pos: %d positions for sequences of %d tokens (max_pos_encoding)" % (pos.shape[0], L))
+    ids = ids.to(device=weight.device, dtype=torch.int64).contiguous()
+    w, p = _f32c(weight.detach()), _f32c(pos.detach())
+    out = torch.empty(N, L, D, dtype=torch.float32 if out_f32 else rt.act_dtype(), device=weight.device)
+    lib.embed_pos(rt.dt(), ids.data_ptr(), w.data_ptr(), p.data_ptr(), out.data_ptr(), int(out_f32), N, L, V, D, rt.stream())
+    return out
+
+
+def causal_attention(qkv, N, H, L, lens=None):
+    """softmax(Q K^T / sqrt(d) + causal) V per (sequence, head) on the fused projection qkv [N * L, 3 * H * d] (compute dtype, Q | K | V) -> [N * L, H * d].
+    The mask is computed from the indices (Mask(right_context=0)); lens [N] (optional) lets whole 32-row query tiles past a sequence's length be skipped
+    (written as zeros).  Only d = 64 (GPT-Small 768 / 12, GPT-Medium 1024 / 16) has a kernel: other head widths raise NotImplementedError."""
+    _inference_only("ops.causal_attention", qkv)
+    rt.require_gpu(qkv)
+    M, W3 = qkv.shape
+    d = W3 // (3 * H)
+    if d != CAUSAL_HEAD_DIM or 3 * H * d != W3:
+        raise NotImplementedError("ops.causal_attention: head width %d (row of %d over %d heads); the causal attention kernel supports d = %d only" % (d, W3, H, CAUSAL_HEAD_DIM))
+    assert qkv.dtype == rt.act_dtype() and qkv.is_contiguous() and M == N * L, (qkv.dtype, qkv.shape, N, L)
+    o = empty((M, H * d), rt.act_dtype(), qkv)
+    lens_t = None if lens is None else lens.to(device=qkv.device, dtype=torch.int64).contiguous()
+    lib.causal_attention(rt.dt(), qkv.data_ptr(), W3, _p(lens_t), o.data_ptr(), H * d, N, H, L, d, 1.0 / d ** 0.5, rt.stream())
+    return o
+
+
+def lm_head_workspace_bytes(R, V, D):
+    return lib.raw("avec_lm_head_nll_workspace_bytes")(R, V, D)
+
+
+def lm_head_nll(h, weight, bias, tgt):
+    """nll[r] = logsumexp_v(h[r] . weight[v] + bias[v]) - (h[r] . weight[tgt[r]] + bias[tgt[r]]), fp32, 0 where tgt[r] = -1: head Linear + log_softmax + gather as
+    one kernel that never writes the [R, V] logits.  h [R, D] compute dtype; weight: the head's (registered) Linear weight [V, D]."""
+    _inference_only("ops.lm_head_nll", h, weight, bias)
+    rt.require_gpu(h)
+    sh = rt.shadow(weight)
+    V, D = sh.A, sh.C
+    R = h.shape[0]
+    assert h.dtype == rt.act_dtype() and h.is_contiguous() and h.shape[1] == D and sh.Tm == 1, (h.dtype, h.shape, D)
+    tgt = tgt.to(device=h.device, dtype=torch.int64).contiguous().view(-1)
+    assert tgt.numel() == R, (tgt.shape, R)
+    b = bias.detach() if bias is not None else torch.zeros(V, dtype=torch.float32, device=h.device)
+    nbytes = lm_head_workspace_bytes(R, V, D)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=h.device) if nbytes else None
+    nll = torch.empty(R, dtype=torch.float32, device=h.device)
+    lib.lm_head_nll(rt.dt(), h.data_ptr(), D, sh.fwd.data_ptr(), sh.Cp, b.data_ptr(), tgt.data_ptr(), nll.data_ptr(), R, V, D, _p(ws), nbytes, rt.stream())
+    return nll
+
+
+def lm_segment_sum(nll, lens):
+    """nll [S, L] (row (s, t) scores token t + 1), lens [S] tokens incl. <sos> / <eos> -> [S] sums over t < lens - 1"""
+    S, L = nll.shape
+    lens = lens.to(device=nll.device, dtype=torch.int64).contiguous()
+    out = torch.empty(S, dtype=torch.float32, device=nll.device)
+    lib.lm_segment_sum(_f32c(nll).data_ptr(), lens.data_ptr(), S, L, out.data_ptr(), rt.stream())
+    return out
+
+
+def lm_attention_module(x2, N, L, ln, att, lens=None):
+    """x + attention(LN(x)) of a pre-norm TransformerBlock on the fp32 residual rows x2 [N * L, D]: LayerNorm, one Q|K|V product, the causal core, output
+    projection with the residual in its epilogue"""
+    M, D = x2.shape
+    h, _, _ = layernorm_fwd(x2, ln.weight, ln.bias, M, D, False, ln.eps)
+    qkv = empty((M, 3 * D), rt.act_dtype(), x2)
+    ws = (att.query_layer.weight, att.key_layer.weight, att.value_layer.weight)
+    bs = (att.query_layer.bias, att.key_layer.bias, att.value_layer.bias)
+    grp = rt.fused_group(ws[0])
+    if grp is not None and grp.weights[1] is ws[1] and grp.weights[2] is ws[2]:
+        gemm_nt(h, grp.fwd, qkv, M, 3 * D, D, bias=grp.bias)
+    else:
+        for i in range(3):
+            gemm_nt(h, rt.shadow(ws[i]).fwd, qkv[:, i * D:], M, D, D, bias=bs[i], ldo=3 * D)
+    o = causal_attention(qkv, N, att.num_heads, L, lens)
+    return linear_fwd(o, att.output_layer.weight, att.output_layer.bias, M, in_f32=False, out_f32=True, res=x2, alpha=1.0)
+
+
+def lm_ffn_module(x2, ln, l1, l2, act=ACT_GELU):
+    """x + Linear(act(Linear(LN(x)))) on the fp32 residual rows: the activation (GELU, exact erf form) and the residual are GEMM epilogues"""
+    M, D = x2.shape
+    h, _, _ = layernorm_fwd(x2, ln.weight, ln.bias, M, D, False, ln.eps)
+    u = linear_fwd(h, l1.weight, l1.bias, M, in_f32=False, out_f32=False, act=act)
+    return linear_fwd(u, l2.weight, l2.bias, M, in_f32=False, out_f32=True, res=x2, alpha=1.0)
+
+
+def lm_rescore(model, ids, lens, beam_score, alpha, beta, B):
+    """One scoring pass for all B * K hypotheses of a batch: neural = model.score(ids, lens) (nll sums [B * K]), then on the device
+    total = beam_score - alpha * neural + beta * beta * (lens - 1) (this repository's higher-is-better convention; beta enters squared as in the reference,
+    nnet/decoders.py:231,234) and best = the first maximum per utterance; slots with lens == 0 or beam_score == -inf never win.
+    Returns best [B] int64, total [B, K], neural [B, K]."""
+    S = ids.shape[0]
+    K = S // B
+    assert K * B == S and beam_score.numel() == S and lens.numel() == S
+    with torch.no_grad():
+        neural = model.score(ids, lens)
+    dev = neural.device
+    neural = _f32c(neural.view(-1))
+    lens = lens.to(device=dev, dtype=torch.int64).contiguous()
+    beam = _f32c(beam_score.to(dev).view(-1))
+    total = torch.empty(S, dtype=torch.float32, device=dev)
+    best = torch.empty(B, dtype=torch.int64, device=dev)
+    lib.lm_rescore_select(neural.data_ptr(), lens.data_ptr(), beam.data_ptr(), float(alpha), float(beta), B, K, total.data_ptr(), best.data_ptr(), rt.stream())
+    return best, total.view(B, K), neural.view(B, K)

@@ -33,7 +33,7 @@ extern "C" {
 
 #define AVEC_F32 0
 #define AVEC_BF16 1
-#define AVEC_ABI_VERSION 4      /* 2: avec_epilogue_t grew (bnb_*, res_cls0); avec_struct_size() handshake.  3: the row-resident module chains (avec_ffn_chain_*, avec_ln_gemm, avec_layernorm_*_sum) were removed.  4: avec_glu_dwconv_fwd_bn added */
+#define AVEC_ABI_VERSION 4      /* 2: avec_epilogue_t grew (bnb_*, res_cls0); avec_struct_size() handshake.  3: the row-resident module chains (avec_ffn_chain_*, avec_ln_gemm, avec_layernorm_*_sum) were removed.  4: avec_glu_dwconv_fwd_bn added.  (The Transformer-LM entry points and epilogue act = 3 came without a bump: no struct changed, and a binding resolves every declared symbol at load time) */
 #define AVEC_STAT_REPLICAS 64   /* `stats` buffers handed to avec_gemm_nt hold this many [2N] replicas (block b adds to replica b % 64) */
 
 int avec_version(void);
@@ -67,7 +67,7 @@ typedef struct avec_epilogue {
   void* out; long long ldo; int out_f32;       /* final output: act, or fp32 when out_f32 */
   void* out_pre; long long ldpre;              /* optional: value before activation (act) */
   const float* bias;                           /* [N] */
-  int act;                                     /* 0 none, 1 Swish (nnet/activations.py:39-45), 2 ReLU */
+  int act;                                     /* 0 none, 1 Swish (nnet/activations.py:39-45), 2 ReLU, 3 GELU (erf form, nn.GELU(); forward only: dact has no 3) */
   float drop_p; const unsigned long long* rng; unsigned rng_stream;  /* nn.Dropout: counter-based mask, rng = {seed, step} on device */
   const void* res; long long ldres; float alpha; int res_act; /* out = res + alpha * v (res fp32, or act when res_act; residuals nnet/blocks.py:292-301) */
   const void* dact_z; long long ldz; int dact; /* backward: v *= act'(z) */
@@ -455,6 +455,30 @@ int avec_ctc_beam_search(const float* logits, const long long* lengths, int B, i
 /* rows[i][c] = ln P(c | ctx_i) as the beam search sees it: ctx [n][max_len] int32 tokens oldest first (-1 = <s>), ctx_len [n]; only the last order-1
  * tokens of a context are used.  Test and documentation aid for the table layout above. */
 int avec_ngram_rows(const avec_ngram_t* lm, const int* ctx, const int* ctx_len, int n, int max_len, float oov_logprob, float* rows, hipStream_t stream);
+/* ---- Transformer-LM (GPT) rescoring of the beam (avec_amd/csrc/lm.hip; CTCBeamSearchDecoder's neural rescorer, nnet/decoders.py:208-242) -- inference only ----------------
+ * x[n][t][:] = E[ids[n][t]][:] + P[t][:]: nn.Embedding (V x D fp32 table; an id outside [0, V) is clamped) plus the rows of SinPosEmbedding / PosEmbedding1d
+ * (nnet/embeddings.py:20-62, fp32 [>= L][D]).  ids int64 [N][L]; out [N*L][D] act, or fp32 when out_f32 (the residual stream).  D % 8 == 0, 16-byte aligned tables. */
+int avec_embed_pos(int dtype, const long long* ids, const float* E, const float* P, void* out, int out_f32, long long N, int L, int V, int D, hipStream_t stream);
+/* MultiHeadAttention.forwardQKV core under Mask(right_context=0) (nnet/attentions.py:89-138): o = softmax(q k^T * scale + causal) v per (sequence, head) on the fused
+ * projection qkv = act [N*L][ld] (q | k | v at columns 0, H*d, 2*H*d; head h = d columns from h*d), o = act [N*L][ldo].  Causality comes from the indices (no mask
+ * tensor); lens (optional, int64 [N]): query rows from the first 32-row tile at or past lens[n] on are written as zeros (under a causal mask keys >= lens[n] never reach
+ * a row < lens[n]).  d = 64 only (avec_causal_attention_supported), any L. */
+int avec_causal_attention_supported(int d);
+int avec_causal_attention(int dtype, const void* qkv, long long ld, const long long* lens, void* o, long long ldo, int N, int H, int L, int d, float scale, hipStream_t stream);
+/* head Linear + log_softmax + target gather in one kernel: nll[r] = logsumexp_v(h[r] . W[v] + bias[v]) - (h[r] . W[tgt[r]] + bias[tgt[r]]) (fp32), 0 where tgt[r] is
+ * outside [0, V) (-1 = ignore).  h = act [R][ldh], W = act [V][ldw] (the compute-dtype copy of the head weight), D a multiple of 64 (bf16) / 32 (fp32).  The [R][V] logits
+ * are never written; rows of W at or past V are never read.  The workspace size does not depend on R or V (it is 0: the running state lives in registers and LDS). */
+long long avec_lm_head_nll_workspace_bytes(long long R, int V, int D);
+int avec_lm_head_nll(int dtype, const void* h, long long ldh, const void* W, long long ldw, const float* bias, const long long* tgt, float* nll, long long R, int V, int D,
+                     void* workspace, long long workspace_bytes, hipStream_t stream);
+/* nll [S][L] as above with row (s, t) scoring token t + 1 of hypothesis s, lens [S] int64 = tokens of the hypothesis including <sos> and <eos>:
+ * out[s] = sum_{t < lens[s] - 1} nll[s][t], added in that order (nnet/decoders.py:226-231, length_pred = N + eos). */
+int avec_lm_segment_sum(const float* nll, const long long* lens, long long S, int L, float* out, hipStream_t stream);
+/* B utterances x K hypotheses (K = augmentations x beam), lens as above (0 = empty slot):
+ * total[s] = beam_score[s] - alpha * neural[s] + beta * beta * (lens[s] - 1)  (higher is better; beta enters squared as in nnet/decoders.py:231,234; -inf for an empty slot or
+ * beam_score = -inf),  best[b] (int64) = the first maximum of total[b][:]. */
+int avec_lm_rescore_select(const float* neural, const long long* lens, const float* beam_score, float alpha, float beta, int B, int K, float* total, long long* best,
+                           hipStream_t stream);
 /* optimizers.Adam.step (nnet/optimizers.py:71-75) over flat arenas; state_dev = {step, lr} */
 int avec_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
                    float weight_decay, float grad_scale, int zero_grad, long long n, hipStream_t stream);
