@@ -346,6 +346,7 @@ extern "C" int avec_dwconv_glu_bwd_bn(int dtype, const void* da, const void* c, 
                                       void* du, float* dw, float* dbias, float* dgamma, float* dbeta, int B, int T_, int C, int K, int pad_left, hipStream_t st) {
   AVEC_CHECK_ARG(da && c && ss && gamma && dstats && count > 0.f && u && w && du && dw && B > 0 && T_ > 0 && C > 0 && C % 4 == 0 && K > 0 && K <= KMAX && pad_left >= 0 && pad_left < K,
                  "dwconv_glu_bwd_bn: bad arguments");
+  AVEC_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr), "dwconv_glu_bwd_bn: dgamma and dbeta come together (both or neither)");      // the kernel adds to both under one test
   const int nchunks = (T_ + DW_TT - 1) / DW_TT;
   dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); ColWs ws = col_ws_if(grid, KMAX + 1, C, st);
   size_t l2 = (size_t)2 * (DW_TT - 1 + K) * 128 * sizeof(float);
