@@ -2,6 +2,7 @@
 #include "common.h"
 #include "avec_hip.h"
 #include "vec.h"
+#include "host_tables.h"
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -29,39 +30,43 @@ extern "C" int avec_struct_size(int which) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// reduction workspace (vec.h: two-pass column reductions).  One registration per device.
+// reduction workspace (vec.h: two-pass column reductions) and dynamic-LDS opt-in: the bookkeeping is host_tables.h, this file adds the current device and the HIP call
 // ---------------------------------------------------------------------------------------------
-static constexpr int WS_MAX_DEV = 64, WS_MAX_STREAMS = 4;
-static struct { void* base; size_t bytes; } g_ws[WS_MAX_DEV];
-static struct { hipStream_t st; int dev; void* base; size_t bytes; } g_ws_stream[WS_MAX_STREAMS];      // extra workspaces bound to specific streams
-static int g_n_ws_stream = 0;
+static WsRegistry g_ws;
+static LdsOptin g_lds;
 
 extern "C" int avec_set_reduce_workspace(void* base, long long bytes) {
   int dev = 0; hipError_t e = hipGetDevice(&dev);
-  AVEC_CHECK_ARG(e == hipSuccess && dev >= 0 && dev < WS_MAX_DEV, "set_reduce_workspace: no current device");
+  AVEC_CHECK_ARG(e == hipSuccess && dev >= 0 && dev < WsRegistry::MAX_DEV, "set_reduce_workspace: no current device");
   AVEC_CHECK_ARG((base == nullptr && bytes == 0) || (base != nullptr && bytes >= (1 << 16) && ((size_t)base & 255) == 0),
                  "set_reduce_workspace: need a 256-byte aligned buffer of at least 64 KB (or NULL, 0 to unregister)");
-  g_ws[dev].base = base; g_ws[dev].bytes = (size_t)bytes;
+  g_ws.set_default(dev, base, (size_t)bytes);
   return 0;
 }
 extern "C" int avec_set_reduce_workspace_stream(void* base, long long bytes, hipStream_t stream) {
   int dev = 0; hipError_t e = hipGetDevice(&dev);
-  AVEC_CHECK_ARG(e == hipSuccess && base != nullptr && bytes >= (1 << 16) && ((size_t)base & 255) == 0, "set_reduce_workspace_stream: bad arguments");
-  for (int i = 0; i < g_n_ws_stream; ++i) if (g_ws_stream[i].st == stream && g_ws_stream[i].dev == dev) { g_ws_stream[i].base = base; g_ws_stream[i].bytes = (size_t)bytes; return 0; }
-  AVEC_CHECK_ARG(g_n_ws_stream < WS_MAX_STREAMS, "set_reduce_workspace_stream: at most %d stream-bound workspaces", WS_MAX_STREAMS);
-  g_ws_stream[g_n_ws_stream].st = stream; g_ws_stream[g_n_ws_stream].dev = dev; g_ws_stream[g_n_ws_stream].base = base; g_ws_stream[g_n_ws_stream].bytes = (size_t)bytes; ++g_n_ws_stream;
+  AVEC_CHECK_ARG(e == hipSuccess && dev >= 0 && dev < WsRegistry::MAX_DEV && base != nullptr && bytes >= (1 << 16) && ((size_t)base & 255) == 0, "set_reduce_workspace_stream: bad arguments");
+  AVEC_CHECK_ARG(g_ws.set_stream(dev, stream, base, (size_t)bytes), "set_reduce_workspace_stream: at most %d stream-bound workspaces", WsRegistry::MAX_STREAMS);
   return 0;
 }
 ColWs avec_reduce_ws(size_t partial_floats, hipStream_t st) {
-  ColWs ws{nullptr};
-  static const bool off = false;
-  if (off) return ws;
-  int dev = 0; if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= WS_MAX_DEV) return ws;
-  for (int i = 0; i < g_n_ws_stream; ++i) if (g_ws_stream[i].st == st && g_ws_stream[i].dev == dev) {
-    if (partial_floats * sizeof(float) <= g_ws_stream[i].bytes) ws.partial = (float*)g_ws_stream[i].base;
-    return ws;
-  }
-  if (!g_ws[dev].base || partial_floats * sizeof(float) > g_ws[dev].bytes) return ws;
-  ws.partial = (float*)g_ws[dev].base;
-  return ws;
+  int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return ColWs{nullptr};
+  return ColWs{(float*)g_ws.find(dev, st, partial_floats * sizeof(float))};
+}
+
+// 0, LdsOptin::TOO_LARGE, or the HIP error code of the refusal (hipErrorNoDevice without a current device)
+int avec_lds_optin_quiet(const void* kernel, size_t bytes) {
+  if (bytes <= LdsOptin::FREE_BYTES) return 0;
+  int dev = 0; if (hipGetDevice(&dev) != hipSuccess || dev < 0) return (int)hipErrorNoDevice;
+  return g_lds.request(dev, kernel, bytes, [](const void* k, size_t n) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n);
+    if (e != hipSuccess) (void)hipGetLastError();      // the refusal is reported by value; the next launch check must not see it
+    return (int)e;
+  });
+}
+int avec_lds_optin(const void* kernel, size_t bytes) {
+  const int r = avec_lds_optin_quiet(kernel, bytes);
+  if (r == LdsOptin::TOO_LARGE) avec_set_error("%zu bytes of LDS requested (> 160 KiB)", bytes);
+  else if (r) avec_set_error("cannot reserve %zu bytes of LDS: %s", bytes, hipGetErrorString((hipError_t)r));
+  return r;
 }

@@ -251,25 +251,14 @@ static int fill_args(AttnArgs& a, const avec_attn_t* p) {
   AVEC_CHECK_ARG(a.B > 0 && a.H > 0 && a.T > 0 && a.d > 0 && a.d <= 64 * NCS && a.Tk >= a.T, "attention: bad dims B=%d H=%d T=%d Tk=%d d=%d (d <= %d, Tk >= T)", a.B, a.H, a.T, a.Tk, a.d, 64 * NCS);
   return 0;
 }
-template <typename K> static int set_lds(K kern, size_t bytes) {
-  if (bytes > 160 * 1024) { avec_set_error("attention: %zu bytes of LDS requested (> 160 KiB)", bytes); return -1; }
-  static const void* done[16]; static size_t done_bytes[16]; static int ndone = 0;
-  for (int i = 0; i < ndone; ++i) if (done[i] == (const void*)kern && done_bytes[i] >= bytes) return 0;
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { avec_set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-    if (ndone < 16) { done[ndone] = (const void*)kern; done_bytes[ndone] = bytes; ++ndone; }
-  }
-  return 0;
-}
 
 extern "C" int avec_relpos_attention_fwd(int dtype, const avec_attn_t* p, hipStream_t st) {
   AttnArgs a; AVEC_CHECK_ARG(p, "attention_fwd: null args"); if (int r = fill_args(a, p)) return r;
   if (dtype == AVEC_BF16) { const int r = attn_mfma_fwd(a, st); if (r != 1) return r; }      // MFMA path; 1 = not applicable, fall through
   const int DP = a.d | 1; size_t lds = (size_t)(2 * TK + (TQ + TK - 1) + TQ) * DP * 4 + 4 * 64 * 4;
   dim3 grid((a.T + TQ - 1) / TQ, a.B * a.H);
-  if (dtype == AVEC_BF16) { if (int r = set_lds(attn_rows_kernel<bf16, false>, lds)) return r; hipLaunchKernelGGL((attn_rows_kernel<bf16, false>), grid, dim3(256), lds, st, a); }
-  else { if (int r = set_lds(attn_rows_kernel<float, false>, lds)) return r; hipLaunchKernelGGL((attn_rows_kernel<float, false>), grid, dim3(256), lds, st, a); }
+  if (dtype == AVEC_BF16) { if (int r = avec_lds_optin(attn_rows_kernel<bf16, false>, lds)) return r; hipLaunchKernelGGL((attn_rows_kernel<bf16, false>), grid, dim3(256), lds, st, a); }
+  else { if (int r = avec_lds_optin(attn_rows_kernel<float, false>, lds)) return r; hipLaunchKernelGGL((attn_rows_kernel<float, false>), grid, dim3(256), lds, st, a); }
   AVEC_LAUNCH_CHECK(); return 0;
 }
 
@@ -280,14 +269,14 @@ template <typename T> static int launch_bwd(AttnArgs& a, hipStream_t st) {
   bool rows_done = false;
   if (sizeof(T) == 2) { const int r = attn_mfma_bwd_rows(a, st); if (r == 0) rows_done = true; else if (r != 1) return r; }   // bf16 MFMA row pass
   if (!rows_done) {
-    if (int r = set_lds(attn_rows_kernel<T, true>, lds1)) return r;
+    if (int r = avec_lds_optin(attn_rows_kernel<T, true>, lds1)) return r;
     hipLaunchKernelGGL((attn_rows_kernel<T, true>), grid1, dim3(256), lds1, st, a);
   }
   if (a.dsrel || a.Tk != a.T) return 0;            // (Tk != T: key/value cache attached -- only the probability / dQ row pass is defined)  dK/dV/dE are computed by the caller with avec_gemm_tn_batched on P / dS / dSrel (MFMA path)
   size_t lds2 = (size_t)(2 * QC + 2 * 64) * DP * 4;
   const int ktiles = (a.T + 63) / 64, rtiles = (2 * a.T - 1 + 63) / 64;
   dim3 grid2(ktiles + rtiles, a.B * a.H);
-#define LB(DPAD) do { if (int r = set_lds(attn_bwd_cols_kernel<T, DPAD>, lds2)) return r; hipLaunchKernelGGL((attn_bwd_cols_kernel<T, DPAD>), grid2, dim3(256), lds2, st, a, ktiles); } while (0)
+#define LB(DPAD) do { if (int r = avec_lds_optin(attn_bwd_cols_kernel<T, DPAD>, lds2)) return r; hipLaunchKernelGGL((attn_bwd_cols_kernel<T, DPAD>), grid2, dim3(256), lds2, st, a, ktiles); } while (0)
   AVEC_CHECK_ARG(a.d <= 96, "attention_bwd: the register-accumulating column pass serves d <= 96 (d=%d): pass dsrel and use avec_gemm_tn_batched", a.d);
   if (a.d <= 48) LB(48); else if (a.d <= 64) LB(64); else LB(96);
 #undef LB

@@ -537,22 +537,13 @@ __global__ __launch_bounds__(ALIAS ? 128 : 256) void attn_mfma_bwd_kernel(AttnAr
 
 static const bool g_mfma_off = getenv("AVEC_NO_MFMA_ATTN") != nullptr;
 
-template <typename K> static int mfma_set_lds(K kern, size_t bytes) {
-  static const void* done[40]; static size_t done_bytes[40]; static int ndone = 0;
-  for (int i = 0; i < ndone; ++i) if (done[i] == (const void*)kern && done_bytes[i] >= bytes) return 0;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-  if (e != hipSuccess) { avec_set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-  if (ndone < 40) { done[ndone] = (const void*)kern; done_bytes[ndone] = 160 * 1024; ++ndone; }
-  return 0;
-}
-
 int attn_mfma_fwd(const AttnArgs& a, hipStream_t st) {
   if (g_mfma_off || a.mask || a.d > 96 || a.T > 32 * NTMAX || a.Tk != a.T) return 1;
   const int pitch = a.d <= 64 ? 128 : 256;
   const MfmaGeom G = mfma_geom(a.T, a.d, pitch, false);
   if (G.total > 160 * 1024) return 1;
   dim3 grid((a.T + 63) / 64, a.B * a.H);
-#define AVEC_LAUNCH_ATTN(KERNEL) do { if (int r = mfma_set_lds(KERNEL, G.total)) return r; hipLaunchKernelGGL(KERNEL, grid, dim3(G.alias ? 128 : 256), G.total, st, a, G); } while (0)
+#define AVEC_LAUNCH_ATTN(KERNEL) do { if (int r = avec_lds_optin(KERNEL, G.total)) return r; hipLaunchKernelGGL(KERNEL, grid, dim3(G.alias ? 128 : 256), G.total, st, a, G); } while (0)
 #define AVEC_PICK_DKS(NAME, N, A) do { \
     if (pitch == 128) { if (G.DKS == 4) AVEC_LAUNCH_ATTN((NAME<128, N, A, 4>)); else if (G.DKS == 3) AVEC_LAUNCH_ATTN((NAME<128, N, A, 3>)); else AVEC_LAUNCH_ATTN((NAME<128, N, A, 0>)); } \
     else { if (G.DKS == 6) AVEC_LAUNCH_ATTN((NAME<256, N, A, 6>)); else AVEC_LAUNCH_ATTN((NAME<256, N, A, 0>)); } } while (0)

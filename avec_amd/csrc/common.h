@@ -126,5 +126,11 @@ __device__ __forceinline__ float geluf_(float x) { return 0.5f * x * (1.f + erff
 extern "C" const char* avec_last_error();
 void avec_set_error(const char* fmt, ...);
 void avec_note_kernel(const char* fmt, ...);      // api.hip: remembers which kernel instance an entry point chose (avec_last_kernel)
+// api.hip: call before launching `kernel` with `bytes` of dynamic LDS.  Up to 48 KB needs nothing and more than 160 KB is an argument error; in between the kernel is
+// opted in on the current device, with one HIP call per (device, kernel) and growth; a refusal is remembered and comes back as the same HIP error code.
+// avec_lds_optin_quiet: the same without touching avec_last_error, for a caller that has a fallback for a refusal.
+__attribute__((visibility("hidden"))) int avec_lds_optin(const void* kernel, size_t bytes);      // (hidden: the library exports what it exported before)
+__attribute__((visibility("hidden"))) int avec_lds_optin_quiet(const void* kernel, size_t bytes);
+template <typename K> static inline int avec_lds_optin(K kernel, size_t bytes) { return avec_lds_optin((const void*)kernel, bytes); }      // kernels by name
 #define AVEC_CHECK_ARG(cond, ...) do { if (!(cond)) { avec_set_error(__VA_ARGS__); return -1; } } while (0)
 #define AVEC_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { avec_set_error("%s:%d launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return (int)e_; } } while (0)

@@ -969,13 +969,8 @@ extern "C" int avec_wgrad3x3_c128(const void* x, const void* dy, float* dw, long
   }
   C3WWArgs a; a.x = (const bf16*)x; a.dy = (const bf16*)dy; a.dw = dw; a.N = (int)images; a.H = H; a.W = W; a.C = C;
   AVEC_CHECK_ARG(c3_wide_geometry(H, W, C, a.KP, a.RS, a.IT), "wgrad3x3_c128: %d channels, %dx%d images do not fit the slabs", C, H, W);
-  static bool attr_set = false;
   const size_t lds = (size_t)C3X_ROWS * 256 + C3X_KROWS * 128;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad3x3_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { avec_set_error("wgrad3x3_c128: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  if (int r = avec_lds_optin(wgrad3x3_wide_kernel, lds)) return r;
   const int kinds = (C / 64) * (C / 128);
   const long long groups = (images + a.IT - 1) / a.IT;
   long long per_kind = 256 / kinds; if (per_kind < 1) per_kind = 1; if (per_kind > groups) per_kind = groups;
@@ -1003,13 +998,8 @@ extern "C" int avec_wgrad3x3_c64_grouped(const avec_wgrad3x3_item_t* items, int 
     if (used + w > 256 + n) w = 1;
     used += (int)w; g.first[i + 1] = used;
   }
-  static bool attr_set = false;
   const size_t lds = C3_SBYTES + C3W_DBYTES;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad3x3_c64_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { avec_set_error("wgrad3x3_c64_grouped: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  if (int r = avec_lds_optin(wgrad3x3_c64_grouped_kernel, lds)) return r;
   avec_note_kernel("wgrad3x3_c64_grouped_kernel");
   hipLaunchKernelGGL(wgrad3x3_c64_grouped_kernel, dim3((unsigned)used), dim3(512), lds, st, g);
   AVEC_LAUNCH_CHECK();
@@ -1057,13 +1047,8 @@ extern "C" int avec_wgrad3x3_c128_grouped(const avec_wgrad3x3_item_t* items, int
     nwg[best] += kinds[best]; total += kinds[best];
   }
   g.first[0] = 0; for (int i = 0; i < n; ++i) g.first[i + 1] = g.first[i] + nwg[i];
-  static bool attr_set = false;
   const size_t lds = (size_t)C3X_ROWS * 256 + C3X_KROWS * 128;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad3x3_wide_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { avec_set_error("wgrad3x3_c128_grouped: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  if (int r = avec_lds_optin(wgrad3x3_wide_grouped_kernel, lds)) return r;
   avec_note_kernel("wgrad3x3_wide_grouped_kernel");
   hipLaunchKernelGGL(wgrad3x3_wide_grouped_kernel, dim3((unsigned)total), dim3(512), lds, st, g);
   AVEC_LAUNCH_CHECK();
@@ -1085,23 +1070,18 @@ extern "C" int avec_conv3x3_c64_res_masked(const void* x, const void* w, void* y
 static int conv3x3_c64_impl(const void* x, const void* w, void* y, const void* res, const unsigned char* rmask, float* stats, long long images, int H, int W, int flip, hipStream_t st) {
   AVEC_CHECK_ARG(x && w && y && images > 0, "conv3x3_c64: null buffer");
   AVEC_CHECK_ARG(avec_conv3x3_c64_supported(H, W, 64, 64, 3, 3, 1), "conv3x3_c64: %dx%d images do not fit the slab", H, W);
-  static bool attr_set = false;
+  // (statistics AND a residual in one launch would need 36 + 32 + 64 registers beside the accumulators: it spills, and a spilled register of an in-flight asm load is
+  // wrong code -- no caller needs the pair: forward launches carry statistics, backward-data launches the residual)
+  AVEC_CHECK_ARG(!(stats && res), "conv3x3_c64: statistics and a residual in the same launch are not supported");
   const size_t lds = C3_WBYTES + C3_SBYTES;
-  if (!attr_set) {
-    const void* kerns[3] = {(const void*)conv3x3_c64_kernel<false, false>, (const void*)conv3x3_c64_kernel<true, false>, (const void*)conv3x3_c64_res_kernel};
-    for (const void* k : kerns) {
-      hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { avec_set_error("conv3x3_c64: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return (int)e; }
-    }
-    attr_set = true;
-  }
+  // The plain kernel is named first only because the compiler emits the three kernels in the order of their first mention: this keeps the code object
+  // byte-for-byte what it was when the opt-in named all three up front.  Nothing depends on the order; reorder freely when the kernels change anyway.
+  const void* kern = !stats && !res ? (const void*)conv3x3_c64_kernel<false, false> : stats ? (const void*)conv3x3_c64_kernel<true, false> : (const void*)conv3x3_c64_res_kernel;
+  if (int r = avec_lds_optin(kern, lds)) return r;
   static const int wgs_env = 256;
   C3Args a; a.x = (const bf16*)x; a.w = (const bf16*)w; a.y = (bf16*)y; a.res = (const bf16*)res; a.stats = stats; a.N = (int)images; a.H = H; a.W = W; a.flip = flip; a.rmask = rmask;
   const int grid = (int)(images < wgs_env ? images : wgs_env);
   avec_note_kernel(stats ? "conv3x3_c64_kernel<true,false>" : res ? "conv3x3_c64_res_kernel" : "conv3x3_c64_kernel<false,false>");
-  // (statistics AND a residual in one launch would need 36 + 32 + 64 registers beside the accumulators: it spills, and a spilled register of an in-flight asm load is
-  // wrong code -- no caller needs the pair: forward launches carry statistics, backward-data launches the residual)
-  AVEC_CHECK_ARG(!(stats && res), "conv3x3_c64: statistics and a residual in the same launch are not supported");
   if (stats) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false>), dim3(grid), dim3(512), lds, st, a);
   else if (res) hipLaunchKernelGGL(conv3x3_c64_res_kernel, dim3(grid), dim3(512), lds, st, a);
   else hipLaunchKernelGGL((conv3x3_c64_kernel<false, false>), dim3(grid), dim3(512), lds, st, a);
@@ -1112,13 +1092,8 @@ static int conv3x3_c64_impl(const void* x, const void* w, void* y, const void* r
 extern "C" int avec_wgrad3x3_c64(const void* x, const void* dy, float* dw, long long images, int H, int W, hipStream_t st) {
   AVEC_CHECK_ARG(x && dy && dw && images > 0, "wgrad3x3_c64: null buffer");
   AVEC_CHECK_ARG(avec_conv3x3_c64_supported(H, W, 64, 64, 3, 3, 1) && H * (W + 1) <= C3W_KROWS, "wgrad3x3_c64: %dx%d images do not fit the slab", H, W);
-  static bool attr_set = false;
   const size_t lds = C3_SBYTES + C3W_DBYTES;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad3x3_c64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { avec_set_error("wgrad3x3_c64: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  if (int r = avec_lds_optin(wgrad3x3_c64_kernel, lds)) return r;
   C3WArgs a; a.x = (const bf16*)x; a.dy = (const bf16*)dy; a.dw = dw; a.N = (int)images; a.H = H; a.W = W;
   const int grid = (int)(images < 256 ? images : 256);
   avec_note_kernel("wgrad3x3_c64_kernel");

@@ -283,15 +283,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2_bwd_kernel(GemmArgs g) {
 
 bool s2_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-template <typename K> int s2_want_lds(K kern, size_t bytes) {
-  static const void* done[16]; static int ndone = 0;
-  for (int i = 0; i < ndone; ++i) if (done[i] == (const void*)kern) return 0;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) { avec_set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-  if (ndone < 16) done[ndone++] = (const void*)kern;
-  return 0;
-}
-
 }  // namespace
 
 // host side: 1 = not applicable (the caller continues with the general implicit-GEMM kernels), 0 = launched, other = error
@@ -314,10 +305,10 @@ int avec_launch_conv_s2(const GemmArgs& g_in, int mode, hipStream_t st) {
 #define S2(BM, BN, EV) do { \
     const size_t lds = (size_t)3 * BN * 64 + (size_t)3 * (BM + S2_HALO) * 64; \
     if (mode == MODE_CONV_FWD) { dim3 grid((unsigned)((P + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN)); \
-      avec_note_kernel("conv3x3_s2_fwd_kernel<%d,%d,%d>", BM, BN, (int)EV); if (int r = s2_want_lds(conv3x3_s2_fwd_kernel<BM, BN, EV>, lds)) return r; \
+      avec_note_kernel("conv3x3_s2_fwd_kernel<%d,%d,%d>", BM, BN, (int)EV); if (int r = avec_lds_optin(conv3x3_s2_fwd_kernel<BM, BN, EV>, lds)) return r; \
       hipLaunchKernelGGL((conv3x3_s2_fwd_kernel<BM, BN, EV>), grid, dim3(256), lds, st, g); } \
     else { dim3 grid((unsigned)((P + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN), 4); \
-      avec_note_kernel("conv3x3_s2_bwd_kernel<%d,%d,%d>", BM, BN, (int)EV); if (int r = s2_want_lds(conv3x3_s2_bwd_kernel<BM, BN, EV>, lds)) return r; \
+      avec_note_kernel("conv3x3_s2_bwd_kernel<%d,%d,%d>", BM, BN, (int)EV); if (int r = avec_lds_optin(conv3x3_s2_bwd_kernel<BM, BN, EV>, lds)) return r; \
       hipLaunchKernelGGL((conv3x3_s2_bwd_kernel<BM, BN, EV>), grid, dim3(256), lds, st, g); } \
     return 0; } while (0)
   if (g.N >= 128) { if (even) S2(256, 128, true); else S2(256, 128, false); }

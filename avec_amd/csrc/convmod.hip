@@ -276,16 +276,15 @@ extern "C" int avec_glu_dwconv_fwd(int dtype, const void* u, const float* w, con
   AVEC_CHECK_ARG(u && w && out && B > 0 && T_ > 0 && C > 0 && C % 4 == 0 && K > 0 && K <= KMAX && stride > 0 && pad_left >= 0 && pad_left < K, "glu_dwconv_fwd: bad arguments (C=%d K=%d pad_left=%d)", C, K, pad_left);
   const int To = (T_ - 1) / stride + 1;
   const int nchunks = (To + DW_TT - 1) / DW_TT;
-  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); ColWs ws = stats ? col_ws_if(grid, 2, C, st) : ColWs{nullptr};
+  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); const ColPlan plan = ColPlan::grid<2>(grid, C, st, stats != nullptr);
   const size_t lds = (size_t)((DW_TT - 1) * stride + K) * 128 * sizeof(float);
   AVEC_CHECK_ARG(lds <= 64 * 1024, "glu_dwconv_fwd: stride %d too large", stride);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(glu_dwconv_fwd_kernel<T>, grid, dim3(256), lds, st, (const T*)u, w, bias, (T*)out, stats, B, T_, C, K, stride, To, pad_left, nchunks, ws));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(glu_dwconv_fwd_kernel<T>, grid, dim3(256), lds, st, (const T*)u, w, bias, (T*)out, stats, B, T_, C, K, stride, To, pad_left, nchunks, plan.ws));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {stats, stats + C}; return col_finalize(ws, grid.x, grid.y, 2, 128, dst, C, st); }
-  return 0;
+  return plan.finish({stats, stats + C}, C, st);
 }
 // BatchNorm finalize (norm.hip bn_finalize_kernel, training mode) reading the two-pass column-reduction partials of glu_dwconv_fwd_kernel directly: the second pass
-// (col_finalize) and the finalize were two ~4.8 us launches back to back in every conformer block's dependent chain (round 6).  block = 16 channels x 16 slot lanes;
+// (ColPlan::finish) and the finalize were two ~4.8 us launches back to back in every conformer block's dependent chain (round 6).  block = 16 channels x 16 slot lanes;
 // partial[(colblock * nslots + slot) * 256 + n * 128 + w], channel c = 128 colblock + w, n = 0 sum / 1 sum of squares.
 __global__ __launch_bounds__(256) void bn_finalize_ws_kernel(const float* __restrict__ partial, int nslots, float count, const float* gamma, const float* beta, float* rmean, float* rvar,
                                                              long long* nbt, float momentum, float eps, float* ss, int C) {
@@ -326,19 +325,26 @@ extern "C" int avec_glu_dwconv_fwd_bn(int dtype, const void* u, const float* w, 
                  "glu_dwconv_fwd_bn: bad arguments (C=%d K=%d pad_left=%d)", C, K, pad_left);
   const int To = (T_ - 1) / stride + 1;
   const int nchunks = (To + DW_TT - 1) / DW_TT;
-  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); ColWs ws = col_ws_if(grid, 2, C, st);
+  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); const ColPlan plan = ColPlan::grid<2>(grid, C, st);
   const size_t lds = (size_t)((DW_TT - 1) * stride + K) * 128 * sizeof(float);
   AVEC_CHECK_ARG(lds <= 64 * 1024, "glu_dwconv_fwd_bn: stride %d too large", stride);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(glu_dwconv_fwd_kernel<T>, grid, dim3(256), lds, st, (const T*)u, w, bias, (T*)out, stats, B, T_, C, K, stride, To, pad_left, nchunks, ws));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(glu_dwconv_fwd_kernel<T>, grid, dim3(256), lds, st, (const T*)u, w, bias, (T*)out, stats, B, T_, C, K, stride, To, pad_left, nchunks, plan.ws));
   AVEC_LAUNCH_CHECK();
   const float count = (float)((long long)B * To);
-  if (ws.partial) {
-    hipLaunchKernelGGL(bn_finalize_ws_kernel, dim3((C + 15) / 16), dim3(256), 0, st, (const float*)ws.partial, (int)grid.y, count, gamma, beta, running_mean, running_var,
+  if (plan.ws.partial) {
+    hipLaunchKernelGGL(bn_finalize_ws_kernel, dim3((C + 15) / 16), dim3(256), 0, st, (const float*)plan.ws.partial, (int)plan.nslots, count, gamma, beta, running_mean, running_var,
                        num_batches_tracked, momentum, eps, ss, C);
     AVEC_LAUNCH_CHECK();
     return 0;
   }
   return avec_bn_finalize(stats, 1, nullptr, count, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, ss, C, 1, st);
+}
+// second pass of the depthwise weight gradient: partial rows are [KMAX + 1][128], taps 0..K-1 go to dw[k][C], row KMAX to dbias
+static int dw_finish(const ColPlan& plan, float* dw, float* dbias, int C, int K, hipStream_t st) {
+  float* dst[KMAX + 1];
+  for (int k = 0; k < KMAX; ++k) dst[k] = (k < K) ? dw + (long long)k * C : nullptr;
+  dst[KMAX] = dbias;
+  return plan.finish(dst, C, st);
 }
 // avec_bn_bwd_apply (act = Swish, local batch statistics over B * T rows, dstats = the reduced (sum d, sum d xhat) of avec_bn_bwd_reduce) + avec_dwconv_glu_bwd in ONE launch
 // (stride 1): da = gradient of the BatchNorm + Swish output, c = the BatchNorm input (= the depthwise convolution's output); dgamma / dbeta += dstats.
@@ -348,20 +354,14 @@ extern "C" int avec_dwconv_glu_bwd_bn(int dtype, const void* da, const void* c, 
                  "dwconv_glu_bwd_bn: bad arguments");
   AVEC_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr), "dwconv_glu_bwd_bn: dgamma and dbeta come together (both or neither)");      // the kernel adds to both under one test
   const int nchunks = (T_ + DW_TT - 1) / DW_TT;
-  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); ColWs ws = col_ws_if(grid, KMAX + 1, C, st);
+  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); const ColPlan plan = ColPlan::grid<KMAX + 1>(grid, C, st);
   size_t l2 = (size_t)2 * (DW_TT - 1 + K) * 128 * sizeof(float);
   if (l2 < (size_t)4 * (KMAX + 1) * 128 * sizeof(float)) l2 = (size_t)4 * (KMAX + 1) * 128 * sizeof(float);
   AVEC_CHECK_ARG(l2 <= 64 * 1024, "dwconv_glu_bwd_bn: kernel size %d too large", K);
   DwBnb bnb{c, ss, gamma, dstats, 1.f / count, dgamma, dbeta};
-  DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv_glu_bwd_fused_kernel<T>, grid, dim3(256), l2, st, (const T*)da, (const T*)u, w, (T*)du, dw, dbias, B, T_, C, K, pad_left, nchunks, ws, bnb));
+  DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv_glu_bwd_fused_kernel<T>, grid, dim3(256), l2, st, (const T*)da, (const T*)u, w, (T*)du, dw, dbias, B, T_, C, K, pad_left, nchunks, plan.ws, bnb));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) {
-    float* dst[KMAX + 1];
-    for (int k = 0; k < KMAX; ++k) dst[k] = (k < K) ? dw + (long long)k * C : nullptr;
-    dst[KMAX] = dbias;
-    return col_finalize(ws, grid.x, grid.y, KMAX + 1, 128, dst, C, st);
-  }
-  return 0;
+  return dw_finish(plan, dw, dbias, C, K, st);
 }
 extern "C" int avec_dwconv_glu_bwd(int dtype, const void* dc, const void* u, const float* w, void* du, float* dw, float* dbias,
                                    int B, int T_, int C, int K, int stride, int pad_left, hipStream_t st) {
@@ -369,23 +369,16 @@ extern "C" int avec_dwconv_glu_bwd(int dtype, const void* dc, const void* u, con
   const int To = (T_ - 1) / stride + 1;
   long long n4 = (long long)B * T_ * (C / 4); long long nb = (n4 + 255) / 256; if (nb > 4096) nb = 4096;
   const int nchunks = (To + DW_TT - 1) / DW_TT;
-  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); ColWs ws = col_ws_if(grid, KMAX + 1, C, st);
+  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)(B * nchunks)); const ColPlan plan = ColPlan::grid<KMAX + 1>(grid, C, st);
   size_t lds = (size_t)((DW_TT - 1) * stride + K) * 128 * sizeof(float);
   if (lds < (size_t)4 * (KMAX + 1) * 128 * sizeof(float)) lds = (size_t)4 * (KMAX + 1) * 128 * sizeof(float);      // the reduction image of the weight-gradient kernel
   AVEC_CHECK_ARG(lds <= 64 * 1024, "dwconv_glu_bwd: stride %d too large", stride);
-  static const bool no_fused = false;
-  if (stride == 1 && !no_fused) {
+  if (stride == 1) {
     size_t l2 = (size_t)2 * (DW_TT - 1 + K) * 128 * sizeof(float); if (l2 < lds) l2 = lds;
-    DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv_glu_bwd_fused_kernel<T>, grid, dim3(256), l2, st, (const T*)dc, (const T*)u, w, (T*)du, dw, dbias, B, T_, C, K, pad_left, nchunks, ws));
+    DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv_glu_bwd_fused_kernel<T>, grid, dim3(256), l2, st, (const T*)dc, (const T*)u, w, (T*)du, dw, dbias, B, T_, C, K, pad_left, nchunks, plan.ws));
   } else
   DISPATCH_T(dtype, hipLaunchKernelGGL(dwconv_glu_bwd_input_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, (const T*)dc, (const T*)u, w, (T*)du, B, T_, C, K, stride, To, pad_left);
-             hipLaunchKernelGGL(dwconv_bwd_weight_kernel<T>, grid, dim3(256), lds, st, (const T*)dc, (const T*)u, dw, dbias, B, T_, C, K, stride, To, pad_left, nchunks, ws));
+             hipLaunchKernelGGL(dwconv_bwd_weight_kernel<T>, grid, dim3(256), lds, st, (const T*)dc, (const T*)u, dw, dbias, B, T_, C, K, stride, To, pad_left, nchunks, plan.ws));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) {
-    float* dst[KMAX + 1];
-    for (int k = 0; k < KMAX; ++k) dst[k] = (k < K) ? dw + (long long)k * C : nullptr;
-    dst[KMAX] = dbias;
-    return col_finalize(ws, grid.x, grid.y, KMAX + 1, 128, dst, C, st);
-  }
-  return 0;
+  return dw_finish(plan, dw, dbias, C, K, st);
 }

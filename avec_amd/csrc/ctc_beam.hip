@@ -328,14 +328,6 @@ int check_lm(const avec_ngram_t* lm, int V) {
   AVEC_CHECK_ARG(lm->ctx_cap == 0 || (lm->ctx_key && lm->ctx_bo && lm->ctx_off && lm->ctx_cnt && lm->cont_tok && lm->cont_lp), "ctc_beam: null LM table");
   return 0;
 }
-template <typename Kern> int set_lds(Kern kern, size_t bytes) {
-  AVEC_CHECK_ARG(bytes <= 160 * 1024, "ctc_beam: %zu bytes of LDS (> 160 KiB)", bytes);
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { avec_set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-  }
-  return 0;
-}
 }  // namespace
 
 extern "C" long long avec_ctc_beam_workspace_bytes(int B, int T, int W) { return (long long)B * T * W * 4; }
@@ -355,10 +347,10 @@ extern "C" int avec_ctc_beam_search(const float* logits, const long long* length
   if (lm) { if (int r = check_lm(lm, V)) return r; a.lm = *lm; }
   const size_t bytes = lay(W, V, lm != nullptr).total;
   if (lm) {
-    if (int r = set_lds(ctc_beam_kernel<true>, bytes)) return r;
+    if (int r = avec_lds_optin(ctc_beam_kernel<true>, bytes)) return r;
     hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(NT), bytes, st, a);
   } else {
-    if (int r = set_lds(ctc_beam_kernel<false>, bytes)) return r;
+    if (int r = avec_lds_optin(ctc_beam_kernel<false>, bytes)) return r;
     hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(NT), bytes, st, a);
   }
   AVEC_LAUNCH_CHECK(); return 0;

@@ -447,16 +447,14 @@ extern "C" int avec_audio_stem_conv_fwd(int dtype, const float* mel, const float
   AVEC_CHECK_ARG(mel && w && y && B > 0 && n_mels > 0 && F > 0 && C > 0, "audio_stem_conv_fwd: bad arguments");
   StemA s = stemA(B, n_mels, F, C);
   if (as8_ok(s)) {
-    const unsigned nb = as8_blocks(s); ColWs ws = stats ? avec_reduce_ws((size_t)nb * 2 * C, st) : ColWs{nullptr};
+    const unsigned nb = as8_blocks(s); const ColPlan plan = ColPlan::flat<2>(nb, C, st, stats != nullptr);
     const size_t lds = ((size_t)(n_mels + 2) * 3 + (size_t)C * 12) * 4;
-    static const bool no_x = false;
-    if (as8x_ok(s) && !no_x) { const size_t l2 = ((size_t)(((n_mels + 2) * 3 + 4 + 3) & ~3) + (size_t)C * 2) * 4;
-      DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_conv8x_kernel<T>, dim3(nb), dim3(256), l2, st, mel, w, bias, (T*)y, stats, s, ws)); }
+    if (as8x_ok(s)) { const size_t l2 = ((size_t)(((n_mels + 2) * 3 + 4 + 3) & ~3) + (size_t)C * 2) * 4;
+      DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_conv8x_kernel<T>, dim3(nb), dim3(256), l2, st, mel, w, bias, (T*)y, stats, s, plan.ws)); }
     else
-    DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_conv8_kernel<T>, dim3(nb), dim3(256), lds, st, mel, w, bias, (T*)y, stats, s, ws));
+    DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_conv8_kernel<T>, dim3(nb), dim3(256), lds, st, mel, w, bias, (T*)y, stats, s, plan.ws));
     AVEC_LAUNCH_CHECK();
-    if (ws.partial) { float* const dst[2] = {stats, stats + C}; return col_finalize(ws, 1, nb, 2, C, dst, C, st); }
-    return 0;
+    return plan.finish({stats, stats + C}, C, st);
   }
   DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_conv_kernel<T>, stem_grid(s), dim3(256), 0, st, mel, w, bias, (T*)y, stats, s));
   AVEC_LAUNCH_CHECK(); return 0;
@@ -480,31 +478,28 @@ extern "C" int avec_audio_stem_bwd(int dtype, const void* da, const void* y, con
   if (as8_ok(s)) {
     const unsigned nb = as8_blocks(s);
     if (phase == 0) {
-      ColWs ws = avec_reduce_ws((size_t)nb * 2 * C, st);
-      static const bool no_x = false;
-      if (as8x_ok(s) && !no_x) DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_bwd_reduce8x_kernel<T>, dim3(nb), dim3(256), (size_t)2 * C * 4, st, (const T*)da, (const T*)y, ss, dstats, s, ws));
+      const ColPlan plan = ColPlan::flat<2>(nb, C, st);
+      if (as8x_ok(s)) DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_bwd_reduce8x_kernel<T>, dim3(nb), dim3(256), (size_t)2 * C * 4, st, (const T*)da, (const T*)y, ss, dstats, s, plan.ws));
       else
-      DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_bwd_reduce8_kernel<T>, dim3(nb), dim3(256), (size_t)2 * C * 4, st, (const T*)da, (const T*)y, ss, dstats, s, ws));
+      DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_bwd_reduce8_kernel<T>, dim3(nb), dim3(256), (size_t)2 * C * 4, st, (const T*)da, (const T*)y, ss, dstats, s, plan.ws));
       AVEC_LAUNCH_CHECK();
-      if (ws.partial) { float* const dst[2] = {dstats, dstats + C}; return col_finalize(ws, 1, nb, 2, C, dst, C, st); }
+      return plan.finish({dstats, dstats + C}, C, st);
     } else {
-      ColWs ws = avec_reduce_ws((size_t)nb * 10 * C, st);
+      const ColPlan plan = ColPlan::flat<10>(nb, C, st);
       const size_t lds = ((size_t)(n_mels + 2) * 3 + (size_t)C * 10) * 4;
-      static const bool no_x = false;
-      if (as8x_ok(s) && !no_x) { const size_t l2 = ((size_t)(((n_mels + 2) * 3 + 4 + 3) & ~3) + (size_t)C * 10) * 4;
+      if (as8x_ok(s)) { const size_t l2 = ((size_t)(((n_mels + 2) * 3 + 4 + 3) & ~3) + (size_t)C * 10) * 4;
         DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_bwd_params8x_kernel<T>, dim3(nb), dim3(256), l2, st, (const T*)da, (const T*)y, mel, ss, gamma, dstats, count_ptr, count,
-                                             dw, dbias, dgamma, dbeta, s, ws)); }
+                                             dw, dbias, dgamma, dbeta, s, plan.ws)); }
       else
       DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_bwd_params8_kernel<T>, dim3(nb), dim3(256), lds, st, (const T*)da, (const T*)y, mel, ss, gamma, dstats, count_ptr, count,
-                                           dw, dbias, dgamma, dbeta, s, ws));
+                                           dw, dbias, dgamma, dbeta, s, plan.ws));
       AVEC_LAUNCH_CHECK();
-      if (ws.partial) {      // partial rows are [10][C]: taps 0..8 go to dw[c*9 + q] (element stride 9), row 9 to dbias
-        float* dst[10]; for (int q = 0; q < 9; ++q) dst[q] = dw + q; dst[9] = nullptr;
-        if (int r = col_finalize(ws, 1, nb, 10, C, dst, C, st, 9)) return r;
-        if (dbias) { for (int q = 0; q < 9; ++q) dst[q] = nullptr; dst[9] = dbias; return col_finalize(ws, 1, nb, 10, C, dst, C, st, 1); }
-      }
+      // partial rows are [10][C]: taps 0..8 go to dw[c*9 + q] (element stride 9), row 9 to dbias
+      float* dst[10]; for (int q = 0; q < 9; ++q) dst[q] = dw + q; dst[9] = nullptr;
+      if (int r = plan.finish(dst, C, st, 9)) return r;
+      for (int q = 0; q < 9; ++q) dst[q] = nullptr; dst[9] = dbias;
+      return dbias ? plan.finish(dst, C, st) : 0;
     }
-    return 0;
   }
   if (phase == 0) { DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_bwd_reduce_kernel<T>, stem_grid(s), dim3(256), 0, st, (const T*)da, (const T*)y, ss, dstats, s)); }
   else { DISPATCH_T(dtype, hipLaunchKernelGGL(audio_stem_bwd_params_kernel<T>, stem_grid(s), dim3(256), 0, st, (const T*)da, (const T*)y, mel, ss, gamma, dstats, count_ptr, count, dw, dbias, dgamma, dbeta, s)); }
@@ -728,11 +723,10 @@ extern "C" int avec_stem_pool_bwd_reduce_pooled(int dtype, const void* dpool, co
   AVEC_CHECK_ARG(dpool && idx && ymax && ss && dstats && frames > 0 && C % 8 == 0 && C <= 2048, "stem_pool_bwd_reduce_pooled: bad arguments (C %% 8 == 0, C <= 2048)");
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const long long P = frames * OH * OW;
-  ColWs ws; const unsigned nb8 = col8_cfg(P, C, 2, &ws, st);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(stem_pool_bwd_reduce_pooled_kernel<T>, dim3(nb8), dim3(256), 0, st, (const T*)dpool, idx, (const T*)ymax, ss, dstats, P, C, ws));
+  const ColPlan plan = ColPlan::flat8<2>(P, C, st);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(stem_pool_bwd_reduce_pooled_kernel<T>, dim3(plan.nslots), dim3(256), 0, st, (const T*)dpool, idx, (const T*)ymax, ss, dstats, P, C, plan.ws));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {dstats, dstats + C}; return col_finalize(ws, 1, nb8, 2, C, dst, C, st); }
-  return 0;
+  return plan.finish({dstats, dstats + C}, C, st);
 }
 
 extern "C" int avec_stem_pool_bwd(int dtype, const void* dpool, const unsigned char* idx, const void* y, const float* ss, const float* gamma, float* dstats,
@@ -741,12 +735,11 @@ extern "C" int avec_stem_pool_bwd(int dtype, const void* dpool, const unsigned c
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   if (C % 8 == 0 && C <= 2048) {
     if (phase == 0) {
-      ColWs ws; const unsigned nb8 = col8_cfg(frames * H * W, C, 2, &ws, st);
-      DISPATCH_T(dtype, hipLaunchKernelGGL(stem_pool_bwd_reduce8_kernel<T>, dim3(nb8), dim3(256), 0, st, (const T*)dpool, idx, (const T*)y, ss, dstats,
-                                           frames, H, W, C, OH, OW, ws));
+      const ColPlan plan = ColPlan::flat8<2>(frames * H * W, C, st);
+      DISPATCH_T(dtype, hipLaunchKernelGGL(stem_pool_bwd_reduce8_kernel<T>, dim3(plan.nslots), dim3(256), 0, st, (const T*)dpool, idx, (const T*)y, ss, dstats,
+                                           frames, H, W, C, OH, OW, plan.ws));
       AVEC_LAUNCH_CHECK();
-      if (ws.partial) { float* const dst[2] = {dstats, dstats + C}; return col_finalize(ws, 1, nb8, 2, C, dst, C, st); }
-      return 0;
+      return plan.finish({dstats, dstats + C}, C, st);
     } else {
       long long n8 = frames * H * W * (C / 8); long long nb = (n8 + 255) / 256; if (nb > 16384) nb = 16384;
       DISPATCH_T(dtype, hipLaunchKernelGGL(stem_pool_bwd_apply8_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, (const T*)dpool, idx, (const T*)y, ss, gamma, dstats, count_ptr, count,
@@ -755,11 +748,10 @@ extern "C" int avec_stem_pool_bwd(int dtype, const void* dpool, const unsigned c
     AVEC_LAUNCH_CHECK(); return 0;
   }
   if (phase == 0) {
-    dim3 grid = col_grid(frames * H * W, C); ColWs ws = col_ws_if(grid, 2, C, st);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(stem_pool_bwd_reduce_kernel<T>, grid, dim3(256), 0, st, (const T*)dpool, idx, (const T*)y, ss, dstats, frames, H, W, C, OH, OW, ws));
+    dim3 grid = col_grid(frames * H * W, C); const ColPlan plan = ColPlan::grid<2>(grid, C, st);
+    DISPATCH_T(dtype, hipLaunchKernelGGL(stem_pool_bwd_reduce_kernel<T>, grid, dim3(256), 0, st, (const T*)dpool, idx, (const T*)y, ss, dstats, frames, H, W, C, OH, OW, plan.ws));
     AVEC_LAUNCH_CHECK();
-    if (ws.partial) { float* const dst[2] = {dstats, dstats + C}; return col_finalize(ws, grid.x, grid.y, 2, 128, dst, C, st); }
-    return 0;
+    return plan.finish({dstats, dstats + C}, C, st);
   } else {
     long long n4 = frames * H * W * (C / 4); long long nb = (n4 + 255) / 256; if (nb > 8192) nb = 8192;
     DISPATCH_T(dtype, hipLaunchKernelGGL(stem_pool_bwd_apply_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, (const T*)dpool, idx, (const T*)y, ss, gamma, dstats, count_ptr, count,

@@ -1318,15 +1318,6 @@ static RowSrc make_src(const void* ptr, const avec_rows_t* d) {
   return s;
 }
 
-template <typename K> static int want_lds(K kern, size_t bytes) {
-  static const void* done[256]; static int ndone = 0;
-  for (int i = 0; i < ndone; ++i) if (done[i] == (const void*)kern) return 0;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) { avec_set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-  if (ndone < 256) done[ndone++] = (const void*)kern;
-  return 0;
-}
-
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // register-direct epilogue (conv_epilogue_tr, transposed product): bf16 output and residual in whole 16-byte pieces, nothing but alpha / residual / BatchNorm statistics
 // to fuse.  AVEC_NO_EPI_TR=1: the staged epilogue everywhere (A/B runs).
@@ -1375,14 +1366,14 @@ static int launch_nt_mode(const GemmArgs& g_in, int mode, int src_f32, hipStream
   static const int rb_env = rb_env_set ? atoi(getenv("AVEC_NT_RB")) : 128;
   const size_t epi_lds = (size_t)64 * (BN + 4) * 4 + 10 * BN * 4;
 #define G2(MODE, FC, RB_) do { const size_t l2 = (size_t)STG * (BM + BN) * RB_ > epi_lds ? (size_t)STG * (BM + BN) * RB_ : epi_lds; \
-    avec_note_kernel("gemm_nt_glds_kernel<%s,%d,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, STG, (int)FC, RB_); if (int r = want_lds(gemm_nt_glds_kernel<T, BM, BN, MODE, STG, FC, RB_>, l2)) return r; hipLaunchKernelGGL((gemm_nt_glds_kernel<T, BM, BN, MODE, STG, FC, RB_>), grid, dim3(256), l2, st, g); return 0; } while (0)
+    avec_note_kernel("gemm_nt_glds_kernel<%s,%d,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, STG, (int)FC, RB_); if (int r = avec_lds_optin(gemm_nt_glds_kernel<T, BM, BN, MODE, STG, FC, RB_>, l2)) return r; hipLaunchKernelGGL((gemm_nt_glds_kernel<T, BM, BN, MODE, STG, FC, RB_>), grid, dim3(256), l2, st, g); return 0; } while (0)
   // 64-byte rows (K-step 32): half the ring, 4 resident workgroups per CU instead of 2 -- measured +4..18 % on the implicit-GEMM layers with
   // thousands of tiles, -16 % on the deep-K / few-tile ones (512-channel 3x3 stage): chosen by tile count.  AVEC_NT_RB=64/128 forces it.
   const long long ntiles = (long long)grid.x * grid.y;
   const bool rb64 = sizeof(T) == 2 && (rb_env_set ? rb_env == 64 : ntiles >= 1536);
   static const int stg_env = 3;     // ring depth of the fast implicit-GEMM kernels with 64-byte rows: 3 measured +2..6 % over 2, 4 is -5..10 %
 #define G3(MODE, S_) do { const size_t l2 = (size_t)S_ * (BM + BN) * 64 > epi_lds ? (size_t)S_ * (BM + BN) * 64 : epi_lds; \
-    avec_note_kernel("gemm_nt_glds_kernel<%s,%d,%d,%d,%d,1,64>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, S_); if (int r = want_lds(gemm_nt_glds_kernel<T, BM, BN, MODE, S_, true, 64>, l2)) return r; hipLaunchKernelGGL((gemm_nt_glds_kernel<T, BM, BN, MODE, S_, true, 64>), grid, dim3(256), l2, st, g); return 0; } while (0)
+    avec_note_kernel("gemm_nt_glds_kernel<%s,%d,%d,%d,%d,1,64>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, S_); if (int r = avec_lds_optin(gemm_nt_glds_kernel<T, BM, BN, MODE, S_, true, 64>, l2)) return r; hipLaunchKernelGGL((gemm_nt_glds_kernel<T, BM, BN, MODE, S_, true, 64>), grid, dim3(256), l2, st, g); return 0; } while (0)
 #define G(MODE) do { if (MODE != MODE_PLAIN && g.fast_conv) { if (rb64 && stg_env == 3 && (BM + BN) > 128) G3(MODE, 3); if (rb64 && stg_env == 4 && (BM + BN) > 128) G3(MODE, 4); \
     if (rb64) G2(MODE, true, 64); else G2(MODE, true, 128); } G2(MODE, false, 128); } while (0)
   static const bool use_glds = true;
@@ -1402,22 +1393,22 @@ static int launch_nt_mode(const GemmArgs& g_in, int mode, int src_f32, hipStream
         if (tr) {
           const size_t lt = (size_t)2 * (BM + BN) * 128;
           avec_note_kernel("gemm_nt_plain_kernel<%d,%d,2,tr>", BM, BN);
-          if (int r = want_lds(gemm_nt_plain_kernel<BM, BN, 2, true>, lt)) return r;
+          if (int r = avec_lds_optin(gemm_nt_plain_kernel<BM, BN, 2, true>, lt)) return r;
           hipLaunchKernelGGL((gemm_nt_plain_kernel<BM, BN, 2, true>), grid, dim3(256), lt, st, g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g); return 0;
         }
         avec_note_kernel("gemm_nt_plain_kernel<%d,%d,2,false>", BM, BN);
-        if (int r = want_lds(gemm_nt_plain_kernel<BM, BN, 2>, l2s)) return r;
+        if (int r = avec_lds_optin(gemm_nt_plain_kernel<BM, BN, 2>, l2s)) return r;
         hipLaunchKernelGGL((gemm_nt_plain_kernel<BM, BN, 2>), grid, dim3(256), l2s, st, g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g); return 0;
       }
       const size_t l2 = (size_t)4 * (BM + BN) * 128 > epi_lds ? (size_t)4 * (BM + BN) * 128 : epi_lds;
       if (tr) {
         const size_t lt = (size_t)4 * (BM + BN) * 128;
         avec_note_kernel("gemm_nt_plain_kernel<%d,%d,4,tr>", BM, BN);
-        if (int r = want_lds(gemm_nt_plain_kernel<BM, BN, 4, true>, lt)) return r;
+        if (int r = avec_lds_optin(gemm_nt_plain_kernel<BM, BN, 4, true>, lt)) return r;
         hipLaunchKernelGGL((gemm_nt_plain_kernel<BM, BN, 4, true>), grid, dim3(256), lt, st, g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g); return 0;
       }
       avec_note_kernel("gemm_nt_plain_kernel<%d,%d,4,false>", BM, BN);
-      if (int r = want_lds(gemm_nt_plain_kernel<BM, BN>, l2)) return r;
+      if (int r = avec_lds_optin(gemm_nt_plain_kernel<BM, BN>, l2)) return r;
       hipLaunchKernelGGL((gemm_nt_plain_kernel<BM, BN>), grid, dim3(256), l2, st, g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g); return 0;
     }
   }
@@ -1428,14 +1419,14 @@ static int launch_nt_mode(const GemmArgs& g_in, int mode, int src_f32, hipStream
       if (epi_tr_ok(g)) {
         const size_t lt = (size_t)3 * (BM + BN) * 64;
         avec_note_kernel("gemm_nt_conv_lean_kernel<%d,%d,tr>", BN, mode);
-        if (mode == MODE_CONV_FWD) { if (int r = want_lds(gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD, true>, lt)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD, true>), grid, dim3(256), lt, st, g); }
-        else { if (int r = want_lds(gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD, true>, lt)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD, true>), grid, dim3(256), lt, st, g); }
+        if (mode == MODE_CONV_FWD) { if (int r = avec_lds_optin(gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD, true>, lt)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD, true>), grid, dim3(256), lt, st, g); }
+        else { if (int r = avec_lds_optin(gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD, true>, lt)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD, true>), grid, dim3(256), lt, st, g); }
         return 0;
       }
       if (g.e.res_mask) { avec_set_error("gemm_nt: res_mask needs the register-direct epilogue"); return -1; }
       avec_note_kernel("gemm_nt_conv_lean_kernel<%d,%d>", BN, mode);
-      if (mode == MODE_CONV_FWD) { if (int r = want_lds(gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD>, l2)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD>), grid, dim3(256), l2, st, g); }
-      else { if (int r = want_lds(gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD>, l2)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD>), grid, dim3(256), l2, st, g); }
+      if (mode == MODE_CONV_FWD) { if (int r = avec_lds_optin(gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD>, l2)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD>), grid, dim3(256), l2, st, g); }
+      else { if (int r = avec_lds_optin(gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD>, l2)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD>), grid, dim3(256), l2, st, g); }
       return 0;
     }
   }
@@ -1444,7 +1435,7 @@ static int launch_nt_mode(const GemmArgs& g_in, int mode, int src_f32, hipStream
 #undef G2
 #undef G3
 #undef G
-#define L(MODE, F, A) do { avec_note_kernel("gemm_nt_kernel<%s,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, (int)F, (int)A); if (int r = want_lds(gemm_nt_kernel<T, BM, BN, MODE, F, A>, lds)) return r; hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, MODE, F, A>), grid, dim3(256), lds, st, g); } while (0)
+#define L(MODE, F, A) do { avec_note_kernel("gemm_nt_kernel<%s,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, (int)F, (int)A); if (int r = avec_lds_optin(gemm_nt_kernel<T, BM, BN, MODE, F, A>, lds)) return r; hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, MODE, F, A>), grid, dim3(256), lds, st, g); } while (0)
   if (mode == MODE_PLAIN) {
     if (f32src) { if (a16) L(MODE_PLAIN, true, true); else L(MODE_PLAIN, true, false); }
     else { if (a16) L(MODE_PLAIN, false, true); else L(MODE_PLAIN, false, false); }
@@ -1464,7 +1455,7 @@ static int launch_conv_shift(const GemmArgs& g_in, int mode, hipStream_t st) {
   GemmArgs g = g_in; g.perm2 = 0; g.pTs[0] = xcd_order ? 1 : 0;        // (no parity classes here: pTs[0] is this kernel's tile-order switch)
 #define S(BM, BN, MODE) do { const size_t ring = (size_t)3 * BN * 64 + (size_t)2 * (BM + 64) * 64 + 512 + (BM / 64 - 1) * 2048, epi = (size_t)64 * (BN + 4) * 4 + 10 * BN * 4; const size_t lds = ring > epi ? ring : epi; \
     dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN)); \
-    avec_note_kernel("conv3x3_shift_kernel<%d,%d,%d>", BM, BN, MODE); if (int r = want_lds(conv3x3_shift_kernel<BM, BN, MODE>, lds)) return r; hipLaunchKernelGGL((conv3x3_shift_kernel<BM, BN, MODE>), grid, dim3(256), lds, st, g); return 0; } while (0)
+    avec_note_kernel("conv3x3_shift_kernel<%d,%d,%d>", BM, BN, MODE); if (int r = avec_lds_optin(conv3x3_shift_kernel<BM, BN, MODE>, lds)) return r; hipLaunchKernelGGL((conv3x3_shift_kernel<BM, BN, MODE>), grid, dim3(256), lds, st, g); return 0; } while (0)
   // 256-row tiles halve the weight-tile DMA per FLOP (measured 5-15 % on the 3200-image ResNet stages 2-3, slower once fewer than ~3 tiles per CU remain)
   static const int bm_env = getenv("AVEC_SHIFT_BM") ? atoi(getenv("AVEC_SHIFT_BM")) : 0;
   // tile height by wave quantisation: workgroups / (rounds * resident slots), slots = 256 CUs x 3 (128 rows, 136 VGPRs) or x 2 (256 rows, 237 VGPRs);
@@ -1474,7 +1465,7 @@ static int launch_conv_shift(const GemmArgs& g_in, int mode, hipStream_t st) {
   const bool tr_ok = epi_tr_ok(g) && !g.e.res_cls0;
 #define ST(BM, BN, MODE) do { const size_t ring = (size_t)3 * BN * 64 + (size_t)2 * (BM + 64) * 64 + 512 + (BM / 64 - 1) * 2048; const size_t lds = ring; \
     dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN)); \
-    avec_note_kernel("conv3x3_shift_kernel<%d,%d,%d,tr>", BM, BN, MODE); if (int r = want_lds(conv3x3_shift_kernel<BM, BN, MODE, true>, lds)) return r; hipLaunchKernelGGL((conv3x3_shift_kernel<BM, BN, MODE, true>), grid, dim3(256), lds, st, g); return 0; } while (0)
+    avec_note_kernel("conv3x3_shift_kernel<%d,%d,%d,tr>", BM, BN, MODE); if (int r = avec_lds_optin(conv3x3_shift_kernel<BM, BN, MODE, true>, lds)) return r; hipLaunchKernelGGL((conv3x3_shift_kernel<BM, BN, MODE, true>), grid, dim3(256), lds, st, g); return 0; } while (0)
   if (g.N >= 128 && (bm_env == 256 || (bm_env == 0 && e256 > e128) || (g.e.res_mask && tr_ok))) {
     if (tr_ok) { if (mode == MODE_CONV_FWD) ST(256, 128, MODE_CONV_FWD); else ST(256, 128, MODE_CONV_BWD); }
     if (mode == MODE_CONV_FWD) S(256, 128, MODE_CONV_FWD); else S(256, 128, MODE_CONV_BWD);
@@ -1564,7 +1555,7 @@ extern "C" int avec_gemm_nt_fp8(const void* A, long long lda, const void* W, lon
   AVEC_CHECK_ARG(!(e.drop_p > 0.f) || e.rng, "gemm_nt_fp8: dropout without rng state");
 #define F8(BM, BN, S_) do { dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((N + BN - 1) / BN)); \
     const size_t ring = (size_t)S_ * (BM + BN) * 128, epi = (size_t)64 * (BN + 4) * 4 + 10 * BN * 4; const size_t lds = ring > epi ? ring : epi; \
-    if (int r = want_lds(gemm_nt_fp8_kernel<BM, BN, S_>, lds)) return r; \
+    if (int r = avec_lds_optin(gemm_nt_fp8_kernel<BM, BN, S_>, lds)) return r; \
     hipLaunchKernelGGL((gemm_nt_fp8_kernel<BM, BN, S_>), grid, dim3(256), lds, stream, g, amax_a, amax_w); } while (0)
   const long long t128 = ((M + 127) / 128) * ((N + 127) / 128);
   if (N > 64 && t128 >= 384) F8(128, 128, 2);
@@ -1608,7 +1599,7 @@ static int launch_tn_tile(TnArgs g, int mode, int q_f32, int nbatch, hipStream_t
       static const int kt_env = getenv("AVEC_TN_KT") ? atoi(getenv("AVEC_TN_KT")) : 32;
       const long long q_elems = mode == MODE_PLAIN ? 0 : ((g.M + (long long)g.q.OH * g.q.OW - 1) / ((long long)g.q.OH * g.q.OW) + 1) * g.q.H * g.q.W * g.q.C;
       const bool q32 = q_elems < (1ll << 31);
-#define LT(MODE, Q32, KT_) do { const size_t l2 = (size_t)2 * KT_ * (BI + BJ) * 2; g.q_nwrap = (KT_ + g.q_ohw - 1) / g.q_ohw; avec_note_kernel("gemm_tn_tr_kernel<%d,%d,%d,2,%d,%d>", BI, BJ, MODE, (int)Q32, KT_); if (int r = want_lds(gemm_tn_tr_kernel<BI, BJ, MODE, 2, Q32, KT_>, l2)) return r; \
+#define LT(MODE, Q32, KT_) do { const size_t l2 = (size_t)2 * KT_ * (BI + BJ) * 2; g.q_nwrap = (KT_ + g.q_ohw - 1) / g.q_ohw; avec_note_kernel("gemm_tn_tr_kernel<%d,%d,%d,2,%d,%d>", BI, BJ, MODE, (int)Q32, KT_); if (int r = avec_lds_optin(gemm_tn_tr_kernel<BI, BJ, MODE, 2, Q32, KT_>, l2)) return r; \
         hipLaunchKernelGGL((gemm_tn_tr_kernel<BI, BJ, MODE, 2, Q32, KT_>), grid, dim3(256), l2, st, g); return 0; } while (0)
 #define LK(KT_) do { if (mode == MODE_PLAIN) LT(MODE_PLAIN, false, KT_); else if (q32) LT(MODE_CONV_FWD, true, KT_); else LT(MODE_CONV_FWD, false, KT_); } while (0)
       if (kt_env == 64) LK(64); else LK(32);
@@ -1617,10 +1608,9 @@ static int launch_tn_tile(TnArgs g, int mode, int q_f32, int nbatch, hipStream_t
     }
   }
   if (g.pcs) {      // kernels without the fused column sums: a separate pass (plain atomics only when weight gradients run on their own stream)
-    static const bool side_wgrad = false;
-    if (int r = colsum_launch(sizeof(T) == 2 ? AVEC_BF16 : AVEC_F32, g.P, g.ldp, g.pcs, g.M, g.I, !side_wgrad, st)) return r;
+    if (int r = colsum_launch(sizeof(T) == 2 ? AVEC_BF16 : AVEC_F32, g.P, g.ldp, g.pcs, g.M, g.I, true, st)) return r;
   }     // kernels without the fused column sums
-#define L(MODE, F, A) do { avec_note_kernel("gemm_tn_kernel<%s,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BI, BJ, MODE, (int)F, (int)A); if (int r = want_lds(gemm_tn_kernel<T, BI, BJ, MODE, F, A>, lds)) return r; hipLaunchKernelGGL((gemm_tn_kernel<T, BI, BJ, MODE, F, A>), grid, dim3(256), lds, st, g); } while (0)
+#define L(MODE, F, A) do { avec_note_kernel("gemm_tn_kernel<%s,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BI, BJ, MODE, (int)F, (int)A); if (int r = avec_lds_optin(gemm_tn_kernel<T, BI, BJ, MODE, F, A>, lds)) return r; hipLaunchKernelGGL((gemm_tn_kernel<T, BI, BJ, MODE, F, A>), grid, dim3(256), lds, st, g); } while (0)
   if (tn_collect && sizeof(T) == 2 && BI == 64 && BJ == 64 && mode == MODE_PLAIN && !f32src && !a16 && !g.pcs && tn_collect->n < AVEC_TN_MULTI_MAX) {
     TnMulti& m = *tn_collect; const int k = m.n++;           // (avec_gemm_tn_batched_multi: this problem joins the common launch)
     m.g[k] = g; m.gx[k] = (int)grid.x; m.gy[k] = (int)grid.y; m.first[k + 1] = m.first[k] + (int)(grid.x * grid.y * grid.z);
@@ -1717,7 +1707,7 @@ extern "C" int avec_gemm_tn_batched_multi(int dtype, const avec_tn_batched_t* it
   if (m.n > 0) {
     const size_t lds = (size_t)2 * (64 + 64) * LDS_ROW;
     avec_note_kernel("gemm_tn_multi_kernel<%d>", m.n);
-    if (int r = want_lds(gemm_tn_multi_kernel, lds)) return r;
+    if (int r = avec_lds_optin(gemm_tn_multi_kernel, lds)) return r;
     hipLaunchKernelGGL(gemm_tn_multi_kernel, dim3((unsigned)m.first[m.n]), dim3(256), lds, stream, m);
     AVEC_LAUNCH_CHECK();
   }
@@ -1774,7 +1764,7 @@ extern "C" int avec_gemm_tn_grouped(int dtype, const avec_tn_item_t* items, int 
   const int KT = kt_env == 32 ? 32 : 64, STG = (stg_env == 4 && KT == 32) ? 4 : 2;       // (2 x 64 rows and 4 x 32 rows measure the same, 3 stages are slower: profiles/r03_tn_grouped.txt)
   const size_t lds = (size_t)STG * KT * (BT + BT) * 2;
   avec_note_kernel("gemm_tn_tr_grouped_kernel<%d,%d,%d>", BT, STG, KT);
-#define TNG(BT_, S_, K_) do { if (BT == BT_ && STG == S_ && KT == K_) { if (int r = want_lds(gemm_tn_tr_grouped_kernel<BT_, S_, K_>, lds)) return r; \
+#define TNG(BT_, S_, K_) do { if (BT == BT_ && STG == S_ && KT == K_) { if (int r = avec_lds_optin(gemm_tn_tr_grouped_kernel<BT_, S_, K_>, lds)) return r; \
     hipLaunchKernelGGL((gemm_tn_tr_grouped_kernel<BT_, S_, K_>), dim3((unsigned)first), dim3(256), lds, stream, grp); } } while (0)
   TNG(128, 2, 32); TNG(128, 2, 64); TNG(64, 2, 32); TNG(64, 2, 64); TNG(128, 4, 32); TNG(64, 4, 32);
 #undef TNG

@@ -2,7 +2,6 @@
 //   CTC      : nnet/losses.py:311-334  (log_softmax -> nn.CTCLoss(blank=0, reduction="none", zero_infinity))
 //   Adam     : nnet/optimizers.py:61-93 over torch.optim.Adam (coupled L2 weight decay), lr from a device scalar
 //   shadows  : compute-dtype copies of the GEMM weights in the two layouts the NT kernels want
-#include <atomic>
 #include "vec.h"
 #include "avec_hip.h"
 
@@ -279,23 +278,10 @@ extern "C" long long avec_ctc_workspace_floats(int B, int T, int Lmax) { return 
 
 // Waves per utterance of the all-LDS kernels: the log-normaliser and gradient phases work frame by frame, one frame per wave and pass -- 16 waves when their
 // occupancy histograms still fit the 64 KB (each is V floats), else 4
-static int ctc_waves(size_t lds4, int V) {
-  static const int want = 16;
-  if (want < 16 || lds4 + (size_t)12 * V * 4 > 128 * 1024) return 4;
-  // (more than 64 KB of dynamic LDS has to be asked for once per kernel AND device; the call is cheap, the state is per device and published with release / acquire
-  //  so that a second device or a concurrent first call from the autograd thread never launches without it)
-  static std::atomic<int> state[16];                        // per device: 0 unknown, 1 granted, 2 refused
-  int dev = 0; if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  int stt = state[dev].load(std::memory_order_acquire);
-  if (stt == 0) {
-    const bool ok = hipFuncSetAttribute((const void*)ctc_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess &&
-                    hipFuncSetAttribute((const void*)ctc_lds_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess;
-    if (!ok) (void)hipGetLastError();
-    stt = ok ? 1 : 2;
-    state[dev].store(stt, std::memory_order_release);
-  }
-  const bool attr_ok = stt == 1;
-  return (attr_ok || lds4 + (size_t)12 * V * 4 <= 64 * 1024) ? 16 : 4;
+static int ctc_waves(const void* kernel, size_t lds4, int V) {
+  const size_t lds16 = lds4 + (size_t)12 * V * 4;
+  if (lds16 <= 64 * 1024) return 16;
+  return lds16 <= 128 * 1024 && avec_lds_optin_quiet(kernel, 128 * 1024) == 0 ? 16 : 4;      // (a refusal is remembered: 4 waves from then on, no second HIP call)
 }
 extern "C" int avec_ctc_loss(const float* logits, const long long* in_lens, const long long* targets, const long long* tgt_lens, float* nll, float* mean_out,
                              float* grad, float* workspace, int B, int T, int V, int Lmax, int blank, int zero_infinity, hipStream_t st) {
@@ -304,19 +290,14 @@ extern "C" int avec_ctc_loss(const float* logits, const long long* in_lens, cons
   const size_t Smax = 2 * (size_t)Lmax + 1;
   const size_t lds_fast = (3 * (size_t)T * Smax + T + 4 * (size_t)V + Smax) * 4;
   if (lds_fast <= 64 * 1024) {
-    const int nw = ctc_waves(lds_fast, V);
+    const int nw = ctc_waves((const void*)ctc_lds_kernel, lds_fast, V);
     hipLaunchKernelGGL(ctc_lds_kernel, dim3(B), dim3(64 * nw), lds_fast + (size_t)(nw - 4) * V * 4, st, logits, in_lens, targets, tgt_lens, nll, mean_out, grad, B, T, V, Lmax, blank, zero_infinity);
     AVEC_LAUNCH_CHECK(); return 0;
   }
   const size_t lds_alpha = ((size_t)T * Smax + T + 3 * Smax) * 4;
   static const bool no_alpha = getenv("AVEC_CTC_NO_ALPHA_LDS") != nullptr;
   if (lds_alpha <= 150 * 1024 && !no_alpha) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)ctc_alpha_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      if (e != hipSuccess) { avec_set_error("ctc_loss: cannot reserve LDS: %s", hipGetErrorString(e)); return (int)e; }
-      attr_set = true;
-    }
+    if (int r = avec_lds_optin(ctc_alpha_lds_kernel, lds_alpha)) return r;
     hipLaunchKernelGGL(ctc_alpha_lds_kernel, dim3(B), dim3(256), lds_alpha, st, logits, in_lens, targets, tgt_lens, nll, mean_out, grad, B, T, V, Lmax, blank, zero_infinity);
     AVEC_LAUNCH_CHECK(); return 0;
   }
@@ -341,7 +322,7 @@ extern "C" int avec_ctc_loss_multi(int n_heads, const float* const* logits, cons
     if (need > lds) lds = need;
   }
   AVEC_CHECK_ARG(lds <= 64 * 1024, "ctc_loss_multi: a head does not fit the all-LDS kernel (use avec_ctc_loss per head)");
-  const int nw = ctc_waves(lds, V);
+  const int nw = ctc_waves((const void*)ctc_lds_multi_kernel, lds, V);
   hipLaunchKernelGGL(ctc_lds_multi_kernel, dim3((unsigned)(n_heads * B)), dim3(64 * nw), lds + (size_t)(nw - 4) * V * 4, st, h, targets, tgt_lens, B, V, Lmax, blank, zero_infinity);
   AVEC_LAUNCH_CHECK(); return 0;
 }

@@ -39,6 +39,7 @@ __global__ __launch_bounds__(256) void col_finalize_kernel(ColFin f) {
   }
 }
 int col_finalize(const ColWs& ws, unsigned colblocks, unsigned nslots, int NV, int W, float* const* dst, int C, hipStream_t st, int dstride) {
+  AVEC_CHECK_ARG(NV >= 1 && NV <= FIN_MAXNV, "col_finalize: %d reduced quantities (at most %d)", NV, FIN_MAXNV);
   ColFin f; f.partial = ws.partial; f.NV = NV; f.W = W; f.C = C; f.nslots = (int)nslots; f.dstride = dstride;
   for (int i = 0; i < FIN_MAXNV; ++i) f.dst[i] = i < NV ? dst[i] : nullptr;
   dim3 grid((unsigned)((NV * W + 15) / 16), colblocks, (nslots + 127) / 128);
@@ -382,17 +383,15 @@ static int layernorm_bwd_impl(int dtype, const void* dy, int dy_f32, const float
     AVEC_LAUNCH_CHECK(); return 0;
   }
   long long nb = (M + 15) / 16; if (nb > 256) nb = 256; if (nb < 1) nb = 1;
-  ColWs ws = avec_reduce_ws((size_t)nb * 2 * D, st);
-  if (!ws.partial && nb > 128) nb = 128;
+  const ColPlan plan = ColPlan::flat<2>((unsigned)nb, D, st).cap_without_ws(128);      // every block issues 2*D atomics without a workspace
   const size_t lds = (size_t)2 * D * sizeof(float);
-#define AVEC_LN_BWD(TG, NG) hipLaunchKernelGGL((ln_bwd_kernel<TG, NG>), dim3((unsigned)nb), dim3(256), lds, st, (const TG*)dy, x, mean, rstd, gamma, dx, dres, dgamma, dbeta, M, D, ws)
+#define AVEC_LN_BWD(TG, NG) hipLaunchKernelGGL((ln_bwd_kernel<TG, NG>), dim3(plan.nslots), dim3(256), lds, st, (const TG*)dy, x, mean, rstd, gamma, dx, dres, dgamma, dbeta, M, D, plan.ws)
   const bool f32in = dy_f32 || dtype == AVEC_F32;
   if (D <= 512) { if (f32in) AVEC_LN_BWD(float, 2); else AVEC_LN_BWD(bf16, 2); }
   else { if (f32in) AVEC_LN_BWD(float, 6); else AVEC_LN_BWD(bf16, 6); }
 #undef AVEC_LN_BWD
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {dgamma, dbeta}; return col_finalize(ws, 1, (unsigned)nb, 2, D, dst, D, st); }
-  return 0;
+  return plan.finish({dgamma, dbeta}, D, st);
 }
 extern "C" int avec_layernorm_bwd(int dtype, const void* dy, int dy_f32, const float* x, const float* mean, const float* rstd, const float* gamma,
                                   float* dx, const float* dres, float* dgamma, float* dbeta, long long M, int D, hipStream_t st) {
@@ -453,11 +452,10 @@ extern "C" int avec_grad_prep(int dtype, const float* dout, long long ld, void* 
     DISPATCH_T(dtype, hipLaunchKernelGGL(grad_prep_flat_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, dout, ld, (T*)dacc, alpha, drop_p, rng, rng_stream, M, N));
     AVEC_LAUNCH_CHECK(); return 0;
   }
-  dim3 grid = col_grid(M, N); ColWs ws = dbias ? col_ws_if(grid, 1, N, st) : ColWs{nullptr};
-  DISPATCH_T(dtype, hipLaunchKernelGGL(grad_prep_kernel<T>, grid, dim3(256), 0, st, dout, ld, (T*)dacc, alpha, drop_p, rng, rng_stream, dbias, M, N, ws));
+  dim3 grid = col_grid(M, N); const ColPlan plan = ColPlan::grid<1>(grid, N, st);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(grad_prep_kernel<T>, grid, dim3(256), 0, st, dout, ld, (T*)dacc, alpha, drop_p, rng, rng_stream, dbias, M, N, plan.ws));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[1] = {dbias}; return col_finalize(ws, grid.x, grid.y, 1, 128, dst, N, st); }
-  return 0;
+  return plan.finish({dbias}, N, st);
 }
 
 // column sums of an act matrix:  out[n] += sum_m x[m][n]
@@ -475,11 +473,10 @@ extern "C" int avec_colsum(int dtype, const void* x, long long ld, float* out, l
 // use_ws = false: plain atomics (callers that may run concurrently with other users of the reduction workspace, e.g. weight gradients on the side stream)
 int colsum_launch(int dtype, const void* x, long long ld, float* out, long long M, int N, bool use_ws, hipStream_t st) {
   AVEC_CHECK_ARG(x && out && M > 0 && N > 0 && N % 4 == 0 && ld % 4 == 0, "colsum: bad arguments");
-  dim3 grid = col_grid(M, N); if (!use_ws && grid.y > 16) grid.y = 16; ColWs ws = use_ws ? col_ws_if(grid, 1, N, st) : ColWs{nullptr};
-  DISPATCH_T(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, st, (const T*)x, ld, out, M, N, ws));
+  dim3 grid = col_grid(M, N); if (!use_ws && grid.y > 16) grid.y = 16; const ColPlan plan = ColPlan::grid<1>(grid, N, st, use_ws);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, st, (const T*)x, ld, out, M, N, plan.ws));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[1] = {out}; return col_finalize(ws, grid.x, grid.y, 1, 128, dst, N, st); }
-  return 0;
+  return plan.finish({out}, N, st);
 }
 
 // =============================================================================================
@@ -499,11 +496,10 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ y, 
 }
 extern "C" int avec_bn_stats(int dtype, const void* y, float* stats, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(y && stats && M > 0 && C > 0 && C % 4 == 0, "bn_stats: bad arguments");
-  dim3 grid = col_grid(M, C); ColWs ws = col_ws_if(grid, 2, C, st);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_stats_kernel<T>, grid, dim3(256), 0, st, (const T*)y, stats, M, C, ws));
+  dim3 grid = col_grid(M, C); const ColPlan plan = ColPlan::grid<2>(grid, C, st);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_stats_kernel<T>, grid, dim3(256), 0, st, (const T*)y, stats, M, C, plan.ws));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {stats, stats + C}; return col_finalize(ws, grid.x, grid.y, 2, 128, dst, C, st); }
-  return 0;
+  return plan.finish({stats, stats + C}, C, st);
 }
 
 // block = 16 channels x 16 replica lanes (the 64 replicated partial sums of the GEMM epilogue are read in parallel, 4 per lane)
@@ -751,26 +747,23 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce8_kernel(const T* __restrict
 }
 extern "C" int avec_bn_bwd_reduce_mask(int dtype, const void* dout, const void* y, const unsigned char* mask, const float* ss, float* dstats, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(dout && y && mask && ss && dstats && M > 0 && col8_ok(C), "bn_bwd_reduce_mask: bad arguments");
-  ColWs ws; const unsigned nb = col8_cfg(M, C, 2, &ws, st);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce8_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)nullptr, ss, 2, dstats, M, C, ws, mask));
+  const ColPlan plan = ColPlan::flat8<2>(M, C, st);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce8_kernel<T>, dim3(plan.nslots), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)nullptr, ss, 2, dstats, M, C, plan.ws, mask));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {dstats, dstats + C}; return col_finalize(ws, 1, nb, 2, C, dst, C, st); }
-  return 0;
+  return plan.finish({dstats, dstats + C}, C, st);
 }
 extern "C" int avec_bn_bwd_reduce(int dtype, const void* dout, const void* y, const void* out, const float* ss, int act, float* dstats, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(dout && y && ss && dstats && M > 0 && C % 4 == 0, "bn_bwd_reduce: bad arguments");
   if (col8_ok(C)) {
-    ColWs ws; const unsigned nb = col8_cfg(M, C, 2, &ws, st);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce8_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, act, dstats, M, C, ws));
+    const ColPlan plan = ColPlan::flat8<2>(M, C, st);
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce8_kernel<T>, dim3(plan.nslots), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, act, dstats, M, C, plan.ws));
     AVEC_LAUNCH_CHECK();
-    if (ws.partial) { float* const dst[2] = {dstats, dstats + C}; return col_finalize(ws, 1, nb, 2, C, dst, C, st); }
-    return 0;
+    return plan.finish({dstats, dstats + C}, C, st);
   }
-  dim3 grid = col_grid(M, C); ColWs ws = col_ws_if(grid, 2, C, st);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, grid, dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, act, dstats, M, C, ws));
+  dim3 grid = col_grid(M, C); const ColPlan plan = ColPlan::grid<2>(grid, C, st);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, grid, dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, act, dstats, M, C, plan.ws));
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {dstats, dstats + C}; return col_finalize(ws, grid.x, grid.y, 2, 128, dst, C, st); }
-  return 0;
+  return plan.finish({dstats, dstats + C}, C, st);
 }
 // dy = gamma*rstd*(dr - mean(dr) - yhat*mean(dr*yhat)); optional dres = dr; block 0 adds dgamma/dbeta
 template <typename T>

@@ -255,14 +255,6 @@ static bool stem3_geom(Stem3& G, long long clips, int T_, int H, int W, size_t* 
   *slab_bytes = (size_t)((5 * G.SH * G.WP + 7) & ~7) * 2;
   return *slab_bytes <= 60 * 1024 && G.items < (1ll << 31);
 }
-template <typename K> static int s3_set_lds(K kern, size_t bytes) {
-  static const void* done[4]; static int ndone = 0;
-  for (int i = 0; i < ndone; ++i) if (done[i] == (const void*)kern) return 0;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  if (e != hipSuccess) { avec_set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-  if (ndone < 4) done[ndone++] = (const void*)kern;
-  return 0;
-}
 
 extern "C" int avec_stem3d_supported(long long clips, int T_, int H, int W) {
   Stem3 G; size_t sb; return clips > 0 && T_ > 0 && H > 6 && W >= 31 && stem3_geom(G, clips, T_, H, W, &sb) ? 1 : 0;     // OW >= 16: the pixel walk wraps at most once per step
@@ -273,12 +265,11 @@ extern "C" int avec_stem3d_fwd(const float* video, const void* w_shadow, int ldw
   Stem3 G; size_t sb;
   AVEC_CHECK_ARG(stem3_geom(G, clips, T_, H, W, &sb), "stem3d_fwd: frame %dx%d too large for the LDS band (use avec_stem_im2col + avec_gemm_nt)", H, W);
   const size_t lds = sb + (size_t)4 * 32 * 72 * 2 + 128 * 4;
-  if (int r = s3_set_lds(stem3_fwd_kernel, lds)) return r;
-  ColWs ws = stats ? avec_reduce_ws((size_t)G.items * 128, st) : ColWs{nullptr};
-  hipLaunchKernelGGL(stem3_fwd_kernel, dim3((unsigned)G.items), dim3(256), lds, st, video, (const bf16*)w_shadow, ldw, bias, (bf16*)y, stats ? 1 : 0, G, ws, stats);
+  if (int r = avec_lds_optin(stem3_fwd_kernel, lds)) return r;
+  const ColPlan plan = ColPlan::flat<2>((unsigned)G.items, S3_C, st, stats != nullptr);
+  hipLaunchKernelGGL(stem3_fwd_kernel, dim3((unsigned)G.items), dim3(256), lds, st, video, (const bf16*)w_shadow, ldw, bias, (bf16*)y, stats ? 1 : 0, G, plan.ws, stats);
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {stats, stats + S3_C}; return col_finalize(ws, 1, (unsigned)G.items, 2, S3_C, dst, S3_C, st); }
-  return 0;
+  return plan.finish({stats, stats + S3_C}, S3_C, st);
 }
 
 extern "C" int avec_stem3d_wgrad(const float* video, const void* dy, float* dw, long long clips, int T_, int H, int W, hipStream_t st) {
@@ -286,11 +277,10 @@ extern "C" int avec_stem3d_wgrad(const float* video, const void* dy, float* dw, 
   Stem3 G; size_t sb;
   AVEC_CHECK_ARG(stem3_geom(G, clips, T_, H, W, &sb), "stem3d_wgrad: frame %dx%d too large for the LDS band", H, W);
   const size_t lds = sb + (size_t)128 * 128;
-  if (int r = s3_set_lds(stem3_wgrad_kernel, lds)) return r;
+  if (int r = avec_lds_optin(stem3_wgrad_kernel, lds)) return r;
   unsigned nb = 512; if ((long long)nb > G.items) nb = (unsigned)G.items;
-  ColWs ws = avec_reduce_ws((size_t)nb * S3_C * S3_K, st);
-  hipLaunchKernelGGL(stem3_wgrad_kernel, dim3(nb), dim3(256), lds, st, video, (const bf16*)dy, dw, G, ws);
+  const ColPlan plan = ColPlan::flat<1>(nb, S3_C * S3_K, st);
+  hipLaunchKernelGGL(stem3_wgrad_kernel, dim3(nb), dim3(256), lds, st, video, (const bf16*)dy, dw, G, plan.ws);
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[1] = {dw}; return col_finalize(ws, 1, nb, 1, S3_C * S3_K, dst, S3_C * S3_K, st); }
-  return 0;
+  return plan.finish({dw}, S3_C * S3_K, st);
 }

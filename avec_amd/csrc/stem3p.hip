@@ -728,15 +728,6 @@ static bool s3p_geom(S3P& G, long long clips, int T_, int H, int W, size_t* lds_
   G.items = clips * T_ * G.NB;
   return G.items < (1ll << 31) && clips * T_ * (long long)G.OH * G.OW * S3P_C < (1ll << 40);
 }
-template <typename K> static int s3p_set_lds(K kern) {
-  static const void* done[4]; static int ndone = 0;
-  for (int i = 0; i < ndone; ++i) if (done[i] == (const void*)kern) return 0;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  if (e != hipSuccess) { avec_set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-  if (ndone < 4) done[ndone++] = (const void*)kern;
-  return 0;
-}
-
 extern "C" int avec_stem3p_supported(long long clips, int T_, int H, int W) {
   S3P G; size_t a, b; return s3p_geom(G, clips, T_, H, W, &a, &b) ? 1 : 0;
 }
@@ -746,25 +737,23 @@ extern "C" int avec_stem3p_fwd(const void* video_bf16, const void* w_shadow, con
   AVEC_CHECK_ARG(video_bf16 && w_shadow && gamma && zp && idx && (((size_t)video_bf16) & 15) == 0, "stem3p_fwd: null / unaligned pointer");
   S3P G; size_t lf, lb;
   AVEC_CHECK_ARG(s3p_geom(G, clips, T_, H, W, &lf, &lb), "stem3p_fwd: frame %dx%d not supported (W %% 8 == 0, W >= 32; use avec_stem_im2col + avec_gemm_nt)", H, W);
-  if (int r = s3p_set_lds(stem3p_fwd_kernel)) return r;
+  if (int r = avec_lds_optin(stem3p_fwd_kernel, lf)) return r;
   unsigned nb = 512; if ((long long)nb > G.items) nb = (unsigned)G.items;      // persistent: two workgroups per CU
-  ColWs ws = stats ? avec_reduce_ws((size_t)nb * 128, st) : ColWs{nullptr};
+  const ColPlan plan = ColPlan::flat<2>(nb, S3P_C, st, stats != nullptr);
   avec_note_kernel("stem3p_fwd_kernel");
   static const int abl = getenv("AVEC_S3P_ABL") ? atoi(getenv("AVEC_S3P_ABL")) : 0;      // kernel ablation (measurement only): 2 no conv tile, 4 no ring writes / statistics, 8 no pool stage, 16 no slab DMA
-  hipLaunchKernelGGL(stem3p_fwd_kernel, dim3(nb), dim3(256), lf, st, (const bf16*)video_bf16, (const bf16*)w_shadow, bias, gamma, (bf16*)zp, idx, stats ? 1 : 0, G, ws, stats, abl);
+  hipLaunchKernelGGL(stem3p_fwd_kernel, dim3(nb), dim3(256), lf, st, (const bf16*)video_bf16, (const bf16*)w_shadow, bias, gamma, (bf16*)zp, idx, stats ? 1 : 0, G, plan.ws, stats, abl);
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {stats, stats + S3P_C}; return col_finalize(ws, 1, nb, 2, S3P_C, dst, S3P_C, st); }
-  return 0;
+  return plan.finish({stats, stats + S3P_C}, S3P_C, st);
 }
 
 extern "C" int avec_stem3p_reduce(void* dpool, const void* zp, const float* ss, float* dstats, long long frames, int PH, int PW, hipStream_t st) {
   AVEC_CHECK_ARG(dpool && zp && ss && dstats && frames > 0 && PH > 0 && PW > 0, "stem3p_reduce: bad arguments");
   const long long P = frames * PH * PW;
-  ColWs ws; const unsigned nb8 = col8_cfg(P, S3P_C, 2, &ws, st);
-  hipLaunchKernelGGL(stem3p_reduce_kernel, dim3(nb8), dim3(256), 0, st, (bf16*)dpool, (const bf16*)zp, ss, dstats, P, S3P_C, ws);
+  const ColPlan plan = ColPlan::flat8<2>(P, S3P_C, st);
+  hipLaunchKernelGGL(stem3p_reduce_kernel, dim3(plan.nslots), dim3(256), 0, st, (bf16*)dpool, (const bf16*)zp, ss, dstats, P, S3P_C, plan.ws);
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[2] = {dstats, dstats + S3P_C}; return col_finalize(ws, 1, nb8, 2, S3P_C, dst, S3P_C, st); }
-  return 0;
+  return plan.finish({dstats, dstats + S3P_C}, S3P_C, st);
 }
 
 static bool s3w_geom(const S3P& G, long long clips, S3W& Q, size_t* lds) {
@@ -790,28 +779,22 @@ extern "C" int avec_stem3p_wgrad(const void* video_bf16, const void* w_shadow, c
   S3P G; S3W Q; size_t lf, lb, lw;
   AVEC_CHECK_ARG(s3p_geom(G, clips, T_, H, W, &lf, &lb) && s3w_geom(G, clips, Q, &lw), "stem3p_wgrad: frame %dx%d not supported", H, W);
   unsigned nb = 256; if ((long long)nb > Q.units) nb = (unsigned)Q.units;
-  ColWs ws = avec_reduce_ws((size_t)nb * S3P_C * 245, st);
+  const ColPlan plan = ColPlan::flat<1>(nb, S3P_C * 245, st);
   avec_note_kernel("stem3p_wgrad_roles_kernel");
   static const int abl = getenv("AVEC_S3W_ABL") ? atoi(getenv("AVEC_S3W_ABL")) : 0;      // kernel ablation (measurement only): 1 no conv part, 2 no stage 2, 4 no weight-gradient part, 8 no DMA prefetch
-  { static bool attr2 = false;
-    if (!attr2) {
-      hipError_t e = hipFuncSetAttribute((const void*)stem3p_wgrad_roles_kernel<208>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)stem3p_wgrad_roles_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) { avec_set_error("hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-      attr2 = true;
-    }
+  {
     const size_t lw2 = lw + 1024;             // + the stage-2 constant table
     AVEC_CHECK_ARG(lw2 <= 160 * 1024, "stem3p_wgrad: LDS");
+    if (int r = G.pitch == 208 ? avec_lds_optin(stem3p_wgrad_roles_kernel<208>, lw2) : avec_lds_optin(stem3p_wgrad_roles_kernel<0>, lw2)) return r;
     if (G.pitch == 208)      // (W = 88: the gather offsets of a step are instruction immediates)
       hipLaunchKernelGGL(stem3p_wgrad_roles_kernel<208>, dim3(nb), dim3(512), lw2, st, (const bf16*)video_bf16, (const bf16*)w_shadow, bias, (const bf16*)dpool_masked, idx, ss, gamma,
-                         dstats, count_ptr, count, dw, dgamma, dbeta, G, Q, ws, abl);
+                         dstats, count_ptr, count, dw, dgamma, dbeta, G, Q, plan.ws, abl);
     else
       hipLaunchKernelGGL(stem3p_wgrad_roles_kernel<0>, dim3(nb), dim3(512), lw2, st, (const bf16*)video_bf16, (const bf16*)w_shadow, bias, (const bf16*)dpool_masked, idx, ss, gamma,
-                         dstats, count_ptr, count, dw, dgamma, dbeta, G, Q, ws, abl);
+                         dstats, count_ptr, count, dw, dgamma, dbeta, G, Q, plan.ws, abl);
   }
   AVEC_LAUNCH_CHECK();
-  if (ws.partial) { float* const dst[1] = {dw}; return col_finalize(ws, 1, nb, 1, S3P_C * 245, dst, S3P_C * 245, st); }
-  return 0;
+  return plan.finish({dw}, S3P_C * 245, st);
 }
 
 extern "C" int avec_stem3p_dz(const void* video_bf16, const void* w_shadow, const float* bias, const void* dpool_masked, const unsigned char* idx, const float* ss,
@@ -820,7 +803,7 @@ extern "C" int avec_stem3p_dz(const void* video_bf16, const void* w_shadow, cons
   AVEC_CHECK_ARG(video_bf16 && w_shadow && dpool_masked && idx && ss && gamma && dstats && dz, "stem3p_dz: null pointer");
   S3P G; size_t lf, lb;
   AVEC_CHECK_ARG(s3p_geom(G, clips, T_, H, W, &lf, &lb), "stem3p_dz: frame %dx%d not supported", H, W);
-  if (int r = s3p_set_lds(stem3p_dz_kernel)) return r;
+  if (int r = avec_lds_optin(stem3p_dz_kernel, lb)) return r;
   avec_note_kernel("stem3p_dz_kernel");
   unsigned nb = 512; if ((long long)nb > G.items) nb = (unsigned)G.items;
   hipLaunchKernelGGL(stem3p_dz_kernel, dim3(nb), dim3(256), lb, st, (const bf16*)video_bf16, (const bf16*)w_shadow, bias, (const bf16*)dpool_masked, idx, ss, gamma,

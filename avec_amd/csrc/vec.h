@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include <cstdlib>
+#include <initializer_list>
 
 // ---- 4-wide vector helpers -------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ void ld4(const T* p, float v[4]);
@@ -58,7 +59,7 @@ template <> struct Raw8<float> { float4 a, b; __device__ __forceinline__ void lo
 // The workspace is registered per device with avec_set_reduce_workspace() and must not be shared by concurrent streams.
 // =============================================================================================
 struct ColWs { float* partial; };
-ColWs avec_reduce_ws(size_t partial_floats, hipStream_t st);     // api.hip; the workspace registered for stream `st` (else the device default); {nullptr} when none / too small
+ColWs avec_reduce_ws(size_t partial_floats, hipStream_t st);     // api.hip (for ColPlan only); the workspace bound to stream `st`, else the device default; {nullptr} when none / too small
 
 __device__ __forceinline__ float* ws_slot(const ColWs& ws, unsigned colblock, unsigned slot, unsigned nslots, int ncols) {
   return ws.partial + ((size_t)colblock * nslots + slot) * ncols;
@@ -68,7 +69,7 @@ struct ColFin { const float* partial; float* dst[FIN_MAXNV]; int NV, W, C, nslot
 // grid (ceil(NV*W/16), colblocks, ceil(nslots/128)); thread = (column cw = tid & 15, slot lane sl = tid >> 4)
 __global__ __launch_bounds__(256) void col_finalize_kernel(ColFin f);     // norm.hip
 int colsum_launch(int dtype, const void* x, long long ld, float* out, long long M, int N, bool use_ws, hipStream_t st);   // norm.hip
-int col_finalize(const ColWs& ws, unsigned colblocks, unsigned nslots, int NV, int W, float* const* dst, int C, hipStream_t st, int dstride = 1);   // norm.hip
+int col_finalize(const ColWs& ws, unsigned colblocks, unsigned nslots, int NV, int W, float* const* dst, int C, hipStream_t st, int dstride = 1);   // norm.hip (for ColPlan::finish only)
 
 // =============================================================================================
 // column-wise block reduction helper: block = 32 column groups (x4) x 8 row lanes
@@ -93,17 +94,10 @@ __device__ __forceinline__ void colreduce_atomic(float (&part)[NV][4], float* co
     __syncthreads();
   }
 }
-// workspace for a col_grid launch with NV reduced quantities (finish with col_finalize(ws, grid.x, grid.y, NV, 128, dst, C, st))
-static inline ColWs col_ws(dim3 grid, int NV, hipStream_t st) { return avec_reduce_ws((size_t)grid.x * grid.y * NV * 128, st); }
-// ... only when the one-pass version would issue many atomics (the second pass costs a launch)
-// AVEC_COLWS_MIN_ATOMICS: one-pass below this many atomics (default 16384).  Round 4 measured the step with 70 000 (the BatchNorm reductions of the conformer
-// convolution modules lose their second-pass launch, ~4.7 us each inside a dependent chain): 20.00 vs 19.90 ms; with 270 000: 21.2 ms -- the contended fp32 atomics
-// cost more than the launch they replace.
+// AVEC_COLWS_MIN_ATOMICS: one-pass below this many atomics (default 16384; the second pass costs a launch).  Round 4 measured the step with 70 000 (the BatchNorm
+// reductions of the conformer convolution modules lose their second-pass launch, ~4.7 us each inside a dependent chain): 20.00 vs 19.90 ms; with 270 000: 21.2 ms --
+// the contended fp32 atomics cost more than the launch they replace.
 static inline long long col_ws_min_atomics() { return 16384; }
-static inline ColWs col_ws_if(dim3 grid, int NV, int C, hipStream_t st) {
-  const long long atomics = (long long)grid.y * NV * C;
-  return atomics > col_ws_min_atomics() ? col_ws(grid, NV, st) : ColWs{nullptr};
-}
 
 static inline dim3 col_grid(long long M, int C) {
   unsigned gx = (unsigned)((C / 4 + 31) / 32);
@@ -147,12 +141,41 @@ static inline bool col8_ok(int C) { return C % 8 == 0 && C <= 2048; }
 #endif
 static inline long long col8_cap() { return AVEC_COL8_CAP; }      /* re-swept at the end of round 3 (tools/bench_bn.py): 1024 beats 2048 on every ResNet stage but the first (equal there) */
 static inline unsigned col8_blocks(long long M, int C) { const int R = 256 / (C / 8); long long nb = (M + R - 1) / R; if (nb > col8_cap()) nb = col8_cap(); return (unsigned)nb; }
-// grid size + workspace of a flat 8-wide launch (finish with col_finalize(ws, 1, nb, NV, C, dst, C, st)); without a workspace the
-// block count is kept low (every block issues NV*C atomics)
-static inline unsigned col8_cfg(long long M, int C, int NV, ColWs* ws, hipStream_t st) {
-  unsigned nb = col8_blocks(M, C);
-  if ((long long)nb * NV * C <= col_ws_min_atomics()) { *ws = ColWs{nullptr}; return nb; }      // small reductions: one pass, atomics
-  *ws = avec_reduce_ws((size_t)nb * NV * C, st);
-  if (!ws->partial && nb > 256) nb = 256;
-  return nb;
-}
+
+// =============================================================================================
+// Host side of one two-pass reduction: the workspace request, the (colblock, slot, nslots, ncols) the kernel passes to ws_slot and the
+// (colblocks, nslots, NV, W) of the second pass are one value.  A launch site builds a plan, launches `nslots` (x `colblocks`) blocks
+// with plan.ws as the kernel's ColWs and calls finish(); without a workspace (ws.partial == nullptr) the kernel used atomics and
+// finish() does nothing.
+// =============================================================================================
+struct __attribute__((visibility("hidden"))) ColPlan {
+  ColWs ws; unsigned colblocks, nslots; int NV, W;
+  // kernels that leave through colreduce_atomic on a col_grid-shaped (colblocks, nslots) grid: 128 columns per column block.  One pass
+  // when the caller wants no workspace or the atomics are few.
+  template <int NV_> static ColPlan grid(dim3 g, int C, hipStream_t st, bool want_ws = true) {
+    static_assert(NV_ <= FIN_MAXNV, "col_finalize_kernel carries FIN_MAXNV destinations");
+    const bool two = want_ws && (long long)g.y * NV_ * C > col_ws_min_atomics();
+    return ColPlan{two ? avec_reduce_ws((size_t)g.x * g.y * NV_ * 128, st) : ColWs{nullptr}, g.x, g.y, NV_, 128};
+  }
+  // nb blocks that each store one [NV][W] row (colreduce8_atomic, the as_commit-style kernels, the visual stems)
+  template <int NV_> static ColPlan flat(unsigned nb, int W, hipStream_t st, bool want_ws = true) {
+    static_assert(NV_ <= FIN_MAXNV, "col_finalize_kernel carries FIN_MAXNV destinations");
+    return ColPlan{want_ws ? avec_reduce_ws((size_t)nb * NV_ * W, st) : ColWs{nullptr}, 1, nb, NV_, W};
+  }
+  // flat 8-wide mapping over M rows of C channels: col8_blocks blocks; small reductions take one pass, and without a workspace the
+  // block count is kept low (every block issues NV*C atomics)
+  template <int NV_> static ColPlan flat8(long long M, int C, hipStream_t st) {
+    const unsigned nb = col8_blocks(M, C);
+    if ((long long)nb * NV_ * C <= col_ws_min_atomics()) return flat<NV_>(nb, C, st, false);
+    return flat<NV_>(nb, C, st).cap_without_ws(256);
+  }
+  ColPlan cap_without_ws(unsigned cap) const { ColPlan p = *this; if (!p.ws.partial && p.nslots > cap) p.nslots = cap; return p; }
+  // second pass: dst[n][c * dstride] += sum over slots, n < NV, c < C (a null dst[n] is skipped)
+  int finish(float* const* dst, int C, hipStream_t st, int dstride = 1) const {
+    return ws.partial ? col_finalize(ws, colblocks, nslots, NV, W, dst, C, st, dstride) : 0;
+  }
+  int finish(std::initializer_list<float*> dst, int C, hipStream_t st, int dstride = 1) const {
+    AVEC_CHECK_ARG((int)dst.size() == NV, "column reduction: %d destinations for %d quantities", (int)dst.size(), NV);
+    return finish(dst.begin(), C, st, dstride);
+  }
+};

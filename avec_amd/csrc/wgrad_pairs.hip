@@ -335,12 +335,7 @@ int wgrad3x3_pairs_grouped(const avec_wgrad3x3_item_t* items, int n, hipStream_t
     int R = (int)(shares / kinds + 0.5); if (R < 1) R = 1; if (R > g.stages[i]) R = g.stages[i];
     g.ranges[i] = ranges_env > 0 ? (ranges_env < g.stages[i] ? ranges_env : g.stages[i]) : R;
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad3x3_pairs_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WP_LDS);
-    if (e != hipSuccess) { avec_set_error("wgrad3x3_pairs: cannot reserve %zu bytes of LDS: %s", (size_t)WP_LDS, hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  if (int r = avec_lds_optin(wgrad3x3_pairs_grouped_kernel, WP_LDS)) return r;
   avec_note_kernel("wgrad3x3_pairs_grouped_kernel");
   hipLaunchKernelGGL(wgrad3x3_pairs_grouped_kernel, dim3((unsigned)grid), dim3(512), WP_LDS, st, g);
   AVEC_LAUNCH_CHECK();

@@ -11,7 +11,7 @@ The harness (class Ws)
                "Some word is no longer NaN after the launch" is the observation that the two-pass branch ran.
       atomics  no workspace registered.
       small    the 64 KB minimum registered inside a larger allocation whose remainder holds a sentinel that must be bit-identical afterwards.  avec_reduce_ws
-               (api.hip) hands the buffer out when partial_floats * 4 <= bytes.  For every kernel behind col_ws_if / col8_cfg the partials are at least as many
+               (api.hip) hands the buffer out when partial_floats * 4 <= bytes.  For every kernel behind ColPlan::grid / ColPlan::flat8 the partials are at least as many
                floats as the atomics they replace (gx * gy * NV * 128 >= gy * NV * C), so "more than 16 384 atomics" never fits 64 KB: they must run on atomics and
                leave the buffer alone.  The audio stem has no such threshold (nb * NV * C floats): 2048 blocks x 8 floats = exactly 64 KB must use the buffer, 2049
                blocks must not (STEM_EDGE).
@@ -407,6 +407,169 @@ def test_small_workspace_edge(F, fits):
         yr, ref, scale = R.stem_fwd_ref(mel64, w64, b64)
         check("audio_stem_conv_fwd", ("edge", F), "exact", stats, (ref, scale), INIT[0])
         assert torch.equal(y.cpu().double().view(B, To, C, Fo), yr)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# LayerNorm backward parameter gradients: min(ceil(M / 16), 256) slots of [2][D], 128 without a workspace; no atomics threshold
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+LN_ROWS = [17, 16 * 128 + 5]          # two slots, the second with one row / 129 slots: more than the 128 blocks launched without a workspace
+
+
+@pytest.mark.parametrize("setup", SETUPS)
+@pytest.mark.parametrize("dy_dtype", DTYPES)
+@pytest.mark.parametrize("D", [8, 180])
+def test_layernorm_bwd_param_grads(setup, dy_dtype, D):
+    """dgamma[c] += sum_m dy * (x - mean) * rstd, dbeta[c] += sum_m dy through avec_layernorm_bwd: integer dy, x and gamma, mean 0, rstd a power of two per row, so
+    every term is a multiple of 1/2 and the comparison with fp64 is torch.equal.  A registered workspace is used whenever 2 * D floats per slot fit it."""
+    lib = _lib()
+    with Ws(setup) as ws:
+        for i, M in enumerate(LN_ROWS):
+            case = (M, D, dy_dtype, setup)
+            dy, dyb = put(R.int_tensor((M, D), -3, 3, 1300 + i), dy_dtype)
+            x64, g64 = R.int_tensor((M, D), 0, 3, 1310 + i), R.int_tensor((D,), -2, 2, 1320 + i)
+            rs64 = torch.tensor([0.5, 1.0, 2.0], dtype=torch.float64)[torch.arange(M) % 3]
+            x, gamma, mean, rstd = f32(x64), f32(g64), torch.zeros(M, device=dev()), f32(rs64)
+            dx = torch.empty(M, D, device=dev())
+            dgamma, dbeta = torch.full((D,), INIT[0], device=dev()), torch.full((D,), INIT[1], device=dev())
+            used = ws.run(lambda: lib.layernorm_bwd(DT[dy_dtype], dy.data_ptr(), 0, x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), dx.data_ptr(), None,
+                                                    dgamma.data_ptr(), dbeta.data_ptr(), M, D, ws.stream))
+            nb = min((M + 15) // 16, 256)
+            fits = {"twopass": True, "atomics": False, "small": nb * 2 * D * 4 <= R.WS_MIN_BYTES}[setup]
+            assert used == fits, (case, nb, "slots of 2 * D floats")
+            check("layernorm_bwd dgamma", case, "exact", dgamma, R.reduce([dyb * x64 * rs64[:, None]]), INIT[0], 0.5)
+            check("layernorm_bwd dbeta", case, "exact", dbeta, R.reduce([dyb]), INIT[1])
+            assert bool(torch.isfinite(dx).all()), case
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# video stem tail, BatchNorm-backward sums through the max pool: over the conv output (8-wide for C % 8 == 0, else 4-wide) and over the pooled tensors
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+def _pool_twopass_expected(M, C):
+    """the regime tests/colreduce_ref.py's geometry asks for with a large workspace: more than 16 384 atomics in one pass"""
+    if C % 8 == 0:
+        return R.col8_blocks(M, C) * 2 * C > 16384
+    return R.col_grid(M, C)[1] * 2 * C > 16384
+
+
+# (C, H, W) of one frame, rows = H * W just below / just above the threshold, the last block or row slot partial:
+#   C = 64 (8-wide, 32 rows per block): 128 blocks x 128 atomics = 16 384 up to 4096 rows; 63 x 65 = 4095 rows, 63 x 66 = 4158 rows (130 blocks)
+#   C = 12 (4-wide, 64 rows per slot): 682 slots x 24 atomics = 16 368 up to 43 648 rows; 135 x 323 = 43 605 rows, 135 x 324 = 43 740 rows (684 slots)
+POOL_SHAPES = {64: [(63, 65), (63, 66)], 12: [(135, 323), (135, 324)]}
+IDENT_SS = lambda C: torch.cat([torch.ones(C), torch.zeros(C), torch.zeros(C), torch.ones(C)]).to(dev())      # scale 1, shift 0, mean 0, rstd 1
+
+
+def _pool_regimes(name, C, rows, dtype, launch, ref_scale):
+    """`launch(ws, dstats)` in the three set-ups: exact against fp64 in each, bit-equal between them, two-pass exactly where the geometry model says"""
+    got = {}
+    for setup in SETUPS:
+        with Ws(setup) as ws:
+            dstats = torch.full((2 * C,), INIT[1], device=dev())
+            used = ws.run(lambda: launch(ws, dstats))
+            case = (C, rows, dtype, setup)
+            check(name, case, "exact", dstats, ref_scale, INIT[1])
+            assert used == (setup == "twopass" and _pool_twopass_expected(rows, C)), (name, case, used)
+            got[setup] = dstats.cpu()
+    assert torch.equal(got["twopass"], got["atomics"]) and torch.equal(got["small"], got["atomics"]), (name, C, rows, dtype)
+    return _pool_twopass_expected(rows, C)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C", [64, 12])
+def test_stem_pool_bwd_reduce(C, dtype):
+    """avec_stem_pool_bwd phase 0: dstats = (sum dr, sum dr * (y - mean) * rstd) over the conv output, dr the pooled gradient routed to each window's winner.  Integer
+    y and dpool with ss = (1, 0, 0, 1): relu(y) = y where a winner exists, so the sums are (sum of dpool over windows with a winner, sum of dpool * pooled output)
+    -- integers.  The window indices come from avec_stem_pool_fwd, whose output is compared with torch's max pool first."""
+    lib, seen = _lib(), set()
+    for k, (H, W) in enumerate(POOL_SHAPES[C]):
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y, yb = put(R.int_tensor((H * W, C), -2, 3, 1400 + k), dtype)
+        dp, dpb = put(R.int_tensor((OH * OW, C), -3, 3, 1410 + k), dtype)
+        ss, gamma = IDENT_SS(C), torch.ones(C, device=dev())
+        out, idx = torch.empty(OH * OW, C, dtype=y.dtype, device=dev()), torch.empty(OH * OW, C, dtype=torch.uint8, device=dev())
+        from avec_amd import runtime as rt
+        lib.stem_pool_fwd(DT[dtype], y.data_ptr(), ss.data_ptr(), out.data_ptr(), idx.data_ptr(), None, 1, H, W, C, rt.stream())
+        torch.cuda.synchronize()
+        pooled = torch.nn.functional.max_pool2d(yb.view(1, H, W, C).permute(0, 3, 1, 2).clamp_min(0), 3, 2, 1).permute(0, 2, 3, 1).reshape(OH * OW, C)
+        assert torch.equal(out.cpu().double(), pooled) and torch.equal(idx.cpu() != 255, pooled > 0), ("stem_pool_fwd", C, H, W)
+        ref_scale = R.reduce([torch.cat([dpb * (pooled > 0), dpb * pooled], 1)])
+        two = _pool_regimes("stem_pool_bwd/0", C, H * W, dtype,
+                            lambda ws, dstats: lib.stem_pool_bwd(DT[dtype], dp.data_ptr(), idx.data_ptr(), y.data_ptr(), ss.data_ptr(), gamma.data_ptr(), dstats.data_ptr(),
+                                                                 None, float(H * W), 0, None, None, None, 1, H, W, C, ws.stream), ref_scale)
+        seen.add("twopass" if two else "atomics")
+    assert seen == {"twopass", "atomics"}, "stem_pool_bwd C=%d: the shape list reached only %s (col_ws_min_atomics retuned?)" % (C, sorted(seen))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_stem_pool_bwd_reduce_pooled(dtype):
+    """avec_stem_pool_bwd_reduce_pooled: dstats = (sum dpool, sum dpool * (ymax - mean) * rstd) over the pooled elements whose window has a winner (idx != 255).
+    63 x 65 = 4095 / 63 x 66 = 4158 pooled rows of C = 64: 128 / 130 blocks of 32 rows around the 16 384-atomics threshold, the last block partial"""
+    lib, seen, C = _lib(), set(), 64
+    for k, (OH, OW) in enumerate(POOL_SHAPES[C]):
+        H, W, P = 2 * OH - 1, 2 * OW - 1, OH * OW
+        dp, dpb = put(R.int_tensor((P, C), -3, 3, 1500 + k), dtype)
+        ym, ymb = put(R.int_tensor((P, C), -2, 3, 1510 + k), dtype)
+        sel = R.int_tensor((P, C), 0, 11, 1520 + k)
+        idx = torch.where(sel > 8, torch.full_like(sel, 255), sel).to(torch.uint8).to(dev())      # a quarter of the windows without a winner
+        ss = IDENT_SS(C)
+        has = (sel <= 8).double()
+        ref_scale = R.reduce([torch.cat([dpb * has, dpb * has * ymb], 1)])
+        two = _pool_regimes("stem_pool_bwd_reduce_pooled", C, P, dtype,
+                            lambda ws, dstats: lib.stem_pool_bwd_reduce_pooled(DT[dtype], dp.data_ptr(), idx.data_ptr(), ym.data_ptr(), ss.data_ptr(), dstats.data_ptr(),
+                                                                               1, H, W, C, ws.stream), ref_scale)
+        seen.add("twopass" if two else "atomics")
+    assert seen == {"twopass", "atomics"}, "stem_pool_bwd_reduce_pooled: the shape list reached only %s (col_ws_min_atomics retuned?)" % sorted(seen)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# visual stem (avec_stem3d_fwd / _wgrad, avec_stem3p_fwd / _reduce / _wgrad): the same clip with the workspace owned by the test, two-pass against atomics
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+LOST_PARTIAL = 1.0 / (2 * 2048)              # the size of one lost partial at the largest slot count (module header)
+# worst twopass-versus-atomics rel_err (max |a - b| / max |b|) per tensor over the four paths (pooled, pooled_unfused, direct, im2col), measured on the parent
+# commit, the one BEFORE the launch sites moved to ColPlan; the bound is 8 x that, the margin this module uses over a measured baseline.  A measured 0 is a bound
+# of 0: the tensor is bit-equal in the two regimes.
+STEM_REGIME_MEASURED = {
+    (1, 3, 72, 40): {"stem output": 0.0, "conv weight gradient": 6.65e-6, "bn weight gradient": 1.7e-7, "running variance (batch statistics)": 6.47e-8, "bn bias gradient": 4.39e-8},
+    (1, 5, 40, 64): {"stem output": 0.0, "conv weight gradient": 3.17e-6, "bn weight gradient": 3.02e-7, "running variance (batch statistics)": 6.43e-8, "bn bias gradient": 2.75e-8},
+}
+# (1, 5, 40, 64) stands in for (1, 5, 48, 64), the W % 8 == 0 shape of tests/test_gpu_parity.py: on the parent the weight gradient at (1, 5, 48, 64) differs by
+# 1.29e-4 between the regimes in some runs (direct and pooled paths), and 8 x that is 1.0e-3, above LOST_PARTIAL; (1, 4, 56, 48) gave 2.04e-4.  (1, 5, 40, 64)
+# (T = 5, W % 8 == 0: all four paths run) and (1, 5, 56, 56) stayed at 3.2e-6 / 1.5e-6.
+STEM_REGIME_SHAPES = [(1, 3, 72, 40), (1, 5, 40, 64)]
+
+
+@pytest.mark.parametrize("shape", STEM_REGIME_SHAPES)
+def test_visual_stem_twopass_matches_atomics(shape):
+    """tests/test_gpu_parity.py's visual-stem comparison (its smallest shape and a T = 5, W % 8 == 0 shape) run twice, with the reduction workspace owned by Ws("twopass")
+    and by Ws("atomics"): the path-against-path assertions of that test hold in each, the poisoned workspace shows that the two-pass branch ran, and every tensor
+    of every path agrees between the regimes within 8 x STEM_REGIME_MEASURED[shape]:
+
+                                                (1, 3, 72, 40)                   (1, 5, 40, 64)
+                                                parent       bound (x 8)        parent       bound (x 8)
+        stem output                             0            0 (bit-equal)      0            0 (bit-equal)
+        conv weight gradient                    6.65e-6      5.3e-5             3.17e-6      2.5e-5
+        bn weight gradient                      1.7e-7       1.4e-6             3.02e-7      2.4e-6
+        running variance (batch statistics)     6.47e-8      5.2e-7             6.43e-8      5.1e-7
+        bn bias gradient                        4.39e-8      3.5e-7             2.75e-8      2.2e-7
+
+    Every bound is below 1 / (2 * 2048) = 2.4e-4: a lost or doubled partial row would not pass."""
+    from tests.helpers import rel_err
+    from tests.test_gpu_parity import STEM_TENSORS, assert_stem_paths_agree, visual_stem_modes
+    res = {}
+    for setup in ("twopass", "atomics"):
+        with Ws(setup) as ws:
+            used = ws.run(lambda: res.__setitem__(setup, visual_stem_modes(shape)))
+            assert used == (setup == "twopass"), (shape, setup)
+        assert_stem_paths_agree(res[setup], shape[3])
+    measured = STEM_REGIME_MEASURED[shape]
+    assert set(measured) == set(STEM_TENSORS) and all(8 * v < LOST_PARTIAL for v in measured.values()), measured
+    worst = {}
+    for path in res["twopass"]:
+        for k, name in enumerate(STEM_TENSORS):
+            e = rel_err(res["atomics"][path][k], res["twopass"][path][k])
+            print("visual stem %s %-15s %-36s twopass vs atomics rel_err %.3g" % (shape, path, name, e))
+            worst[name] = max(worst.get(name, 0.0), e)
+    for name, e in worst.items():
+        assert e <= 8 * measured[name], (shape, name, e, 8 * measured[name])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
