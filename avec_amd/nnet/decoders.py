@@ -22,6 +22,20 @@ def ctc_collapse(tokens, length, blank=0):
     return out
 
 
+def words_from_pieces(pieces, spans, logps):
+    """Word records from aligned sentencepiece pieces (host): a word begins at the first piece and before every piece that starts with "\u2581"; its text is the
+    pieces joined with "\u2581" removed, start = the first piece's start, end = the last piece's end, logp = the sum over its pieces.  Words whose text is empty
+    (a lone "\u2581") are dropped.  spans: (start, end) per piece, in any unit.  Returns [(text, start, end, logp)]."""
+    groups = []
+    for piece, (start, end), lp in zip(pieces, spans, logps):
+        if not groups or piece.startswith("\u2581"):
+            groups.append([piece, start, end, lp])
+        else:
+            g = groups[-1]
+            g[0], g[2], g[3] = g[0] + piece, end, g[3] + lp
+    return [(g[0].replace("\u2581", ""), g[1], g[2], g[3]) for g in groups if g[0].replace("\u2581", "")]
+
+
 class CTCGreedySearchDecoder(nn.Module):
     def __init__(self, tokenizer_path=None, blank_token=0):
         super().__init__()
@@ -45,6 +59,48 @@ class CTCGreedySearchDecoder(nn.Module):
             tokens, lens = outputs
             ids = [t[:int(n)].tolist() for t, n in zip(tokens.cpu(), lens.cpu())]
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
+
+    def align(self, outputs, ids, frame_seconds=0.04):
+        """Token (and word) timestamps of known transcripts: the CTC forced alignment of avec_amd/csrc/ctc_align.hip, one launch for the batch.
+        outputs = (logits [B, T, V], lengths [B]); ids = a list of token lists, or (tokens [B, Lmax], lens [B]) tensors.  One record per utterance:
+        {"score": log-probability of the best path (-inf: the transcript cannot be aligned, e.g. more tokens than frames; "tokens" is then empty),
+         "tokens": [(id, start_frame, end_frame, logp)], "token_seconds": [(start, end)] = frames * frame_seconds (0.04 s = one frame of the 25 fps
+         output of the AV model), and with a tokenizer "words": [(text, start_frame, end_frame, logp)] and "word_seconds": [(start, end)]}.
+        end_frame is exclusive; the blank frames between two tokens belong to neither."""
+        logits, lengths = outputs[0], outputs[1]
+        if isinstance(ids, (tuple, list)) and len(ids) == 2 and torch.is_tensor(ids[0]):
+            tokens, lens = ids[0], ids[1]
+        else:
+            lens = torch.tensor([len(h) for h in ids], dtype=torch.int64)
+            tokens = torch.full((len(ids), max(1, int(lens.max()) if len(ids) else 1)), -1, dtype=torch.int64)
+            for b, h in enumerate(ids):
+                if len(h):
+                    tokens[b, :len(h)] = torch.tensor(list(h), dtype=torch.int64)
+        _, spans, score, logp = ops.ctc_align(logits, lengths, tokens, lens, blank=self.blank_token)
+        tok, n, spans, score, logp = tokens.cpu().tolist(), lens.cpu().tolist(), spans.cpu().tolist(), score.cpu().tolist(), logp.cpu().tolist()
+        records = []
+        for b in range(len(tok)):
+            k = int(n[b]) if score[b] > float("-inf") else 0
+            rec = {"score": score[b], "tokens": [(tok[b][i], spans[b][i][0], spans[b][i][1], logp[b][i]) for i in range(k)]}
+            rec["token_seconds"] = [(s * frame_seconds, e * frame_seconds) for _, s, e, _ in rec["tokens"]]
+            if self.tokenizer is not None:
+                pieces = [self.tokenizer.id_to_piece(t) for t, _, _, _ in rec["tokens"]]
+                rec["words"] = words_from_pieces(pieces, [(s, e) for _, s, e, _ in rec["tokens"]], [lp for _, _, _, lp in rec["tokens"]])
+                rec["word_seconds"] = [(s * frame_seconds, e * frame_seconds) for _, s, e, _ in rec["words"]]
+            records.append(rec)
+        return records
+
+    def _decode_ids(self, logits, logits_len):
+        return self.token_ids(logits, logits_len)
+
+    def decode_with_timestamps(self, outputs, frame_seconds=0.04):
+        """forward(outputs) plus the alignment of the winning hypothesis: (ids, or text with a tokenizer; records as align() returns them)"""
+        if getattr(self, "test_time_aug", False):
+            raise NotImplementedError("decode_with_timestamps with test_time_aug=True: the decoder does not expose which augmentation won, so there are no logits "
+                                      "to align the winning hypothesis to")
+        ids = self._decode_ids(outputs[0], outputs[1])
+        records = self.align(outputs, ids, frame_seconds)
+        return (self.tokenizer.decode(ids) if self.tokenizer is not None else ids), records
 
 
 class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
@@ -160,6 +216,9 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
         tok0, len0 = tokens[:, 0].reshape(B, naug, T).cpu(), out_len[:, 0].reshape(B, naug).cpu()
         best = score[:, 0].reshape(B, naug).cpu().argmax(dim=1)        # the first maximum: ties go to the lower augmentation index
         return [tok0[b, best[b], :len0[b, best[b]]].tolist() for b in range(B)]
+
+    def _decode_ids(self, logits, logits_len):
+        return self.beam_search(logits, logits_len)
 
     def forward(self, outputs, from_logits=True):
         if from_logits:

@@ -1927,6 +1927,32 @@ def ctc_beam_search(logits, lengths, beam, tmp=1.0, lm=None, alpha=0.6, beta=1.0
     return tokens, out_len, score, ctc_logp
 
 
+def ctc_align(logits, logits_len, targets, target_len, blank=0, tier=0):
+    """CTC forced alignment (Viterbi) of targets [B, Lmax] (target_len [B]) to logits [B, T, V] (logits_len [B]): one launch for the whole batch, no host
+    synchronisation.  Returns path [B, T] int32 (the token of every frame, -1 past logits_len), spans [B, Lmax, 2] int32 ((first frame, last frame + 1) of every
+    target token, -1 past target_len), score [B] (log-probability of the best path) and token_logp [B, Lmax]; an utterance that cannot be aligned has score -inf,
+    path and spans -1 (include/avec_hip.h: avec_ctc_align).  tier: 0 auto, 1 all-LDS, 2 workspace (same results bit for bit)."""
+    rt.require_gpu(logits)
+    B, T, V = logits.shape
+    lg = _f32c(logits)
+    dev = lg.device
+    tg = targets.to(device=dev, dtype=torch.int64)
+    if tg.dim() == 1:
+        tg = tg.view(B, -1)
+    tg = tg.contiguous()
+    Lmax = tg.shape[1]
+    il = logits_len.to(device=dev, dtype=torch.int64).contiguous()
+    tl = target_len.to(device=dev, dtype=torch.int64).contiguous()
+    ws = torch.empty(max(16, lib.raw("avec_ctc_align_workspace_bytes")(B, T, Lmax)), dtype=torch.uint8, device=dev)
+    path = torch.empty(B, T, dtype=torch.int32, device=dev)
+    spans = torch.empty(B, Lmax, 2, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    token_logp = torch.empty(B, Lmax, dtype=torch.float32, device=dev)
+    lib.ctc_align(lg.data_ptr(), il.data_ptr(), _p(tg), tl.data_ptr(), B, T, V, Lmax, blank, tier, ws.data_ptr(), ws.numel(),
+                  path.data_ptr(), _p(spans), score.data_ptr(), _p(token_logp), rt.stream())
+    return path, spans, score, token_logp
+
+
 def ngram_rows(lm, contexts):
     """ln P(. | ctx) [n, V] on the device for a list of token histories (oldest first, -1 = <s>): avec_ngram_rows"""
     dev = torch.device("cuda", torch.cuda.current_device())

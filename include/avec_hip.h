@@ -455,6 +455,25 @@ int avec_ctc_beam_search(const float* logits, const long long* lengths, int B, i
 /* rows[i][c] = ln P(c | ctx_i) as the beam search sees it: ctx [n][max_len] int32 tokens oldest first (-1 = <s>), ctx_len [n]; only the last order-1
  * tokens of a context are used.  Test and documentation aid for the table layout above. */
 int avec_ngram_rows(const avec_ngram_t* lm, const int* ctx, const int* ctx_len, int n, int max_len, float oov_logprob, float* rows, hipStream_t stream);
+/* ---- CTC forced alignment (avec_amd/csrc/ctc_align.hip): token timestamps for a GIVEN label sequence ------------------------------------------------
+ * Viterbi (best-path) alignment of targets to CTC logits: argmax over paths pi with collapse(pi) == target of sum_t log_softmax(logits[t])[pi_t].
+ * Inputs as avec_ctc_loss: logits [B][T][V] fp32, in_lens [B] int64 (clamped to [0, T]), targets [B][Lmax] int64, tgt_lens [B] int64 (clamped to [0, Lmax]).
+ * Outputs: path [B][T] int32 = the token of every frame, blank included (-1 for t >= in_len); spans [B][Lmax][2] int32 = (first frame, last frame + 1) of the frames
+ * that emit target token i (-1, -1 for i >= tgt_len; the blank frames between tokens belong to no token); score [B] = the log-probability of the best path;
+ * token_logp [B][Lmax] = the sum of log_softmax over the token's own frames (0 for i >= tgt_len).
+ * Infeasible utterance (in_len < tgt_len + number of adjacent equal targets, or a target inside tgt_len that equals blank or lies outside [0, V)): score = -inf,
+ * path and spans all -1, token_logp 0; such a target is never used as an index and targets at or past tgt_len are never read.  tgt_len == 0 is feasible (all blank);
+ * in_len == 0 == tgt_len gives score 0.  Logits without a path of finite probability (-inf / NaN) give the infeasible outputs too.
+ * Tie rule over the S = 2 L + 1 extended states, recursion in fp32, delta_t[s] = max(...) + (logits[t][ext[s]] - lse[t]): the predecessor of s is s unless
+ * delta[s-1] is strictly greater; s-2 (allowed when ext[s] != blank && ext[s] != ext[s-2]) only if strictly greater than the winner of those two; the end state is
+ * S-1 unless delta[S-2] is strictly greater.  tier: 0 = auto (1 when avec_ctc_align_fits_lds), 1 = emissions and backpointers in LDS (an argument error when the
+ * shape does not fit), 2 = in the workspace; the tiers agree bit for bit.  workspace: avec_ctc_align_workspace_bytes, 16-byte aligned, required for every tier. */
+long long avec_ctc_align_workspace_bytes(int B, int T, int Lmax);
+int avec_ctc_align_fits_lds(int T, int Lmax);          /* 1 when the all-LDS tier can run this shape */
+int avec_ctc_align(const float* logits, const long long* in_lens, const long long* targets, const long long* tgt_lens,
+                   int B, int T, int V, int Lmax, int blank, int tier /* 0 auto, 1 all-LDS, 2 workspace */,
+                   void* workspace, long long workspace_bytes,
+                   int* path, int* spans, float* score, float* token_logp, hipStream_t stream);
 /* ---- Transformer-LM (GPT) rescoring of the beam (avec_amd/csrc/lm.hip; CTCBeamSearchDecoder's neural rescorer, nnet/decoders.py:208-242) -- inference only ----------------
  * x[n][t][:] = E[ids[n][t]][:] + P[t][:]: nn.Embedding (V x D fp32 table; an id outside [0, V) is clamped) plus the rows of SinPosEmbedding / PosEmbedding1d
  * (nnet/embeddings.py:20-62, fp32 [>= L][D]).  ids int64 [N][L]; out [N*L][D] act, or fp32 when out_f32 (the residual stream).  D % 8 == 0, 16-byte aligned tables. */
