@@ -13,6 +13,11 @@
 // find the W-th largest key by a bitwise search of counts (ballot / wave sums): no sort, no atomics.
 // A prefix is identified by a 64-bit rolling hash; an extension (i, c) re-creates beam j when hash(j's parent) = hash(i), len(j) = len(i) + 1 and
 // last(j) = c (node ids would not do: a prefix can be dropped and created again later).
+//
+// Streaming (avec_ctc_beam_stream): the same kernel with STREAM set.  Everything a frame hands to the next one is the current Beams buffer, n_live and the
+// backpointer rows, so a launch that loads the buffer from a caller-owned state at its start and stores it at its end can stop after any frame and go on in a
+// later launch: per utterance the state is the W * BEAM_BYTES_PER_SLOT bytes of the buffer (always loaded into st0) plus a 16-byte header {n_live, frames
+// consumed, tag of (W, LM order), Tcap}.  The frame body is this one loop for both, so chunked and offline searches do the same arithmetic in the same order.
 #include "common.h"
 #include "avec_hip.h"
 
@@ -138,9 +143,13 @@ struct BeamArgs {
   const float* logits; const long long* lengths; int T, V, W; float inv_tmp;
   avec_ngram_t lm; float alpha, beta, oov;
   int* bp; int* tokens; int* out_len; float* score; float* ctc_logp;
+  // streaming only: lengths = frames of this chunk per utterance (null: T), T = frames per utterance in `logits`, Tcap = rows of bp and of tokens
+  int Tcap, emit; const unsigned char* reset; unsigned char* state; int* stable_len;
 };
+constexpr int STATE_TAG = 0x43544342;
+__host__ __device__ inline size_t state_stride(int W) { return a16((size_t)W * BEAM_BYTES_PER_SLOT) + 16; }
 
-template <bool LM>
+template <bool LM, bool STREAM>
 __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -149,12 +158,27 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
   u64* ck = (u64*)(sm + L.ck); float* cpnb = (float*)(sm + L.cpnb); float* clm = (float*)(sm + L.clm); float* spb = (float*)(sm + L.spb);
   float* logp_s = (float*)(sm + L.logp); float* rows = (float*)(sm + L.rows);
   u64* selk = (u64*)(sm + L.selk); int* selp = (int*)(sm + L.selp); int* n_live = (int*)(sm + L.misc);
-  const long long len_ll = a.lengths[b];
-  const int len = len_ll < 0 ? 0 : (len_ll > T ? T : (int)len_ll);
+  const int TO = STREAM ? a.Tcap : T;                  // rows of bp and of tokens
+  const long long len_ll = (STREAM && !a.lengths) ? T : a.lengths[b];
+  int len = len_ll < 0 ? 0 : (len_ll > T ? T : (int)len_ll);
   const float* lg = a.logits + (size_t)b * T * V;
-  int* bp = a.bp + (size_t)b * T * W;
-
-  if (tid == 0) {                                      // the empty prefix
+  int* bp = a.bp + (size_t)b * TO * W;
+  int t0 = 0;                                          // frames consumed by earlier launches
+  bool fresh = true;
+  if constexpr (STREAM) {
+    const int* st = (const int*)(a.state + (size_t)b * state_stride(W));
+    const int* hdr = st + a16((size_t)W * BEAM_BYTES_PER_SLOT) / 4;
+    // a state this kernel did not write for the same W, LM order and Tcap (zeroed memory, say) starts from the empty prefix: its fields index LDS and bp
+    fresh = (a.reset && a.reset[b]) || hdr[2] != (STATE_TAG ^ (W | K << 8)) || hdr[3] != TO || hdr[0] < 0 || hdr[0] > W || hdr[1] < 0 || hdr[1] > TO;
+    if (!fresh) {
+      t0 = hdr[1];
+      int* dst = (int*)(sm + L.st0);
+      for (int q = tid; q < W * (BEAM_BYTES_PER_SLOT / 4); q += NT) dst[q] = st[q];
+      if (tid == 0) *n_live = hdr[0];
+    }
+    len = len < TO - t0 ? len : TO - t0;
+  }
+  if (fresh && tid == 0) {                             // the empty prefix
     const Beams s = carve(sm + L.st0, W);
     s.hash[0] = H_EMPTY; s.phash[0] = 0; s.pb[0] = 0.f; s.pnb[0] = -INFINITY; s.lm[0] = 0.f; s.last[0] = -1; s.len[0] = 0;
     s.clen[0] = K > 0 ? 1 : 0;
@@ -281,7 +305,7 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
           code = i | ((c + 1) << 8);
         }
         N.pnb[r] = cpnb[p]; N.lm[r] = clm[p];
-        bp[(size_t)t * W + r] = code;
+        bp[(size_t)(t0 + t) * W + r] = code;
       }
       if (lane == 0) *n_live = ns;
     }
@@ -290,24 +314,53 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
   }
   const Beams S = carve(sm + (cur ? L.st1 : L.st0), W);
   const int nl = *n_live;
-  int* tok = a.tokens + (size_t)b * W * T;
+  if constexpr (STREAM) {
+    int* st = (int*)(a.state + (size_t)b * state_stride(W));
+    const int* src = (const int*)(sm + (cur ? L.st1 : L.st0));
+    for (int q = tid; q < W * (BEAM_BYTES_PER_SLOT / 4); q += NT) st[q] = src[q];
+    if (tid == 0) {
+      int* hdr = st + a16((size_t)W * BEAM_BYTES_PER_SLOT) / 4;
+      hdr[0] = nl; hdr[1] = t0 + len; hdr[2] = STATE_TAG ^ (W | K << 8); hdr[3] = TO;
+    }
+    if (!a.emit) return;
+  }
+  int* tok = a.tokens + (size_t)b * W * TO;
   if (tid < W) {
     const int w = tid;
     float sc = -INFINITY, cl = -INFINITY; int ol = 0;
     if (w < nl) {
       cl = lse2(S.pb[w], S.pnb[w]); sc = cl + S.lm[w]; ol = S.len[w];
       int slot = w, pos = ol - 1;
-      for (int t = len - 1; t >= 0 && pos >= 0; --t) {   // walk the backpointers
+      for (int t = t0 + len - 1; t >= 0 && pos >= 0; --t) {   // walk the backpointers (streaming: through every frame so far)
         const int code = bp[(size_t)t * W + slot];
-        if (code >> 8) tok[(size_t)w * T + pos--] = (code >> 8) - 1;
+        if (code >> 8) tok[(size_t)w * TO + pos--] = (code >> 8) - 1;
         slot = code & 255;
+        if (STREAM && slot >= W) slot = 0;               // (rows a caller swapped under the state: stay inside the buffer)
       }
     }
     a.score[(size_t)b * W + w] = sc; a.ctc_logp[(size_t)b * W + w] = cl; a.out_len[(size_t)b * W + w] = ol;
   }
-  for (int q = tid; q < W * T; q += NT) {
-    const int w = q / T, k = q - w * T;
+  for (int q = tid; q < W * TO; q += NT) {
+    const int w = q / TO, k = q - w * TO;
     if (k >= (w < nl ? S.len[w] : 0)) tok[q] = 0;
+  }
+  if constexpr (STREAM) {                              // the longest common prefix of the live beams: every later hypothesis extends one of them
+    int* common = n_live + 1;
+    if (tid == 0) {
+      int m = nl > 0 ? S.len[0] : 0;
+      for (int w = 1; w < nl; ++w) m = m < S.len[w] ? m : S.len[w];
+      *common = m;
+    }
+    __syncthreads();                                   // tokens of all beams written, *common set
+    const int m = *common;
+    for (int k = tid; k < m; k += NT) {
+      const int c = tok[k];
+      bool same = true;
+      for (int w = 1; w < nl; ++w) same = same && tok[(size_t)w * TO + k] == c;
+      if (!same) atomicMin(common, k);
+    }
+    __syncthreads();
+    if (tid == 0) a.stable_len[b] = *common;
   }
 }
 
@@ -345,13 +398,45 @@ extern "C" int avec_ctc_beam_search(const float* logits, const long long* length
   a.lm = avec_ngram_t{}; a.alpha = alpha; a.beta = beta; a.oov = oov_logprob;
   a.bp = (int*)workspace; a.tokens = tokens; a.out_len = out_len; a.score = score; a.ctc_logp = ctc_logp;
   if (lm) { if (int r = check_lm(lm, V)) return r; a.lm = *lm; }
+  a.Tcap = T; a.emit = 1; a.reset = nullptr; a.state = nullptr; a.stable_len = nullptr;
   const size_t bytes = lay(W, V, lm != nullptr).total;
   if (lm) {
-    if (int r = avec_lds_optin(ctc_beam_kernel<true>, bytes)) return r;
-    hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(B), dim3(NT), bytes, st, a);
+    if (int r = avec_lds_optin(ctc_beam_kernel<true, false>, bytes)) return r;
+    hipLaunchKernelGGL((ctc_beam_kernel<true, false>), dim3(B), dim3(NT), bytes, st, a);
   } else {
-    if (int r = avec_lds_optin(ctc_beam_kernel<false>, bytes)) return r;
-    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(B), dim3(NT), bytes, st, a);
+    if (int r = avec_lds_optin(ctc_beam_kernel<false, false>, bytes)) return r;
+    hipLaunchKernelGGL((ctc_beam_kernel<false, false>), dim3(B), dim3(NT), bytes, st, a);
+  }
+  AVEC_LAUNCH_CHECK(); return 0;
+}
+
+extern "C" long long avec_ctc_beam_state_bytes(int B, int W) { return (long long)B * (long long)state_stride(W); }
+
+extern "C" int avec_ctc_beam_stream(const float* logits, const long long* chunk_len, const unsigned char* reset, int B, int Tc, int V, int W, int Tcap, float inv_tmp,
+                                    const avec_ngram_t* lm, float alpha, float beta, float oov_logprob, void* state, long long state_bytes, void* backptr,
+                                    long long backptr_bytes, int* tokens, int* out_len, float* score, float* ctc_logp, int* stable_len, int emit, hipStream_t st) {
+  AVEC_CHECK_ARG(logits && state && backptr, "ctc_beam_stream: null pointer");
+  AVEC_CHECK_ARG(!emit || (tokens && out_len && score && ctc_logp && stable_len), "ctc_beam_stream: null output with emit set");
+  AVEC_CHECK_ARG(B >= 1 && Tc >= 1 && Tcap >= 1 && V >= 2 && V <= MAXV && W >= 1 && W <= MAXW,
+                 "ctc_beam_stream: bad dims B=%d Tc=%d Tcap=%d V=%d W=%d (Tc >= 1, Tcap >= 1, V <= %d, W <= %d)", B, Tc, Tcap, V, W, MAXV, MAXW);
+  AVEC_CHECK_ARG(state_bytes >= avec_ctc_beam_state_bytes(B, W), "ctc_beam_stream: state of %lld bytes, need %lld", state_bytes, avec_ctc_beam_state_bytes(B, W));
+  AVEC_CHECK_ARG(backptr_bytes >= avec_ctc_beam_workspace_bytes(B, Tcap, W), "ctc_beam_stream: backpointers of %lld bytes, need %lld", backptr_bytes,
+                 avec_ctc_beam_workspace_bytes(B, Tcap, W));
+  AVEC_CHECK_ARG(((size_t)state & 15) == 0, "ctc_beam_stream: the state must be 16-byte aligned");
+  AVEC_CHECK_ARG(inv_tmp > 0.f, "ctc_beam_stream: 1/tmp must be > 0");
+  BeamArgs a;
+  a.logits = logits; a.lengths = chunk_len; a.T = Tc; a.V = V; a.W = W; a.inv_tmp = inv_tmp;
+  a.lm = avec_ngram_t{}; a.alpha = alpha; a.beta = beta; a.oov = oov_logprob;
+  a.bp = (int*)backptr; a.tokens = tokens; a.out_len = out_len; a.score = score; a.ctc_logp = ctc_logp;
+  a.Tcap = Tcap; a.emit = emit; a.reset = reset; a.state = (unsigned char*)state; a.stable_len = stable_len;
+  if (lm) { if (int r = check_lm(lm, V)) return r; a.lm = *lm; }
+  const size_t bytes = lay(W, V, lm != nullptr).total;
+  if (lm) {
+    if (int r = avec_lds_optin(ctc_beam_kernel<true, true>, bytes)) return r;
+    hipLaunchKernelGGL((ctc_beam_kernel<true, true>), dim3(B), dim3(NT), bytes, st, a);
+  } else {
+    if (int r = avec_lds_optin(ctc_beam_kernel<false, true>, bytes)) return r;
+    hipLaunchKernelGGL((ctc_beam_kernel<false, true>), dim3(B), dim3(NT), bytes, st, a);
   }
   AVEC_LAUNCH_CHECK(); return 0;
 }

@@ -1927,6 +1927,53 @@ def ctc_beam_search(logits, lengths, beam, tmp=1.0, lm=None, alpha=0.6, beta=1.0
     return tokens, out_len, score, ctc_logp
 
 
+class CTCBeamStreamState:
+    """Everything a streaming beam search keeps between pushes (ops.ctc_beam_stream), allocated once: the beam state and backpointer rows of avec_ctc_beam_stream,
+    the outputs it writes when it emits, and a reset flag buffer.  batch utterance slots, `beam` beams, at most max_frames frames per utterance.  A zero-filled
+    state is a reset one."""
+
+    def __init__(self, batch, beam, max_frames, device=None):
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.B, self.W, self.Tcap = int(batch), int(beam), int(max_frames)
+        if self.B < 1 or self.Tcap < 1 or not 1 <= self.W <= 64:
+            raise ValueError("CTCBeamStreamState: batch %d, beam %d (1..64), max_frames %d" % (self.B, self.W, self.Tcap))
+        self.state = torch.zeros(lib.raw("avec_ctc_beam_state_bytes")(self.B, self.W), dtype=torch.uint8, device=dev)
+        self.backptr = torch.empty(lib.raw("avec_ctc_beam_workspace_bytes")(self.B, self.Tcap, self.W), dtype=torch.uint8, device=dev)
+        self.tokens = torch.zeros(self.B, self.W, self.Tcap, dtype=torch.int32, device=dev)
+        self.out_len = torch.zeros(self.B, self.W, dtype=torch.int32, device=dev)
+        self.score = torch.full((self.B, self.W), float("-inf"), dtype=torch.float32, device=dev)
+        self.ctc_logp = torch.full((self.B, self.W), float("-inf"), dtype=torch.float32, device=dev)
+        self.stable_len = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.reset_flags = torch.zeros(self.B, dtype=torch.uint8, device=dev)
+
+
+def ctc_beam_stream(st, logits, chunk_len=None, reset=None, tmp=1.0, lm=None, alpha=0.6, beta=1.0, emit=True):
+    """One push of the streaming CTC prefix beam search: `st` (a CTCBeamStreamState) consumes the chunk logits [B, Tc, V]; utterance b takes chunk_len[b] frames
+    (int64 [B] on the device; None: all Tc), clamped so that it never holds more than st.Tcap.  reset: None, or a uint8 / bool mask [B] on the device whose set
+    slots restart from the empty prefix before the chunk.  tmp, lm, alpha, beta as ops.ctc_beam_search, the same for every push of a session.  With emit the
+    state's tokens [B, W, Tcap], out_len, score, ctc_logp hold what ops.ctc_beam_search gives on the frames pushed so far (bit for bit) and stable_len [B] the
+    length of the common prefix of the live beams, which no later frame can change; they are returned (views of st, overwritten by the next emitting push).
+    One launch, no host synchronisation, no allocation beyond the fp32 conversion of the chunk."""
+    B, Tc, V = logits.shape
+    if B != st.B:
+        raise ValueError("ctc_beam_stream: chunk of %d utterances for a state of %d" % (B, st.B))
+    lg = _f32c(logits)
+    dev = st.state.device
+    if lg.device != dev:
+        raise ValueError("ctc_beam_stream: chunk on %s, state on %s" % (lg.device, dev))
+    if chunk_len is not None and not (chunk_len.dtype == torch.int64 and chunk_len.device == dev and chunk_len.is_contiguous() and chunk_len.numel() == B):
+        chunk_len = chunk_len.to(device=dev, dtype=torch.int64).contiguous().view(B)
+    if reset is not None and not (reset.device == dev and reset.is_contiguous() and reset.numel() == B and reset.dtype in (torch.uint8, torch.bool)):
+        raise ValueError("ctc_beam_stream: reset must be a contiguous uint8 / bool mask [B] on the state's device")
+    use_lm = lm is not None and lm.usable
+    lm_arg = _byref(lm.device_struct(dev)) if use_lm else None
+    oov = lm.oov_logprob if use_lm else 0.0
+    lib.ctc_beam_stream(lg.data_ptr(), _p(chunk_len), _p(reset), B, Tc, V, st.W, st.Tcap, 1.0 / tmp, lm_arg, alpha if use_lm else 0.0, beta if use_lm else 0.0, oov,
+                        st.state.data_ptr(), st.state.numel(), st.backptr.data_ptr(), st.backptr.numel(), st.tokens.data_ptr(), st.out_len.data_ptr(),
+                        st.score.data_ptr(), st.ctc_logp.data_ptr(), st.stable_len.data_ptr(), 1 if emit else 0, rt.stream())
+    return (st.tokens, st.out_len, st.score, st.ctc_logp, st.stable_len) if emit else None
+
+
 def ctc_align(logits, logits_len, targets, target_len, blank=0, tier=0):
     """CTC forced alignment (Viterbi) of targets [B, Lmax] (target_len [B]) to logits [B, T, V] (logits_len [B]): one launch for the whole batch, no host
     synchronisation.  Returns path [B, T] int32 (the token of every frame, -1 past logits_len), spans [B, Lmax, 2] int32 ((first frame, last frame + 1) of every

@@ -452,6 +452,23 @@ long long avec_ctc_beam_workspace_bytes(int B, int T, int W);
  * score = ctc_logp = -inf, out_len = 0.  Limits: W <= 64, V <= 1024, order <= 8.  workspace: avec_ctc_beam_workspace_bytes. */
 int avec_ctc_beam_search(const float* logits, const long long* lengths, int B, int T, int V, int W, float inv_tmp, const avec_ngram_t* lm, float alpha, float beta,
                          float oov_logprob, void* workspace, long long workspace_bytes, int* tokens, int* out_len, float* score, float* ctc_logp, hipStream_t stream);
+/* Streaming form of avec_ctc_beam_search: the same search, carried across launches by a caller-owned state, so logits can be decoded chunk by chunk as an
+ * encoder emits them.  Pushing an utterance's frames in any split gives, bit for bit, what avec_ctc_beam_search gives on the frames pushed so far (the frame
+ * loop is the same code; a launch only loads the beam at its start and stores it at its end).  The library keeps no pointers between calls.
+ * state: avec_ctc_beam_state_bytes(B, W) bytes, 16-byte aligned: per utterance the W beam slots and {live beams, frames consumed}.  An utterance starts from the
+ * empty prefix when reset[b] != 0 (reset: [B] bytes, NULL = none), and also when its state was not written by this entry point with the same W, LM order and
+ * Tcap (zero-filled memory, for instance).  Use the same V, W, Tcap, inv_tmp, LM, alpha, beta and backpointer buffer for every push of a session.
+ * logits [B][Tc][V] fp32; chunk_len [B] int64 = frames of this chunk that utterance b consumes (NULL: Tc), clamped to [0, Tc] and to Tcap - frames consumed, so
+ * an utterance never holds more than Tcap frames (0 leaves it as it is; with reset it becomes the empty prefix).  backptr: avec_ctc_beam_workspace_bytes(B, Tcap, W)
+ * bytes, [B][Tcap][W]; a push writes the rows of its own frames.
+ * emit != 0 also writes, for the frames consumed so far, tokens [B][W][Tcap] (zero past out_len), out_len, score and ctc_logp exactly as avec_ctc_beam_search does,
+ * and stable_len [B] int32 = the length of the longest common prefix of the live beams: every later hypothesis extends a live beam, so
+ * tokens[b][0][0 .. stable_len[b]) is final.  The traceback walks every frame consumed so far.  emit == 0 writes no output (the five pointers may be NULL).
+ * Limits as avec_ctc_beam_search: W <= 64, V <= 1024, order <= 8; Tc >= 1, Tcap >= 1. */
+long long avec_ctc_beam_state_bytes(int B, int W);
+int avec_ctc_beam_stream(const float* logits, const long long* chunk_len, const unsigned char* reset, int B, int Tc, int V, int W, int Tcap, float inv_tmp,
+                         const avec_ngram_t* lm, float alpha, float beta, float oov_logprob, void* state, long long state_bytes, void* backptr, long long backptr_bytes,
+                         int* tokens, int* out_len, float* score, float* ctc_logp, int* stable_len, int emit, hipStream_t stream);
 /* rows[i][c] = ln P(c | ctx_i) as the beam search sees it: ctx [n][max_len] int32 tokens oldest first (-1 = <s>), ctx_len [n]; only the last order-1
  * tokens of a context are used.  Test and documentation aid for the table layout above. */
 int avec_ngram_rows(const avec_ngram_t* lm, const int* ctx, const int* ctx_len, int n, int max_len, float oov_logprob, float* rows, hipStream_t stream);
