@@ -1,6 +1,8 @@
 """Decoders (nnet/decoders.py).  Greedy CTC: device argmax (HIP) + exact integer collapse.  Beam search: the CTC prefix beam search with n-gram LM
 fusion of avec_amd/csrc/ctc_beam.hip (in place of `ctcdecode` + KenLM), then the Transformer-LM (GPT) rescoring of the beams (avec_amd/csrc/lm.hip): all
-hypotheses of a batch in one scoring pass."""
+hypotheses of a batch in one scoring pass.  Timestamps: the CTC forced alignment of avec_amd/csrc/ctc_align.hip.  Test-time augmentation
+([B, Naug, T, V] logits): beam_search picks the winner on the host; decode_augmented picks it on the device (avec_amd/csrc/tta.hip), says which augmentation won and
+aligns the winner to that augmentation's logits."""
 import importlib.util
 import os
 import sys
@@ -77,7 +79,10 @@ class CTCGreedySearchDecoder(nn.Module):
                 if len(h):
                     tokens[b, :len(h)] = torch.tensor(list(h), dtype=torch.int64)
         _, spans, score, logp = ops.ctc_align(logits, lengths, tokens, lens, blank=self.blank_token)
-        tok, n, spans, score, logp = tokens.cpu().tolist(), lens.cpu().tolist(), spans.cpu().tolist(), score.cpu().tolist(), logp.cpu().tolist()
+        return self._align_records(tokens.cpu().tolist(), lens.cpu().tolist(), spans.cpu().tolist(), score.cpu().tolist(), logp.cpu().tolist(), frame_seconds)
+
+    def _align_records(self, tok, n, spans, score, logp, frame_seconds):
+        """the records of align() from host lists: tok [B][Lmax], n [B], spans [B][Lmax][2], score [B], logp [B][Lmax]"""
         records = []
         for b in range(len(tok)):
             k = int(n[b]) if score[b] > float("-inf") else 0
@@ -96,8 +101,8 @@ class CTCGreedySearchDecoder(nn.Module):
     def decode_with_timestamps(self, outputs, frame_seconds=0.04):
         """forward(outputs) plus the alignment of the winning hypothesis: (ids, or text with a tokenizer; records as align() returns them)"""
         if getattr(self, "test_time_aug", False):
-            raise NotImplementedError("decode_with_timestamps with test_time_aug=True: the decoder does not expose which augmentation won, so there are no logits "
-                                      "to align the winning hypothesis to")
+            raise NotImplementedError("decode_with_timestamps with test_time_aug=True: it takes [B, T, V] logits; CTCBeamSearchDecoder.decode_augmented(outputs, "
+                                      "timestamps=True) aligns the winning hypothesis to the logits of the augmentation that won")
         ids = self._decode_ids(outputs[0], outputs[1])
         records = self.align(outputs, ids, frame_seconds)
         return (self.tokenizer.decode(ids) if self.tokenizer is not None else ids), records
@@ -109,7 +114,8 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
     The ranking score is ln P_ctc(prefix) + the summed LM terms (higher is better), and a token that is not an LM word costs ln P = -1000.  ctcdecode's
     own score convention and OOV constant cannot be checked against here (ctcdecode and kenlm are not available), so they are not claimed.
     A missing or empty ARPA file means beam search without an LM (warned).  test_time_aug: logits [B, Naug, T, V], lengths [B, Naug]; per utterance
-    the augmentation whose best beam scores highest (ties: the lower index).
+    the augmentation whose best beam scores highest (ties: the lower index); decode_augmented returns the same hypotheses together with the winning augmentation
+    and beam and, on request, the timestamps against that augmentation's logits.
     Neural rescoring (nnet/decoders.py:156-162,208-242): when `neural_config_path` names an existing config file and `os.path.join(config.callback_path,
     neural_checkpoint)` exists, the config is imported, its `model` (anything with `score(ids, lengths)` and `load(path)`; nnet.GPT in the shipped configs) loads the
     checkpoint and is put in eval mode.  Every non-empty beam slot then becomes [sos] + retokenise(tokens) + [eos] (retokenise = neural tokenizer over the decoder
@@ -171,8 +177,9 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
             return hyps
         return self.neural_tokenizer.encode(self.tokenizer.decode(hyps))
 
-    def _rescore(self, tokens, out_len, score, B, naug):
-        """tokens [S, W, T], out_len [S, W], score [S, W] of ops.ctc_beam_search (S = B * naug) -> per utterance the winning token list"""
+    def _rescore_best(self, tokens, out_len, score, B, naug):
+        """tokens [S, W, T], out_len [S, W], score [S, W] of ops.ctc_beam_search (S = B * naug) -> (best [B] int64 on the device: the winning slot in [0, naug * W),
+        the host copies of tokens and out_len)"""
         S, W, T = tokens.shape
         tok, ol, alive = tokens.cpu(), out_len.cpu().tolist(), (score > float("-inf")).cpu().tolist()
         slots = [(s, w) for s in range(S) for w in range(W) if alive[s][w]]
@@ -190,6 +197,12 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
             lm.to(dev)
         best, total, _ = ops.lm_rescore(lm, ids.to(dev), lens.to(dev), score.reshape(-1), self.neural_alpha, self.neural_beta, B)
         self.last_totals = total                                             # [B, naug * W], stays on the device (tests read it)
+        return best, tok, ol
+
+    def _rescore(self, tokens, out_len, score, B, naug):
+        """... -> per utterance the winning token list"""
+        W = tokens.shape[1]
+        best, tok, ol = self._rescore_best(tokens, out_len, score, B, naug)
         out = []
         for b, k in enumerate(best.cpu().tolist()):
             s, w = b * naug + k // W, k % W
@@ -217,11 +230,56 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
         best = score[:, 0].reshape(B, naug).cpu().argmax(dim=1)        # the first maximum: ties go to the lower augmentation index
         return [tok0[b, best[b], :len0[b, best[b]]].tolist() for b in range(B)]
 
+    def decode_augmented(self, outputs, timestamps=False, frame_seconds=0.04):
+        """Decode test-time-augmented logits and say which augmentation won: outputs = (logits [B, n, T, V], lengths [B, n]) as VisualEfficientConformerInterCTC
+        gives them with test_augments (n = 1 is valid).  Returns (ids per utterance, or text with a tokenizer; records), one record per utterance:
+        {"ids": the winning token list (what beam_search returns), "augmentation": the index along n it came from (0 = the clip as given), "beam": its beam slot,
+         "score": its ranking score (-inf: every slot of the utterance is empty)}.  The winner is beam_search's: without a neural rescorer the augmentation whose best
+        beam scores highest (first maximum) and beam 0; with one, the first maximum of the rescored totals over the n * W slots.
+        timestamps=True adds every field of align() for the winning hypothesis against the logits of the augmentation that won ("tokens", "token_seconds", with a
+        tokenizer "words" and "word_seconds"); align()'s "score", the log-probability of the best path, is stored as "align_score".
+        The beam search, the choice (ops.ctc_tta_pick), the gather of the winners' logits and the alignment stay on the device; the results come back in ONE
+        device-to-host copy at the end.  (A neural rescorer fetches the beams before that to retokenise them, as in beam_search.)"""
+        logits, lengths = outputs[0], outputs[1]
+        if logits.dim() != 4 or tuple(lengths.shape) != tuple(logits.shape[:2]):
+            raise ValueError("decode_augmented: logits %s, lengths %s; expected [B, n, T, V] and [B, n]" % (tuple(logits.shape), tuple(lengths.shape)))
+        B, n, T, V = logits.shape
+        flat, flat_len = logits.flatten(0, 1), lengths.flatten(0, 1).to(device=logits.device, dtype=torch.int64)
+        tokens, out_len, score, _ = ops.ctc_beam_search(flat, flat_len, self.beam_size, self.ngram_tmp, self.lm(V), self.ngram_alpha, self.ngram_beta)
+        best_slot = self._rescore_best(tokens, out_len, score, B, n)[0] if self.neural_rescorer is not None else None
+        aug, beam, ids, ids_len, best_score = ops.ctc_tta_pick(tokens, out_len, score, n, best_slot)
+        parts = [aug, beam, ids_len, best_score, ids.reshape(-1)]
+        if timestamps:
+            rows = torch.arange(B, device=aug.device) * n + aug                  # the winners' rows of the flattened batch
+            _, spans, a_score, logp = ops.ctc_align(flat.index_select(0, rows), flat_len.index_select(0, rows), ids, ids_len, blank=self.blank_token)
+            parts += [a_score, spans.reshape(-1), logp.reshape(-1)]
+        host = torch.cat([p.to(torch.float64) for p in parts]).cpu().tolist()   # (every value is an int32-range integer or an fp32: exact in fp64) the one fetch
+
+        def take(k, integer):
+            out = host[take.at:take.at + k]
+            take.at += k
+            return [int(v) for v in out] if integer else out
+        take.at = 0
+        aug, beam, ids_len, best_score = take(B, True), take(B, True), take(B, True), take(B, False)
+        ids = take(B * T, True)
+        tok = [ids[b * T:(b + 1) * T] for b in range(B)]
+        records = [{"ids": tok[b][:ids_len[b]], "augmentation": aug[b], "beam": beam[b], "score": best_score[b]} for b in range(B)]
+        if timestamps:
+            a_score, spans, logp = take(B, False), take(B * T * 2, True), take(B * T, False)
+            spans = [[spans[(b * T + i) * 2:(b * T + i) * 2 + 2] for i in range(T)] for b in range(B)]
+            logp = [logp[b * T:(b + 1) * T] for b in range(B)]
+            for rec, al in zip(records, self._align_records(tok, ids_len, spans, a_score, logp, frame_seconds)):
+                al["align_score"] = al.pop("score")
+                rec.update(al)
+        hyps = [r["ids"] for r in records]
+        return (self.tokenizer.decode(hyps) if self.tokenizer is not None else hyps), records
+
     def stream(self, batch_size, max_frames):
         """A streaming session (CTCBeamStreamSession) over batch_size utterance slots of at most max_frames frames each: push logits chunk by chunk as the
         encoder emits them, read the partial and the final part of the transcript after every chunk, finish() for what beam_search gives on the whole."""
         if self.test_time_aug:
-            raise NotImplementedError("CTCBeamSearchDecoder.stream with test_time_aug=True: the augmentations of an utterance would have to be pushed in step")
+            raise NotImplementedError("CTCBeamSearchDecoder.stream with test_time_aug=True: the augmentations of an utterance would have to be pushed in step, at "
+                                      "twice the encoder cost per chunk; decode_augmented covers whole utterances")
         return CTCBeamStreamSession(self, batch_size, max_frames)
 
     def _decode_ids(self, logits, logits_len):

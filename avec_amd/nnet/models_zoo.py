@@ -39,11 +39,22 @@ class VisualEfficientConformerCE(Model):
         super().compile(losses=losses, loss_weights=loss_weights, optimizer=optimizer, metrics=metrics, decoders=decoders)
 
 
+_DEFAULT = object()                                        # "argument omitted": an explicit None must stay None (nnet/models_zoo.py:128-147)
+
+
+def is_native_flip(augment):
+    """True for the augment the HIP clip-batch kernel covers: a `RandomHorizontalFlip` (torchvision's or avec_amd.compat.torchvision_fallback's, told by the class
+    name) that always flips (p >= 1.0)"""
+    p = getattr(augment, "p", None)
+    return type(augment).__name__ == "RandomHorizontalFlip" and isinstance(p, (int, float)) and p >= 1.0
+
+
 class _InterCTCModel(Model):
     default_loss_weights = None
 
-    def compile(self, losses=None, loss_weights="default", optimizer="Adam", metrics=None, decoders=None):
-        if losses is None:
+    def compile(self, losses=_DEFAULT, loss_weights="default", optimizer="Adam", metrics=None, decoders=None):
+        """losses omitted: CTCLoss() as the reference's default argument; an explicit None: no losses (compiled_losses == [], the test-time-augmentation configs)"""
+        if losses is _DEFAULT:
             losses = L.CTCLoss()
         if loss_weights == "default":
             lw = self.default_loss_weights
@@ -70,17 +81,43 @@ class AudioEfficientConformerInterCTC(_InterCTCModel):
 
 
 class VisualEfficientConformerInterCTC(_InterCTCModel):
-    """nnet/models_zoo.py:99-147 (test-time augmentation is an evaluation nicety outside the hot path)"""
+    """nnet/models_zoo.py:99-147.  test_augments (None, a callable or a list of callables on clips (B, 1, T, H, W)): test-time augmentation.  In eval mode with A
+    augments "outputs" is [logits [B, 1 + A, T', V], lengths [B, 1 + A]] (index 0: the clips as given, then the augments in list order) and the InterCTC entries
+    are those of the clips as given, as in the reference (nnet/models_zoo.py:113-122).  The reference runs the encoder 1 + A times; here it runs ONCE over
+    (1 + A) * B clips laid out utterance-major (row b * (1 + A) + k), so the logits are a plain view and CTCBeamSearchDecoder's flatten(0, 1) costs no copy.
+    That is the same function: eval-mode BatchNorm uses its running statistics and every other layer works per utterance."""
     default_loss_weights = [0.5 / 3, 0.5 / 3, 0.5 / 3, 0.5]
 
     def __init__(self, vocab_size=256, interctc_blocks=[3, 6, 9], test_augments=None):
         super().__init__(name="Visual Efficient Conformer Inter CTC")
-        assert test_augments is None
         self.encoder = networks.VisualEfficientConformerEncoder(vocab_size=vocab_size, interctc_blocks=interctc_blocks)
+        # (a plain list, as in the reference: an augment that is an nn.Module is not registered, so the state_dict keys do not change)
+        self.test_augments = test_augments if isinstance(test_augments, list) else [test_augments] if test_augments is not None else test_augments
+
+    def tta_clips(self, video, native=None):
+        """video (B, T, H, W, 1) -> the (B * (1 + A), T, H, W, 1) clip batch of one augmented pass.  native (default: when every augment is the always-on horizontal
+        flip): one HIP launch (ops.video_tta_batch); otherwise every augment is applied as the reference does, to video.permute(0, 4, 1, 2, 3), and the results are
+        interleaved with PyTorch ops."""
+        augs = self.test_augments
+        n = 1 + len(augs)
+        if native is None:
+            native = n <= 32 and all(is_native_flip(a) for a in augs)
+        if native:
+            return ops.video_tta_batch(video, n, (1 << n) - 2)
+        clips = video.permute(0, 4, 1, 2, 3)
+        both = torch.stack([clips] + [a(clips) for a in augs], dim=1)          # (B, n, 1, T, H, W)
+        return both.flatten(0, 1).permute(0, 2, 3, 4, 1).contiguous()
 
     def forward(self, inputs):
         video, video_lengths = inputs
-        x, lengths, inter = self.encoder(video.permute(0, 4, 1, 2, 3), video_lengths)
+        assert not (self.training and self.test_augments is not None), "Training requires setting test_time_aug to False / test_augments to None"
+        if self.test_augments is None:
+            x, lengths, inter = self.encoder(video.permute(0, 4, 1, 2, 3), video_lengths)
+        else:
+            B, n = video.shape[0], 1 + len(self.test_augments)
+            x, lengths, inter = self.encoder(self.tta_clips(video).permute(0, 4, 1, 2, 3), video_lengths.repeat_interleave(n))
+            x, lengths = x.unflatten(0, (B, n)), lengths.unflatten(0, (B, n))          # views
+            inter = {k: [lg.unflatten(0, (B, n))[:, 0], ln.unflatten(0, (B, n))[:, 0]] for k, (lg, ln) in inter.items()}
         out = {"outputs": [x, lengths]}
         out.update(inter)
         return out

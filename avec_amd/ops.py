@@ -2000,6 +2000,53 @@ def ctc_align(logits, logits_len, targets, target_len, blank=0, tier=0):
     return path, spans, score, token_logp
 
 
+def _aligned16(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def video_tta_batch(video, n, flip_mask):
+    """The clip batch of test-time augmentation for ONE encoder pass: video (B, T, H, W, 1) fp32 -> (B * n, T, H, W, 1), clip b * n + k = video[b] mirrored along W when
+    bit k of flip_mask is set, video[b] otherwise (avec_video_tta_batch: every input row read once, written n times).  Inference only."""
+    _inference_only("ops.video_tta_batch", video)
+    rt.require_gpu(video)
+    if video.dim() != 5 or video.shape[-1] != 1:
+        raise ValueError("ops.video_tta_batch: video of shape %s, expected (B, T, H, W, 1)" % (tuple(video.shape),))
+    n, flip_mask = int(n), int(flip_mask)
+    if not 1 <= n <= 32 or flip_mask < 0 or flip_mask >> n:
+        raise ValueError("ops.video_tta_batch: n = %d (1..32), flip_mask = %s (bits below n only)" % (n, bin(flip_mask)))
+    B, T, H, W, _ = video.shape
+    x = _aligned16(_f32c(video))
+    y = torch.empty(B * n, T, H, W, 1, dtype=torch.float32, device=x.device)
+    lib.video_tta_batch(x.data_ptr(), y.data_ptr(), B, T * H, W, n, flip_mask, rt.stream())
+    return y
+
+
+def ctc_tta_pick(tokens, out_len, score, n, best_slot=None):
+    """Per utterance the winner among its n augmentations, on the device (avec_ctc_tta_pick; one launch, no host synchronisation).  tokens [S, W, T] int32,
+    out_len [S, W] int32, score [S, W] of ops.ctc_beam_search on S = B * n rows (row b * n + k = augmentation k of utterance b).  best_slot [B] int64 (optional):
+    the winning slot in [0, n * W), ops.lm_rescore's `best`; without it the augmentation whose best beam scores highest (first maximum) and beam 0.
+    Returns best_aug [B], best_beam [B], ids [B, T] (zero past ids_len), ids_len [B] (all int64) and best_score [B]."""
+    rt.require_gpu(tokens)
+    S, W, T = tokens.shape
+    n = int(n)
+    if n < 1 or S % n:
+        raise ValueError("ops.ctc_tta_pick: %d rows are not a whole number of utterances of %d augmentations" % (S, n))
+    B, dev = S // n, tokens.device
+    if tuple(out_len.shape) != (S, W) or tuple(score.shape) != (S, W):
+        raise ValueError("ops.ctc_tta_pick: tokens %s, out_len %s, score %s" % (tuple(tokens.shape), tuple(out_len.shape), tuple(score.shape)))
+    tk, ol, sc = tokens.to(torch.int32).contiguous(), out_len.to(device=dev, dtype=torch.int32).contiguous(), _f32c(score.to(dev))
+    if best_slot is not None:
+        best_slot = best_slot.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        if best_slot.numel() != B:
+            raise ValueError("ops.ctc_tta_pick: best_slot of %d entries for %d utterances" % (best_slot.numel(), B))
+    best_aug, best_beam, ids_len = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(3))
+    ids = torch.empty(B, T, dtype=torch.int64, device=dev)
+    best_score = torch.empty(B, dtype=torch.float32, device=dev)
+    lib.ctc_tta_pick(tk.data_ptr(), ol.data_ptr(), sc.data_ptr(), _p(best_slot), B, n, W, T, best_aug.data_ptr(), best_beam.data_ptr(), ids.data_ptr(),
+                     ids_len.data_ptr(), best_score.data_ptr(), rt.stream())
+    return best_aug, best_beam, ids, ids_len, best_score
+
+
 def ngram_rows(lm, contexts):
     """ln P(. | ctx) [n, V] on the device for a list of token histories (oldest first, -1 = <s>): avec_ngram_rows"""
     dev = torch.device("cuda", torch.cuda.current_device())

@@ -398,6 +398,12 @@ int avec_wgrad3x3_c64_grouped(const avec_wgrad3x3_item_t* items, int n, hipStrea
  * that the device only adds the three terms, subtracts mean and divides by stdv: bit-identical pixels);  mean_frame != 0: mask k is filled with the mean of the clip as left by masks 0..k-1, else with 0. */
 int avec_video_input(const unsigned char* clips, const long long* clip_off, const int* geom, const int* masks, int max_masks, int channels, const float* lut, float mean, float stdv,
                      int mean_frame, float* out, float* frame_ws, int B, int Tout, int OH, int OW, hipStream_t stream);
+/* ---- test-time augmentation (avec_amd/csrc/tta.hip) ------------------------------------------ */
+/* The clip batch of VisualEfficientConformerInterCTC.forward with test_augments (nnet/models_zoo.py:113-122: the clips, then test_augment(clips) for every augment,
+ * each through its own encoder pass) for augments that are the horizontal flip, laid out for ONE encoder pass: x fp32 [B][rows][W] (rows = frames * height) ->
+ * y fp32 [B * n][rows][W], y[b * n + k] = x[b] mirrored along W when bit k of flip_mask is set, x[b] otherwise (utterance-major: the logits of the batch are a view
+ * [B][n][T'][V]).  Every input row is read once and written n times; 16-byte accesses when W % 4 == 0.  x and y 16-byte aligned, n <= 32, no flip_mask bit at or above n. */
+int avec_video_tta_batch(const float* x, float* y, int B, long long rows, int W, int n, unsigned flip_mask, hipStream_t stream);
 
 /* ---- loss / optimizer (avec_amd/csrc/loss_optim.hip) ---------------------------------------- */
 /* CTCLoss.forward (nnet/losses.py:311-334): per-utterance -log p, batch mean, and d/dlogits (unscaled) */
@@ -515,6 +521,15 @@ int avec_lm_segment_sum(const float* nll, const long long* lens, long long S, in
  * beam_score = -inf),  best[b] (int64) = the first maximum of total[b][:]. */
 int avec_lm_rescore_select(const float* neural, const long long* lens, const float* beam_score, float alpha, float beta, int B, int K, float* total, long long* best,
                            hipStream_t stream);
+/* The winner among the augmentations of an utterance (CTCBeamSearchDecoder with test_time_aug, nnet/decoders.py:177-180 with the argmin of :242 / :252 over the
+ * n * W slots; avec_amd/csrc/tta.hip), kept on the device together with WHICH augmentation won.  tokens [S][W][T] int32, out_len [S][W] int32, score [S][W] as
+ * avec_ctc_beam_search writes them for S = B * n rows (row b * n + k = augmentation k of utterance b).  best_slot (optional, int64 [B]): the winning slot in
+ * [0, n * W) (avec_lm_rescore_select's `best`), clamped into that range before use.  NULL: the augmentation whose slot-0 score is highest, scanned from augmentation
+ * 0 with a strict >, so ties go to the lower index, and beam 0.  Outputs (int64): best_aug [B], best_beam [B], ids [B][T] = the winner's tokens (zero at and past
+ * ids_len), ids_len [B] = its out_len clamped to [0, T] (0 when its score is -inf), and best_score [B] fp32 = its score.  An utterance whose slots are all empty
+ * gives augmentation 0, beam 0, length 0, score -inf.  One launch, one workgroup per utterance. */
+int avec_ctc_tta_pick(const int* tokens, const int* out_len, const float* score, const long long* best_slot, int B, int n, int W, int T, long long* best_aug,
+                      long long* best_beam, long long* ids, long long* ids_len, float* best_score, hipStream_t stream);
 /* optimizers.Adam.step (nnet/optimizers.py:71-75) over flat arenas; state_dev = {step, lr} */
 int avec_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
                    float weight_decay, float grad_scale, int zero_grad, long long n, hipStream_t stream);
