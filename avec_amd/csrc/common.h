@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <tuple>
 
 #define AVEC_F32 0
 #define AVEC_BF16 1
@@ -132,5 +133,16 @@ void avec_note_kernel(const char* fmt, ...);      // api.hip: remembers which ke
 __attribute__((visibility("hidden"))) int avec_lds_optin(const void* kernel, size_t bytes);      // (hidden: the library exports what it exported before)
 __attribute__((visibility("hidden"))) int avec_lds_optin_quiet(const void* kernel, size_t bytes);
 template <typename K> static inline int avec_lds_optin(K kernel, size_t bytes) { return avec_lds_optin((const void*)kernel, bytes); }      // kernels by name
+static inline bool avec_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// One kernel launch, the instance named once: note its name (printf-style, what avec_last_kernel reports), opt in to `lds` bytes of dynamic LDS (a refusal comes back
+// as its error code), launch.  The kernel's arguments travel as one braced list:
+//   return avec_launch(my_kernel<BM, BN>, grid, dim3(256), lds, stream, {g}, "my_kernel<%d,%d>", BM, BN);
+template <typename... KA, typename... NA>
+static inline int avec_launch(void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const std::tuple<KA...>& args, const char* name_fmt, NA... name_args) {
+  avec_note_kernel(name_fmt, name_args...);
+  if (int r = avec_lds_optin((const void*)kernel, lds)) return r;
+  std::apply([&](const KA&... a) { hipLaunchKernelGGL(kernel, grid, block, lds, stream, a...); }, args);
+  return 0;
+}
 #define AVEC_CHECK_ARG(cond, ...) do { if (!(cond)) { avec_set_error(__VA_ARGS__); return -1; } } while (0)
 #define AVEC_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { avec_set_error("%s:%d launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return (int)e_; } } while (0)

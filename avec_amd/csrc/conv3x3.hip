@@ -1078,9 +1078,8 @@ static int conv3x3_c64_impl(const void* x, const void* w, void* y, const void* r
   // byte-for-byte what it was when the opt-in named all three up front.  Nothing depends on the order; reorder freely when the kernels change anyway.
   const void* kern = !stats && !res ? (const void*)conv3x3_c64_kernel<false, false> : stats ? (const void*)conv3x3_c64_kernel<true, false> : (const void*)conv3x3_c64_res_kernel;
   if (int r = avec_lds_optin(kern, lds)) return r;
-  static const int wgs_env = 256;
   C3Args a; a.x = (const bf16*)x; a.w = (const bf16*)w; a.y = (bf16*)y; a.res = (const bf16*)res; a.stats = stats; a.N = (int)images; a.H = H; a.W = W; a.flip = flip; a.rmask = rmask;
-  const int grid = (int)(images < wgs_env ? images : wgs_env);
+  const int grid = (int)(images < 256 ? images : 256);
   avec_note_kernel(stats ? "conv3x3_c64_kernel<true,false>" : res ? "conv3x3_c64_res_kernel" : "conv3x3_c64_kernel<false,false>");
   if (stats) hipLaunchKernelGGL((conv3x3_c64_kernel<true, false>), dim3(grid), dim3(512), lds, st, a);
   else if (res) hipLaunchKernelGGL(conv3x3_c64_res_kernel, dim3(grid), dim3(512), lds, st, a);

@@ -281,7 +281,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2_bwd_kernel(GemmArgs g) {
   else conv_s2_body<BM, BN, MODE_CONV_BWD, 0, EVEN>(g, smem, bx, by);
 }
 
-bool s2_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+template <int BN, bool EVEN>
+int launch_s2(const GemmArgs& g, int mode, long long P, hipStream_t st) {      // P: coarse pixels
+  constexpr int BM = 256;
+  const size_t lds = (size_t)3 * BN * 64 + (size_t)3 * (BM + S2_HALO) * 64;
+  const unsigned gx = (unsigned)((P + BM - 1) / BM), gy = (unsigned)((g.N + BN - 1) / BN);
+  if (mode == MODE_CONV_FWD) return avec_launch(conv3x3_s2_fwd_kernel<BM, BN, EVEN>, dim3(gx, gy), dim3(256), lds, st, {g}, "conv3x3_s2_fwd_kernel<%d,%d,%d>", BM, BN, (int)EVEN);
+  return avec_launch(conv3x3_s2_bwd_kernel<BM, BN, EVEN>, dim3(gx, gy, 4), dim3(256), lds, st, {g}, "conv3x3_s2_bwd_kernel<%d,%d,%d>", BM, BN, (int)EVEN);      // one grid slice per parity class
+}
 
 }  // namespace
 
@@ -290,10 +297,10 @@ int avec_launch_conv_s2(const GemmArgs& g_in, int mode, hipStream_t st) {
   static const bool off = getenv("AVEC_NO_CONV_S2") != nullptr;
   const RowSrc& a = g_in.a; const Epi& e = g_in.e;
   if (off || mode == MODE_PLAIN || a.KH != 3 || a.KW != 3 || a.stride != 2 || a.pad != 1 || a.OH != (a.H + 1) / 2 || a.OW != (a.W + 1) / 2 || a.OW > 15 || a.OW < 2 || a.C % 32 != 0) return 1;
-  if (!s2_aligned16(a.ptr) || !s2_aligned16(g_in.W) || g_in.ldw % 8 != 0 || (long long)g_in.N * g_in.ldw * 2 >= (1ll << 32) || g_in.N < 64 || g_in.N % 8 != 0) return 1;
+  if (!avec_aligned16(a.ptr) || !avec_aligned16(g_in.W) || g_in.ldw % 8 != 0 || (long long)g_in.N * g_in.ldw * 2 >= (1ll << 32) || g_in.N < 64 || g_in.N % 8 != 0) return 1;
   // register-direct epilogue only: bf16 output, nothing but alpha / bf16 residual / BatchNorm statistics fused
-  if (e.out_f32 || e.out_pre || e.bias || e.act != 0 || e.drop_p > 0.f || e.dact || e.colsum || e.bnb_y || e.ldo % 8 != 0 || !s2_aligned16(e.out)) return 1;
-  if (e.res && (!e.res_act || e.ldres % 8 != 0 || !s2_aligned16(e.res))) return 1;
+  if (e.out_f32 || e.out_pre || e.bias || e.act != 0 || e.drop_p > 0.f || e.dact || e.colsum || e.bnb_y || e.ldo % 8 != 0 || !avec_aligned16(e.out)) return 1;
+  if (e.res && (!e.res_act || e.ldres % 8 != 0 || !avec_aligned16(e.res))) return 1;
   const long long fine = (long long)a.H * a.W, coarse = (long long)a.OH * a.OW;
   long long imgs, P;
   if (mode == MODE_CONV_FWD) { if (g_in.M % coarse) return 1; imgs = g_in.M / coarse; if (e.res) return 1; }
@@ -302,17 +309,6 @@ int avec_launch_conv_s2(const GemmArgs& g_in, int mode, hipStream_t st) {
   if (imgs * fine * a.C * 2 >= (1ll << 32) || P * a.C * 2 >= (1ll << 32) || P < 1 || P + 1024 >= (1ll << 31) || imgs * fine >= (1ll << 31)) return 1;
   GemmArgs g = g_in; g.perm2 = 0;
   const bool even = !((a.H | a.W) & 1);
-#define S2(BM, BN, EV) do { \
-    const size_t lds = (size_t)3 * BN * 64 + (size_t)3 * (BM + S2_HALO) * 64; \
-    if (mode == MODE_CONV_FWD) { dim3 grid((unsigned)((P + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN)); \
-      avec_note_kernel("conv3x3_s2_fwd_kernel<%d,%d,%d>", BM, BN, (int)EV); if (int r = avec_lds_optin(conv3x3_s2_fwd_kernel<BM, BN, EV>, lds)) return r; \
-      hipLaunchKernelGGL((conv3x3_s2_fwd_kernel<BM, BN, EV>), grid, dim3(256), lds, st, g); } \
-    else { dim3 grid((unsigned)((P + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN), 4); \
-      avec_note_kernel("conv3x3_s2_bwd_kernel<%d,%d,%d>", BM, BN, (int)EV); if (int r = avec_lds_optin(conv3x3_s2_bwd_kernel<BM, BN, EV>, lds)) return r; \
-      hipLaunchKernelGGL((conv3x3_s2_bwd_kernel<BM, BN, EV>), grid, dim3(256), lds, st, g); } \
-    return 0; } while (0)
-  if (g.N >= 128) { if (even) S2(256, 128, true); else S2(256, 128, false); }
-  if (even) S2(256, 64, true); else S2(256, 64, false);
-#undef S2
-  return 0;
+  if (g.N >= 128) return even ? launch_s2<128, true>(g, mode, P, st) : launch_s2<128, false>(g, mode, P, st);
+  return even ? launch_s2<64, true>(g, mode, P, st) : launch_s2<64, false>(g, mode, P, st);
 }

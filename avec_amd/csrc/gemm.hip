@@ -485,7 +485,7 @@ __device__ __forceinline__ void glds16_v64(const void* gsrc, unsigned lds_dst_un
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
 }
-// STAGES = 4: all of K <= 256 in flight, two workgroups per CU (64 KB).  STAGES = 2 (AVEC_NT_S2): 32 KB, four workgroups per CU -- for products whose 64 x 64 tiling
+// STAGES = 4: all of K <= 256 in flight, two workgroups per CU (64 KB).  STAGES = 2: 32 KB, four workgroups per CU -- for products whose 64 x 64 tiling
 // exceeds the 512 slots of the deep ring (3200 x 1024 x 256: 800 tiles) one round of workgroups that hide each other's DMA latency instead of two rounds.
 template <int BM, int BN, int STAGES = 4, bool TR = false>      // TR: transposed product + register-direct epilogue (plain_epilogue_tr)
 __global__ __launch_bounds__(256, 2) void gemm_nt_plain_kernel(const void* pa_ptr, const void* pa_w, long long pa_lda, long long pa_ldw, long long pa_M, int pa_N, int pa_K, int pa_ktail, GemmArgs g_unused) {
@@ -1308,6 +1308,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_tr_grouped_kernel(TnGroup grp)
 
 // ------------------------------------------------------------------------------------------------
 // host launchers (C ABI)
+// Every kernel family has one small launch_* template: it sizes the dynamic LDS and goes through avec_launch (common.h), so an instance and the name that
+// avec_last_kernel reports for it come from the same template arguments.  The functions below them only choose.
 // ------------------------------------------------------------------------------------------------
 #include <stdint.h>
 #include <stdlib.h>
@@ -1317,15 +1319,26 @@ static RowSrc make_src(const void* ptr, const avec_rows_t* d) {
   s.H = d->H; s.W = d->W; s.C = d->C; s.KH = d->KH; s.KW = d->KW; s.stride = d->stride; s.pad = d->pad; s.OH = d->OH; s.OW = d->OW;
   return s;
 }
+// the epilogue fields that every NT entry point takes; the BatchNorm-backward fusion, res_cls0 and res_mask stay zero (avec_gemm_nt adds them)
+static Epi make_epi(const avec_epilogue_t* ep) {
+  Epi e; memset(&e, 0, sizeof(e));
+  e.out = ep->out; e.ldo = ep->ldo; e.out_f32 = ep->out_f32; e.out_pre = ep->out_pre; e.ldpre = ep->ldpre; e.bias = ep->bias;
+  e.act = ep->act; e.drop_p = ep->drop_p; e.rng = (const unsigned long long*)ep->rng; e.stream = ep->rng_stream;
+  e.res = ep->res; e.ldres = ep->ldres; e.alpha = ep->alpha; e.res_act = ep->res_act; e.dact_z = ep->dact_z; e.ldz = ep->ldz; e.dact = ep->dact;
+  e.colsum = ep->colsum; e.stats = ep->stats;
+  return e;
+}
+template <typename T> static constexpr const char* elt_name() { return sizeof(T) == 2 ? "bf16" : "float"; }
+static constexpr size_t epi_lds(int BN) { return (size_t)64 * (BN + 4) * 4 + 10 * BN * 4; }      // LDS of the staged epilogues
+static constexpr size_t max_lds(size_t a, size_t b) { return a > b ? a : b; }
 
-static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // register-direct epilogue (conv_epilogue_tr, transposed product): bf16 output and residual in whole 16-byte pieces, nothing but alpha / residual / BatchNorm statistics
 // to fuse.  AVEC_NO_EPI_TR=1: the staged epilogue everywhere (A/B runs).
 static bool epi_tr_ok(const GemmArgs& g) {
   static const bool off = getenv("AVEC_NO_EPI_TR") != nullptr;
   const Epi& e = g.e;
   return !off && !e.out_f32 && !e.out_pre && !e.bias && e.act == 0 && !(e.drop_p > 0.f) && !e.dact && !e.colsum && !e.bnb_y && g.N % 8 == 0 &&
-         e.ldo % 8 == 0 && aligned16(e.out) && (!e.res || (e.res_act && e.ldres % 8 == 0 && aligned16(e.res)));
+         e.ldo % 8 == 0 && avec_aligned16(e.out) && (!e.res || (e.res_act && e.ldres % 8 == 0 && avec_aligned16(e.res)));
 }
 
 // register-direct epilogue of the plain 64 x 64 product: whole 8-column pieces, 16-byte aligned rows of every operand, no column reduction.  AVEC_NO_PLAIN_TR=1: off
@@ -1333,116 +1346,113 @@ static bool plain_tr_ok(const GemmArgs& g) {
   static const bool off = getenv("AVEC_NO_PLAIN_TR") != nullptr || getenv("AVEC_NO_EPI_TR") != nullptr;
   const Epi& e = g.e;
   const long long ob = e.out_f32 ? 4 : 2;
-  return !off && !e.colsum && !e.stats && !e.bnb_y && g.N % 8 == 0 && g.N >= 8 && aligned16(e.out) && (e.ldo * ob) % 16 == 0 &&
-         (!e.out_pre || (aligned16(e.out_pre) && e.ldpre % 8 == 0)) && (!e.bias || aligned16(e.bias)) && (!e.dact || (aligned16(e.dact_z) && e.ldz % 8 == 0)) &&
-         (!e.res || (aligned16(e.res) && (e.ldres * (e.res_act ? 2 : 4)) % 16 == 0));
+  return !off && !e.colsum && !e.stats && !e.bnb_y && g.N % 8 == 0 && g.N >= 8 && avec_aligned16(e.out) && (e.ldo * ob) % 16 == 0 &&
+         (!e.out_pre || (avec_aligned16(e.out_pre) && e.ldpre % 8 == 0)) && (!e.bias || avec_aligned16(e.bias)) && (!e.dact || (avec_aligned16(e.dact_z) && e.ldz % 8 == 0)) &&
+         (!e.res || (avec_aligned16(e.res) && (e.ldres * (e.res_act ? 2 : 4)) % 16 == 0));
+}
+
+template <typename T, int BM, int BN, int MODE, bool F32SRC, bool A16>
+static int launch_nt_generic(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  return avec_launch(gemm_nt_kernel<T, BM, BN, MODE, F32SRC, A16>, grid, dim3(256), (size_t)2 * (BM + BN) * LDS_ROW, st, {g},
+                     "gemm_nt_kernel<%s,%d,%d,%d,%d,%d>", elt_name<T>(), BM, BN, MODE, (int)F32SRC, (int)A16);
+}
+template <typename T, int BM, int BN, int MODE, int STG, bool FC, int RB>
+static int launch_nt_glds(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  return avec_launch(gemm_nt_glds_kernel<T, BM, BN, MODE, STG, FC, RB>, grid, dim3(256), max_lds((size_t)STG * (BM + BN) * RB, epi_lds(BN)), st, {g},
+                     "gemm_nt_glds_kernel<%s,%d,%d,%d,%d,%d,%d>", elt_name<T>(), BM, BN, MODE, STG, (int)FC, RB);
+}
+template <int BM, int BN, int STG, bool TR>
+static int launch_nt_plain(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  const size_t ring = (size_t)STG * (BM + BN) * 128;
+  return avec_launch(gemm_nt_plain_kernel<BM, BN, STG, TR>, grid, dim3(256), TR ? ring : max_lds(ring, epi_lds(BN)), st,
+                     {g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g}, "gemm_nt_plain_kernel<%d,%d,%d,%s>", BM, BN, STG, TR ? "tr" : "false");
+}
+template <int BN, int MODE, bool TR>
+static int launch_nt_conv_lean(const GemmArgs& g, dim3 grid, hipStream_t st) {
+  const size_t ring = (size_t)3 * (128 + BN) * 64;
+  return avec_launch(gemm_nt_conv_lean_kernel<BN, MODE, TR>, grid, dim3(256), TR ? ring : max_lds(ring, epi_lds(BN)), st, {g},
+                     TR ? "gemm_nt_conv_lean_kernel<%d,%d,tr>" : "gemm_nt_conv_lean_kernel<%d,%d>", BN, MODE);
+}
+template <int BM, int BN, int MODE, bool TR>
+static int launch_shift(const GemmArgs& g, hipStream_t st) {
+  const size_t ring = (size_t)3 * BN * 64 + (size_t)2 * (BM + 64) * 64 + 512 + (BM / 64 - 1) * 2048;
+  const dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN));
+  return avec_launch(conv3x3_shift_kernel<BM, BN, MODE, TR>, grid, dim3(256), TR ? ring : max_lds(ring, epi_lds(BN)), st, {g},
+                     TR ? "conv3x3_shift_kernel<%d,%d,%d,tr>" : "conv3x3_shift_kernel<%d,%d,%d>", BM, BN, MODE);
+}
+
+// the kernels that take any product of one gather mode.  dma: the LDS-DMA kernel can take it; rb64: with 64-byte rows (bf16 only)
+template <typename T, int BM, int BN, int MODE>
+static int launch_nt_general(const GemmArgs& g, dim3 grid, bool dma, bool rb64, bool f32src, bool a16, hipStream_t st) {
+  constexpr int STG = (BM + BN) <= 128 ? 4 : 2;      // ring depth: deep for the small latency-bound tiles; the big tiles keep 3 workgroups per CU instead (measured)
+  constexpr int STG64 = (BM + BN) <= 128 ? 4 : 3;    // ... with 64-byte rows: 3 on the big tiles measured +2..6 % over 2, 4 is -5..10 %
+  if (dma) {
+    if constexpr (MODE != MODE_PLAIN) {
+      if (g.fast_conv) {
+        if constexpr (sizeof(T) == 2) { if (rb64) return launch_nt_glds<T, BM, BN, MODE, STG64, true, 64>(g, grid, st); }
+        return launch_nt_glds<T, BM, BN, MODE, STG, true, 128>(g, grid, st);
+      }
+    }
+    return launch_nt_glds<T, BM, BN, MODE, STG, false, 128>(g, grid, st);
+  }
+  // register-staged kernel.  After `dma` it sees an fp32 source (bf16 plain products only) or operands that are not 16-byte aligned; a bf16 convolution that carries
+  // the fp32-source flag is the one aligned product that arrives here
+  if constexpr (sizeof(T) == 2 && MODE == MODE_PLAIN) { if (f32src) return a16 ? launch_nt_generic<T, BM, BN, MODE, true, true>(g, grid, st) : launch_nt_generic<T, BM, BN, MODE, true, false>(g, grid, st); }
+  if constexpr (sizeof(T) == 2 && MODE != MODE_PLAIN) { if (a16) return launch_nt_generic<T, BM, BN, MODE, false, true>(g, grid, st); }
+  return launch_nt_generic<T, BM, BN, MODE, false, false>(g, grid, st);
 }
 
 template <typename T, int BM, int BN>
 static int launch_nt_mode(const GemmArgs& g_in, int mode, int src_f32, hipStream_t st) {
   GemmArgs g = g_in;
   dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN));
-  size_t lds = (size_t)2 * (BM + BN) * LDS_ROW;
   constexpr int VEC = Elt<T>::VEC;
   const bool f32src = src_f32 && sizeof(T) == 2;
   // every chunk address 16-byte aligned?  (then each chunk is one global_load_dwordx4 instead of two dwordx2)
-  const bool a16 = aligned16(g.a.ptr) && aligned16(g.W) && g.K % VEC == 0 && g.ldw % VEC == 0 &&
+  const bool a16 = avec_aligned16(g.a.ptr) && avec_aligned16(g.W) && g.K % VEC == 0 && g.ldw % VEC == 0 &&
                    (mode != MODE_PLAIN || (g.a.ld % (f32src ? 4 : VEC) == 0));
-  static const bool use_glds_ = true;
-  static const bool no_ktail = false;
   // plain bf16 products take the LDS-DMA kernel whatever their alignment (the DMA takes any source address); K = 8n + 4 with the in-LDS tail fix-up
-  const bool plain_any = sizeof(T) == 2 && mode == MODE_PLAIN && !f32src && use_glds_ && !no_ktail && (g.K % 8 == 0 || g.K % 8 == 4) && g.K >= 8 && g.ldw >= g.K && g.a.ld >= g.K &&
-                         g.a.step <= 1;
+  const bool plain_any = sizeof(T) == 2 && mode == MODE_PLAIN && !f32src && (g.K % 8 == 0 || g.K % 8 == 4) && g.K >= 8 && g.ldw >= g.K && g.a.ld >= g.K && g.a.step <= 1;
   g.ktail = (plain_any && g.K % 8 == 4) ? 4 : 0;
-  if (g.perm2 && mode == MODE_CONV_BWD && g.fast_conv && a16 && !f32src && use_glds_) {     // parity-class order: only the fast LDS-DMA kernel knows it
+  if (g.perm2 && mode == MODE_CONV_BWD && g.fast_conv && a16 && !f32src) {     // parity-class order: only the fast LDS-DMA kernel knows it
     g.pTs[0] = 0; for (int c = 0; c < 4; ++c) g.pTs[c + 1] = g.pTs[c] + (int)((perm2_count(g.a, c, g.pImgs) + BM - 1) / BM);
     grid.x = (unsigned)g.pTs[4];
   } else {
     if (g.e.res_cls0) { avec_set_error("gemm_nt: res_cls0: this launch cannot run in parity-class order (alignment)"); return -1; }
     g.perm2 = 0;
   }
-  constexpr int STG = (BM + BN) <= 128 ? 4 : 2;      // ring depth: deep for the small latency-bound tiles; the big tiles keep 3 workgroups per CU instead (measured)
-  static const bool rb_env_set = getenv("AVEC_NT_RB") != nullptr;
-  static const int rb_env = rb_env_set ? atoi(getenv("AVEC_NT_RB")) : 128;
-  const size_t epi_lds = (size_t)64 * (BN + 4) * 4 + 10 * BN * 4;
-#define G2(MODE, FC, RB_) do { const size_t l2 = (size_t)STG * (BM + BN) * RB_ > epi_lds ? (size_t)STG * (BM + BN) * RB_ : epi_lds; \
-    avec_note_kernel("gemm_nt_glds_kernel<%s,%d,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, STG, (int)FC, RB_); if (int r = avec_lds_optin(gemm_nt_glds_kernel<T, BM, BN, MODE, STG, FC, RB_>, l2)) return r; hipLaunchKernelGGL((gemm_nt_glds_kernel<T, BM, BN, MODE, STG, FC, RB_>), grid, dim3(256), l2, st, g); return 0; } while (0)
-  // 64-byte rows (K-step 32): half the ring, 4 resident workgroups per CU instead of 2 -- measured +4..18 % on the implicit-GEMM layers with
-  // thousands of tiles, -16 % on the deep-K / few-tile ones (512-channel 3x3 stage): chosen by tile count.  AVEC_NT_RB=64/128 forces it.
-  const long long ntiles = (long long)grid.x * grid.y;
-  const bool rb64 = sizeof(T) == 2 && (rb_env_set ? rb_env == 64 : ntiles >= 1536);
-  static const int stg_env = 3;     // ring depth of the fast implicit-GEMM kernels with 64-byte rows: 3 measured +2..6 % over 2, 4 is -5..10 %
-#define G3(MODE, S_) do { const size_t l2 = (size_t)S_ * (BM + BN) * 64 > epi_lds ? (size_t)S_ * (BM + BN) * 64 : epi_lds; \
-    avec_note_kernel("gemm_nt_glds_kernel<%s,%d,%d,%d,%d,1,64>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, S_); if (int r = avec_lds_optin(gemm_nt_glds_kernel<T, BM, BN, MODE, S_, true, 64>, l2)) return r; hipLaunchKernelGGL((gemm_nt_glds_kernel<T, BM, BN, MODE, S_, true, 64>), grid, dim3(256), l2, st, g); return 0; } while (0)
-#define G(MODE) do { if (MODE != MODE_PLAIN && g.fast_conv) { if (rb64 && stg_env == 3 && (BM + BN) > 128) G3(MODE, 3); if (rb64 && stg_env == 4 && (BM + BN) > 128) G3(MODE, 4); \
-    if (rb64) G2(MODE, true, 64); else G2(MODE, true, 128); } G2(MODE, false, 128); } while (0)
-  static const bool use_glds = true;
-  static const bool no_lean = false;
   if constexpr (sizeof(T) == 2 && BN == 64 && BM == 64) {       // (128 x 64 with the 4-stage ring leaves one workgroup per CU: slower than the general kernel's 2-stage ring)
-    // the lean plain kernel: whole 16-byte K-chunks, 32-bit byte offsets into both operands
+    // the lean plain kernel: whole 16-byte K-chunks (or the K = 8n + 4 tail), 32-bit byte offsets into both operands
     const long long arows = g.a.step > 1 ? (g.M / (g.a.rows_out > 0 ? g.a.rows_out : 1) + 1) * (long long)g.a.rows_in : g.M;
-    static const bool no_lean_tail = false;
-    if (mode == MODE_PLAIN && !f32src && use_glds && !no_lean && g.a.step <= 1 && (g.K % 8 == 0 || (g.ktail && !no_lean_tail)) && g.K >= 8 && g.ldw >= g.K && g.a.ld >= g.K &&
+    if (mode == MODE_PLAIN && !f32src && g.a.step <= 1 && (g.K % 8 == 0 || g.ktail) && g.K >= 8 && g.ldw >= g.K && g.a.ld >= g.K &&
         arows * g.a.ld * 2 < (1ll << 32) && (long long)g.N * g.ldw * 2 < (1ll << 32)) {
       // two-stage ring for products with more than 512 tiles (the slots of the deep ring) and at most 6 K tiles: 3200 x 1024 x 256 + Swish 10.4 -> 8.2 us,
-      // 3200 x 768 x 256 8.9 -> 6.4 us, 1600 x 1440 x 360 11.7 -> 9.4 us; step 19.31 -> 19.18 ms (tools/gpu/r4_s2.sh; with 256: no further gain).  AVEC_NT_S2=0: off
-      static const int s2_min = 512;
+      // 3200 x 768 x 256 8.9 -> 6.4 us, 1600 x 1440 x 360 11.7 -> 9.4 us; step 19.31 -> 19.18 ms (tools/gpu/r4_s2.sh; with 256: no further gain)
       const bool tr = plain_tr_ok(g);
-      if (s2_min > 0 && (long long)grid.x * grid.y > s2_min && !g.ktail && g.K <= 384) {
-        const size_t l2s = (size_t)2 * (BM + BN) * 128 > epi_lds ? (size_t)2 * (BM + BN) * 128 : epi_lds;
-        if (tr) {
-          const size_t lt = (size_t)2 * (BM + BN) * 128;
-          avec_note_kernel("gemm_nt_plain_kernel<%d,%d,2,tr>", BM, BN);
-          if (int r = avec_lds_optin(gemm_nt_plain_kernel<BM, BN, 2, true>, lt)) return r;
-          hipLaunchKernelGGL((gemm_nt_plain_kernel<BM, BN, 2, true>), grid, dim3(256), lt, st, g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g); return 0;
-        }
-        avec_note_kernel("gemm_nt_plain_kernel<%d,%d,2,false>", BM, BN);
-        if (int r = avec_lds_optin(gemm_nt_plain_kernel<BM, BN, 2>, l2s)) return r;
-        hipLaunchKernelGGL((gemm_nt_plain_kernel<BM, BN, 2>), grid, dim3(256), l2s, st, g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g); return 0;
-      }
-      const size_t l2 = (size_t)4 * (BM + BN) * 128 > epi_lds ? (size_t)4 * (BM + BN) * 128 : epi_lds;
-      if (tr) {
-        const size_t lt = (size_t)4 * (BM + BN) * 128;
-        avec_note_kernel("gemm_nt_plain_kernel<%d,%d,4,tr>", BM, BN);
-        if (int r = avec_lds_optin(gemm_nt_plain_kernel<BM, BN, 4, true>, lt)) return r;
-        hipLaunchKernelGGL((gemm_nt_plain_kernel<BM, BN, 4, true>), grid, dim3(256), lt, st, g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g); return 0;
-      }
-      avec_note_kernel("gemm_nt_plain_kernel<%d,%d,4,false>", BM, BN);
-      if (int r = avec_lds_optin(gemm_nt_plain_kernel<BM, BN>, l2)) return r;
-      hipLaunchKernelGGL((gemm_nt_plain_kernel<BM, BN>), grid, dim3(256), l2, st, g.a.ptr, g.W, g.a.ld, g.ldw, g.M, g.N, g.K, g.ktail, g); return 0;
+      if ((long long)grid.x * grid.y > 512 && !g.ktail && g.K <= 384) return tr ? launch_nt_plain<BM, BN, 2, true>(g, grid, st) : launch_nt_plain<BM, BN, 2, false>(g, grid, st);
+      return tr ? launch_nt_plain<BM, BN, 4, true>(g, grid, st) : launch_nt_plain<BM, BN, 4, false>(g, grid, st);
     }
   }
   if constexpr (sizeof(T) == 2 && BM == 128 && (BN == 128 || BN == 64)) {
     static const bool no_clean = getenv("AVEC_NO_LEAN_CONV") != nullptr;
-    if (mode != MODE_PLAIN && g.fast_conv && a16 && !f32src && use_glds && !no_clean && g.a.C % 32 == 0 && (long long)g.N * g.ldw * 2 < (1ll << 32)) {
-      const size_t l2 = (size_t)3 * (BM + BN) * 64 > epi_lds ? (size_t)3 * (BM + BN) * 64 : epi_lds;
-      if (epi_tr_ok(g)) {
-        const size_t lt = (size_t)3 * (BM + BN) * 64;
-        avec_note_kernel("gemm_nt_conv_lean_kernel<%d,%d,tr>", BN, mode);
-        if (mode == MODE_CONV_FWD) { if (int r = avec_lds_optin(gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD, true>, lt)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD, true>), grid, dim3(256), lt, st, g); }
-        else { if (int r = avec_lds_optin(gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD, true>, lt)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD, true>), grid, dim3(256), lt, st, g); }
-        return 0;
-      }
+    if (mode != MODE_PLAIN && g.fast_conv && a16 && !f32src && !no_clean && g.a.C % 32 == 0 && (long long)g.N * g.ldw * 2 < (1ll << 32)) {
+      const bool fwd = mode == MODE_CONV_FWD;
+      if (epi_tr_ok(g)) return fwd ? launch_nt_conv_lean<BN, MODE_CONV_FWD, true>(g, grid, st) : launch_nt_conv_lean<BN, MODE_CONV_BWD, true>(g, grid, st);
       if (g.e.res_mask) { avec_set_error("gemm_nt: res_mask needs the register-direct epilogue"); return -1; }
-      avec_note_kernel("gemm_nt_conv_lean_kernel<%d,%d>", BN, mode);
-      if (mode == MODE_CONV_FWD) { if (int r = avec_lds_optin(gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD>, l2)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_FWD>), grid, dim3(256), l2, st, g); }
-      else { if (int r = avec_lds_optin(gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD>, l2)) return r; hipLaunchKernelGGL((gemm_nt_conv_lean_kernel<BN, MODE_CONV_BWD>), grid, dim3(256), l2, st, g); }
-      return 0;
+      return fwd ? launch_nt_conv_lean<BN, MODE_CONV_FWD, false>(g, grid, st) : launch_nt_conv_lean<BN, MODE_CONV_BWD, false>(g, grid, st);
     }
   }
   if (g.e.res_mask) { avec_set_error("gemm_nt: res_mask needs the register-direct epilogue (no kernel with it takes this product)"); return -1; }
-  if ((a16 || plain_any) && !f32src && use_glds) { if (mode == MODE_PLAIN) G(MODE_PLAIN); else if (mode == MODE_CONV_FWD) G(MODE_CONV_FWD); else G(MODE_CONV_BWD); }
-#undef G2
-#undef G3
-#undef G
-#define L(MODE, F, A) do { avec_note_kernel("gemm_nt_kernel<%s,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BM, BN, MODE, (int)F, (int)A); if (int r = avec_lds_optin(gemm_nt_kernel<T, BM, BN, MODE, F, A>, lds)) return r; hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, MODE, F, A>), grid, dim3(256), lds, st, g); } while (0)
-  if (mode == MODE_PLAIN) {
-    if (f32src) { if (a16) L(MODE_PLAIN, true, true); else L(MODE_PLAIN, true, false); }
-    else { if (a16) L(MODE_PLAIN, false, true); else L(MODE_PLAIN, false, false); }
-  } else if (mode == MODE_CONV_FWD) { if (a16) L(MODE_CONV_FWD, false, true); else L(MODE_CONV_FWD, false, false); }
-  else { if (a16) L(MODE_CONV_BWD, false, true); else L(MODE_CONV_BWD, false, false); }
-#undef L
-  return 0;
+  // 64-byte rows (K-step 32): half the ring, 4 resident workgroups per CU instead of 2 -- measured +4..18 % on the implicit-GEMM layers with
+  // thousands of tiles, -16 % on the deep-K / few-tile ones (512-channel 3x3 stage): chosen by tile count.  AVEC_NT_RB=64/128 forces it.
+  static const bool rb_env_set = getenv("AVEC_NT_RB") != nullptr;
+  static const int rb_env = rb_env_set ? atoi(getenv("AVEC_NT_RB")) : 128;
+  const long long ntiles = (long long)grid.x * grid.y;
+  const bool rb64 = sizeof(T) == 2 && (rb_env_set ? rb_env == 64 : ntiles >= 1536);
+  const bool dma = (a16 || plain_any) && !f32src;
+  if (mode == MODE_PLAIN) return launch_nt_general<T, BM, BN, MODE_PLAIN>(g, grid, dma, rb64, f32src, a16, st);
+  if (mode == MODE_CONV_FWD) return launch_nt_general<T, BM, BN, MODE_CONV_FWD>(g, grid, dma, rb64, f32src, a16, st);
+  return launch_nt_general<T, BM, BN, MODE_CONV_BWD>(g, grid, dma, rb64, f32src, a16, st);
 }
 
 // host side: 1 = not applicable (caller continues with the generic kernels), 0 = launched, other = error
@@ -1450,12 +1460,8 @@ static int launch_conv_shift(const GemmArgs& g_in, int mode, hipStream_t st) {
   static const bool off = getenv("AVEC_NO_CONV_SHIFT") != nullptr;
   const RowSrc& a = g_in.a;
   if (off || mode == MODE_PLAIN || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.H != a.OH || a.W != a.OW || a.W > 31 || a.C % 32 != 0) return 1;
-  if (!aligned16(a.ptr) || !aligned16(g_in.W) || g_in.ldw % 8 != 0 || g_in.M * a.C >= (1ll << 31) || (long long)g_in.N * g_in.ldw >= (1ll << 31) || g_in.N < 64) return 1;
-  static const bool xcd_order = true;
-  GemmArgs g = g_in; g.perm2 = 0; g.pTs[0] = xcd_order ? 1 : 0;        // (no parity classes here: pTs[0] is this kernel's tile-order switch)
-#define S(BM, BN, MODE) do { const size_t ring = (size_t)3 * BN * 64 + (size_t)2 * (BM + 64) * 64 + 512 + (BM / 64 - 1) * 2048, epi = (size_t)64 * (BN + 4) * 4 + 10 * BN * 4; const size_t lds = ring > epi ? ring : epi; \
-    dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN)); \
-    avec_note_kernel("conv3x3_shift_kernel<%d,%d,%d>", BM, BN, MODE); if (int r = avec_lds_optin(conv3x3_shift_kernel<BM, BN, MODE>, lds)) return r; hipLaunchKernelGGL((conv3x3_shift_kernel<BM, BN, MODE>), grid, dim3(256), lds, st, g); return 0; } while (0)
+  if (!avec_aligned16(a.ptr) || !avec_aligned16(g_in.W) || g_in.ldw % 8 != 0 || g_in.M * a.C >= (1ll << 31) || (long long)g_in.N * g_in.ldw >= (1ll << 31) || g_in.N < 64) return 1;
+  GemmArgs g = g_in; g.perm2 = 0; g.pTs[0] = 1;        // (no parity classes here: pTs[0] is this kernel's tile-order switch, 1 = XCD-aware order)
   // 256-row tiles halve the weight-tile DMA per FLOP (measured 5-15 % on the 3200-image ResNet stages 2-3, slower once fewer than ~3 tiles per CU remain)
   static const int bm_env = getenv("AVEC_SHIFT_BM") ? atoi(getenv("AVEC_SHIFT_BM")) : 0;
   // tile height by wave quantisation: workgroups / (rounds * resident slots), slots = 256 CUs x 3 (128 rows, 136 VGPRs) or x 2 (256 rows, 237 VGPRs);
@@ -1463,19 +1469,14 @@ static int launch_conv_shift(const GemmArgs& g_in, int mode, hipStream_t st) {
   const long long t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128), t256 = ((g.M + 255) / 256) * ((g.N + 127) / 128);
   const double e128 = (double)t128 / (double)(((t128 + 767) / 768) * 768), e256 = 1.08 * (double)t256 / (double)(((t256 + 511) / 512) * 512);
   const bool tr_ok = epi_tr_ok(g) && !g.e.res_cls0;
-#define ST(BM, BN, MODE) do { const size_t ring = (size_t)3 * BN * 64 + (size_t)2 * (BM + 64) * 64 + 512 + (BM / 64 - 1) * 2048; const size_t lds = ring; \
-    dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN)); \
-    avec_note_kernel("conv3x3_shift_kernel<%d,%d,%d,tr>", BM, BN, MODE); if (int r = avec_lds_optin(conv3x3_shift_kernel<BM, BN, MODE, true>, lds)) return r; hipLaunchKernelGGL((conv3x3_shift_kernel<BM, BN, MODE, true>), grid, dim3(256), lds, st, g); return 0; } while (0)
+  const bool fwd = mode == MODE_CONV_FWD;
   if (g.N >= 128 && (bm_env == 256 || (bm_env == 0 && e256 > e128) || (g.e.res_mask && tr_ok))) {
-    if (tr_ok) { if (mode == MODE_CONV_FWD) ST(256, 128, MODE_CONV_FWD); else ST(256, 128, MODE_CONV_BWD); }
-    if (mode == MODE_CONV_FWD) S(256, 128, MODE_CONV_FWD); else S(256, 128, MODE_CONV_BWD);
+    if (tr_ok) return fwd ? launch_shift<256, 128, MODE_CONV_FWD, true>(g, st) : launch_shift<256, 128, MODE_CONV_BWD, true>(g, st);
+    return fwd ? launch_shift<256, 128, MODE_CONV_FWD, false>(g, st) : launch_shift<256, 128, MODE_CONV_BWD, false>(g, st);
   }
-#undef ST
   if (g.e.res_mask) { avec_set_error("gemm_nt: res_mask needs the register-direct epilogue (N >= 128, bf16 output and residual in 16-byte pieces)"); return -1; }
-  if (g.N >= 128) { if (mode == MODE_CONV_FWD) S(128, 128, MODE_CONV_FWD); else S(128, 128, MODE_CONV_BWD); }
-  if (mode == MODE_CONV_FWD) S(128, 64, MODE_CONV_FWD); else S(128, 64, MODE_CONV_BWD);
-#undef S
-  return 0;
+  if (g.N >= 128) return fwd ? launch_shift<128, 128, MODE_CONV_FWD, false>(g, st) : launch_shift<128, 128, MODE_CONV_BWD, false>(g, st);
+  return fwd ? launch_shift<128, 64, MODE_CONV_FWD, false>(g, st) : launch_shift<128, 64, MODE_CONV_BWD, false>(g, st);
 }
 
 template <typename T>
@@ -1484,8 +1485,7 @@ static int launch_nt(const GemmArgs& g, int mode, int src_f32, hipStream_t st) {
   long long t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128);
   if (g.N > 64 && t128 >= 384) return launch_nt_mode<T, 128, 128>(g, mode, src_f32, st);
   // plain bf16 products with whole 16-byte K-chunks: the lean 64 x 64 kernel beats the general 128 x 64 one up to the sizes the model has (3200 x 1024 x 256: 11.3 vs 11.8 us)
-  static const bool no_lean = false;
-  const bool lean = sizeof(T) == 2 && mode == MODE_PLAIN && !src_f32 && !no_lean && g.K % 8 == 0 && ((g.M + 63) / 64) * ((g.N + 63) / 64) <= 4096;      // (K = 8n + 4 with many tiles: the general 128 x 64 kernel is faster, 14.3 vs 16.0 us at 6400 x 720 x 180; the lean kernel takes those shapes only where 64 x 64 tiles are chosen anyway)
+  const bool lean = sizeof(T) == 2 && mode == MODE_PLAIN && !src_f32 && g.K % 8 == 0 && ((g.M + 63) / 64) * ((g.N + 63) / 64) <= 4096;      // (K = 8n + 4 with many tiles: the general 128 x 64 kernel is faster, 14.3 vs 16.0 us at 6400 x 720 x 180; the lean kernel takes those shapes only where 64 x 64 tiles are chosen anyway)
   if (!lean && ((g.M + 127) / 128) * ((g.N + 63) / 64) >= 384) return launch_nt_mode<T, 128, 64>(g, mode, src_f32, st);
   return launch_nt_mode<T, 64, 64>(g, mode, src_f32, st);
 }
@@ -1509,8 +1509,7 @@ extern "C" int avec_gemm_nt(int dtype, const void* A, const avec_rows_t* a_rows,
     const int KE = dtype == AVEC_BF16 ? 64 : 32;
     const long long imgs = a_mode == MODE_CONV_FWD ? (M + (long long)a_rows->OH * a_rows->OW - 1) / ((long long)a_rows->OH * a_rows->OW) : (M + (long long)a_rows->H * a_rows->W - 1) / ((long long)a_rows->H * a_rows->W);
     const long long src_elems = imgs * (a_mode == MODE_CONV_FWD ? (long long)a_rows->H * a_rows->W : (long long)a_rows->OH * a_rows->OW) * a_rows->C;
-    static const bool no_fast = false;
-    g.fast_conv = !no_fast && a_rows->C % KE == 0 && a_rows->KH * a_rows->KW <= 32 && src_elems + (long long)(a_rows->W + a_rows->OW + 2) * a_rows->C * 4 < (1ll << 31) &&
+    g.fast_conv = a_rows->C % KE == 0 && a_rows->KH * a_rows->KW <= 32 && src_elems + (long long)(a_rows->W + a_rows->OW + 2) * a_rows->C * 4 < (1ll << 31) &&
                   (a_mode == MODE_CONV_FWD || a_rows->stride == 1 || a_rows->stride == 2);
     static const bool no_perm = getenv("AVEC_NO_PERM2") != nullptr;
     if (!no_perm && dtype == AVEC_BF16 && g.fast_conv && a_mode == MODE_CONV_BWD && a_rows->stride == 2 && M == imgs * (long long)a_rows->H * a_rows->W) {
@@ -1518,10 +1517,7 @@ extern "C" int avec_gemm_nt(int dtype, const void* A, const avec_rows_t* a_rows,
     }
   }
   Epi& e = g.e;
-  e.out = ep->out; e.ldo = ep->ldo; e.out_f32 = ep->out_f32; e.out_pre = ep->out_pre; e.ldpre = ep->ldpre; e.bias = ep->bias;
-  e.act = ep->act; e.drop_p = ep->drop_p; e.rng = (const unsigned long long*)ep->rng; e.stream = ep->rng_stream;
-  e.res = ep->res; e.ldres = ep->ldres; e.alpha = ep->alpha; e.res_act = ep->res_act; e.dact_z = ep->dact_z; e.ldz = ep->ldz; e.dact = ep->dact;
-  e.colsum = ep->colsum; e.stats = ep->stats;
+  e = make_epi(ep);
   e.bnb_y = ep->bnb_y; e.ldby = ep->ldby; e.bnb_ss = ep->bnb_ss; e.bnb_mask = ep->bnb_mask; e.res_cls0 = ep->res_cls0; e.res_mask = ep->res_mask;
   AVEC_CHECK_ARG(!e.res_mask || (dtype == AVEC_BF16 && !a_f32 && a_mode != AVEC_ROWS_PLAIN && e.res && e.res_act && !e.res_cls0 && e.ldres % 8 == 0),
                  "gemm_nt: res_mask needs a bf16 convolution product with a bf16 residual whose rows are whole 8-element pieces");
@@ -1540,33 +1536,53 @@ extern "C" int avec_gemm_nt(int dtype, const void* A, const avec_rows_t* a_rows,
 
 
 /* fp8 forward Linear product (include/avec_hip.h) */
+template <int BM, int BN, int STG>
+static int launch_nt_fp8(const GemmArgs& g, const float* amax_a, const float* amax_w, hipStream_t st) {
+  const dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN));
+  const size_t lds = max_lds((size_t)STG * (BM + BN) * 128, epi_lds(BN));
+  const auto kernel = gemm_nt_fp8_kernel<BM, BN, STG>;      // not through avec_launch: this entry point notes no name (avec_last_kernel keeps the one before it)
+  if (int r = avec_lds_optin(kernel, lds)) return r;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, g, amax_a, amax_w);
+  return 0;
+}
 extern "C" int avec_gemm_nt_fp8(const void* A, long long lda, const void* W, long long ldw, long long M, int N, int K,
                                 const float* amax_a, const float* amax_w, const avec_epilogue_t* ep, hipStream_t stream) {
   AVEC_CHECK_ARG(A && W && ep && ep->out && amax_a && amax_w, "gemm_nt_fp8: null pointer");
-  AVEC_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 16 == 0 && lda % 16 == 0 && ldw % 16 == 0 && aligned16(A) && aligned16(W),
+  AVEC_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 16 == 0 && lda % 16 == 0 && ldw % 16 == 0 && avec_aligned16(A) && avec_aligned16(W),
                  "gemm_nt_fp8: M=%lld N=%d K=%d lda=%lld ldw=%lld: K and the row strides must be multiples of 16 bytes, operands 16-byte aligned", M, N, K, lda, ldw);
   GemmArgs g; memset(&g, 0, sizeof(g));
   g.a.ptr = A; g.a.ld = lda; g.W = W; g.ldw = ldw; g.M = M; g.N = N; g.K = K;
-  Epi& e = g.e;
-  e.out = ep->out; e.ldo = ep->ldo; e.out_f32 = ep->out_f32; e.out_pre = ep->out_pre; e.ldpre = ep->ldpre; e.bias = ep->bias;
-  e.act = ep->act; e.drop_p = ep->drop_p; e.rng = (const unsigned long long*)ep->rng; e.stream = ep->rng_stream;
-  e.res = ep->res; e.ldres = ep->ldres; e.alpha = ep->alpha; e.res_act = ep->res_act; e.dact_z = ep->dact_z; e.ldz = ep->ldz; e.dact = ep->dact;
-  e.colsum = ep->colsum; e.stats = ep->stats;
-  AVEC_CHECK_ARG(!(e.drop_p > 0.f) || e.rng, "gemm_nt_fp8: dropout without rng state");
-#define F8(BM, BN, S_) do { dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((N + BN - 1) / BN)); \
-    const size_t ring = (size_t)S_ * (BM + BN) * 128, epi = (size_t)64 * (BN + 4) * 4 + 10 * BN * 4; const size_t lds = ring > epi ? ring : epi; \
-    if (int r = avec_lds_optin(gemm_nt_fp8_kernel<BM, BN, S_>, lds)) return r; \
-    hipLaunchKernelGGL((gemm_nt_fp8_kernel<BM, BN, S_>), grid, dim3(256), lds, stream, g, amax_a, amax_w); } while (0)
+  g.e = make_epi(ep);
+  AVEC_CHECK_ARG(!(g.e.drop_p > 0.f) || g.e.rng, "gemm_nt_fp8: dropout without rng state");
   const long long t128 = ((M + 127) / 128) * ((N + 127) / 128);
-  if (N > 64 && t128 >= 384) F8(128, 128, 2);
-  else if (((M + 127) / 128) * ((N + 63) / 64) >= 384) F8(128, 64, 2);
-  else F8(64, 64, 4);
-#undef F8
+  int r;
+  if (N > 64 && t128 >= 384) r = launch_nt_fp8<128, 128, 2>(g, amax_a, amax_w, stream);
+  else if (((M + 127) / 128) * ((N + 63) / 64) >= 384) r = launch_nt_fp8<128, 64, 2>(g, amax_a, amax_w, stream);
+  else r = launch_nt_fp8<64, 64, 4>(g, amax_a, amax_w, stream);
+  if (r) return r;
   AVEC_LAUNCH_CHECK();
   return 0;
 }
 
 static thread_local TnMulti* tn_collect = nullptr;      // set while avec_gemm_tn_batched_multi gathers its problems
+template <typename T, int BI, int BJ, int MODE, bool F32SRC, bool A16>
+static int launch_tn_generic(const TnArgs& g, dim3 grid, hipStream_t st) {
+  return avec_launch(gemm_tn_kernel<T, BI, BJ, MODE, F32SRC, A16>, grid, dim3(256), (size_t)2 * (BI + BJ) * LDS_ROW, st, {g},
+                     "gemm_tn_kernel<%s,%d,%d,%d,%d,%d>", elt_name<T>(), BI, BJ, MODE, (int)F32SRC, (int)A16);
+}
+template <int BI, int BJ, int MODE, bool Q32, int KT>
+static int launch_tn_tr(TnArgs g, dim3 grid, hipStream_t st) {
+  g.q_nwrap = (KT + g.q_ohw - 1) / g.q_ohw;
+  return avec_launch(gemm_tn_tr_kernel<BI, BJ, MODE, 2, Q32, KT>, grid, dim3(256), (size_t)2 * KT * (BI + BJ) * 2, st, {g},
+                     "gemm_tn_tr_kernel<%d,%d,%d,2,%d,%d>", BI, BJ, MODE, (int)Q32, KT);
+}
+template <int BI, int BJ, int KT>
+static int launch_tn_tr_mode(const TnArgs& g, int mode, dim3 grid, hipStream_t st) {
+  if (mode == MODE_PLAIN) return launch_tn_tr<BI, BJ, MODE_PLAIN, false, KT>(g, grid, st);
+  const long long q_elems = ((g.M + (long long)g.q.OH * g.q.OW - 1) / ((long long)g.q.OH * g.q.OW) + 1) * g.q.H * g.q.W * g.q.C;
+  return q_elems < (1ll << 31) ? launch_tn_tr<BI, BJ, MODE_CONV_FWD, true, KT>(g, grid, st) : launch_tn_tr<BI, BJ, MODE_CONV_FWD, false, KT>(g, grid, st);      // 32-bit offsets into the gathered operand?
+}
+
 template <typename T, int BI, int BJ>
 static int launch_tn_tile(TnArgs g, int mode, int q_f32, int nbatch, hipStream_t st) {
   constexpr int KE = BKB / (int)sizeof(T);
@@ -1586,42 +1602,31 @@ static int launch_tn_tile(TnArgs g, int mode, int q_f32, int nbatch, hipStream_t
   split = (g.M + per - 1) / per;
   g.m_per_block = (int)per; g.split = (int)split;
   dim3 grid((g.I + BI - 1) / BI, (g.J + BJ - 1) / BJ, (unsigned)(split * nbatch));
-  size_t lds = (size_t)2 * (BI + BJ) * LDS_ROW;
   constexpr int VEC = Elt<T>::VEC;
   const bool f32src = q_f32 && sizeof(T) == 2;
-  const bool a16 = nbatch == 1 && aligned16(g.P) && aligned16(g.q.ptr) && g.Iq % VEC == 0 && g.Jq % VEC == 0 && g.ldp % VEC == 0 &&
+  const bool a16 = nbatch == 1 && avec_aligned16(g.P) && avec_aligned16(g.q.ptr) && g.Iq % VEC == 0 && g.Jq % VEC == 0 && g.ldp % VEC == 0 &&
                    (mode != MODE_PLAIN || (g.q.ld % (f32src ? 4 : VEC) == 0));
   if (sizeof(T) == 2 && a16 && !f32src && !g.Oact && (mode == MODE_PLAIN || g.q_mg != 0)) {        // bf16: LDS-DMA + transposed-read kernel (gathered operand: images of <= 4096 output pixels)
-    static const bool use_tr = true;
-    if (use_tr) {
-      // reduction rows per LDS tile: 32 (two 16 KB stages for 128x128) keeps 4 workgroups resident per CU; measured on the ResNet weight
-      // gradients 1.2-2.1x over 64-row tiles (2 per CU), and 4-stage rings (1 per CU) are 1.5-2x slower: occupancy hides the HBM latency
-      static const int kt_env = getenv("AVEC_TN_KT") ? atoi(getenv("AVEC_TN_KT")) : 32;
-      const long long q_elems = mode == MODE_PLAIN ? 0 : ((g.M + (long long)g.q.OH * g.q.OW - 1) / ((long long)g.q.OH * g.q.OW) + 1) * g.q.H * g.q.W * g.q.C;
-      const bool q32 = q_elems < (1ll << 31);
-#define LT(MODE, Q32, KT_) do { const size_t l2 = (size_t)2 * KT_ * (BI + BJ) * 2; g.q_nwrap = (KT_ + g.q_ohw - 1) / g.q_ohw; avec_note_kernel("gemm_tn_tr_kernel<%d,%d,%d,2,%d,%d>", BI, BJ, MODE, (int)Q32, KT_); if (int r = avec_lds_optin(gemm_tn_tr_kernel<BI, BJ, MODE, 2, Q32, KT_>, l2)) return r; \
-        hipLaunchKernelGGL((gemm_tn_tr_kernel<BI, BJ, MODE, 2, Q32, KT_>), grid, dim3(256), l2, st, g); return 0; } while (0)
-#define LK(KT_) do { if (mode == MODE_PLAIN) LT(MODE_PLAIN, false, KT_); else if (q32) LT(MODE_CONV_FWD, true, KT_); else LT(MODE_CONV_FWD, false, KT_); } while (0)
-      if (kt_env == 64) LK(64); else LK(32);
-#undef LK
-#undef LT
-    }
+    // reduction rows per LDS tile: 32 (two 16 KB stages for 128x128) keeps 4 workgroups resident per CU; measured on the ResNet weight
+    // gradients 1.2-2.1x over 64-row tiles (2 per CU), and 4-stage rings (1 per CU) are 1.5-2x slower: occupancy hides the HBM latency
+    static const int kt_env = getenv("AVEC_TN_KT") ? atoi(getenv("AVEC_TN_KT")) : 32;
+    return kt_env == 64 ? launch_tn_tr_mode<BI, BJ, 64>(g, mode, grid, st) : launch_tn_tr_mode<BI, BJ, 32>(g, mode, grid, st);
   }
   if (g.pcs) {      // kernels without the fused column sums: a separate pass (plain atomics only when weight gradients run on their own stream)
     if (int r = colsum_launch(sizeof(T) == 2 ? AVEC_BF16 : AVEC_F32, g.P, g.ldp, g.pcs, g.M, g.I, true, st)) return r;
-  }     // kernels without the fused column sums
-#define L(MODE, F, A) do { avec_note_kernel("gemm_tn_kernel<%s,%d,%d,%d,%d,%d>", (sizeof(T) == 2 ? "bf16" : "float"), BI, BJ, MODE, (int)F, (int)A); if (int r = avec_lds_optin(gemm_tn_kernel<T, BI, BJ, MODE, F, A>, lds)) return r; hipLaunchKernelGGL((gemm_tn_kernel<T, BI, BJ, MODE, F, A>), grid, dim3(256), lds, st, g); } while (0)
+  }
   if (tn_collect && sizeof(T) == 2 && BI == 64 && BJ == 64 && mode == MODE_PLAIN && !f32src && !a16 && !g.pcs && tn_collect->n < AVEC_TN_MULTI_MAX) {
     TnMulti& m = *tn_collect; const int k = m.n++;           // (avec_gemm_tn_batched_multi: this problem joins the common launch)
     m.g[k] = g; m.gx[k] = (int)grid.x; m.gy[k] = (int)grid.y; m.first[k + 1] = m.first[k] + (int)(grid.x * grid.y * grid.z);
     return 0;
   }
   if (mode == MODE_PLAIN) {
-    if (f32src) { if (a16) L(MODE_PLAIN, true, true); else L(MODE_PLAIN, true, false); }
-    else { if (a16) L(MODE_PLAIN, false, true); else L(MODE_PLAIN, false, false); }
-  } else { if (a16) L(MODE_CONV_FWD, false, true); else L(MODE_CONV_FWD, false, false); }
-#undef L
-  return 0;
+    if constexpr (sizeof(T) == 2) {      // an fp32 source is staged for bf16 products only
+      if (f32src) return a16 ? launch_tn_generic<T, BI, BJ, MODE_PLAIN, true, true>(g, grid, st) : launch_tn_generic<T, BI, BJ, MODE_PLAIN, true, false>(g, grid, st);
+    }
+    return a16 ? launch_tn_generic<T, BI, BJ, MODE_PLAIN, false, true>(g, grid, st) : launch_tn_generic<T, BI, BJ, MODE_PLAIN, false, false>(g, grid, st);
+  }
+  return a16 ? launch_tn_generic<T, BI, BJ, MODE_CONV_FWD, false, true>(g, grid, st) : launch_tn_generic<T, BI, BJ, MODE_CONV_FWD, false, false>(g, grid, st);
 }
 
 static int gemm_tn_impl(int dtype, const void* P, long long ldp, const void* Q, const avec_rows_t* q_rows, int q_mode, int q_f32,
@@ -1646,7 +1651,7 @@ static int gemm_tn_impl(int dtype, const void* P, long long ldp, const void* Q, 
     bool exact = true; for (int px = 0; px < ohw && exact; ++px) exact = (int)(((unsigned)px * mg) >> 20) == px / q_rows->OW;
     g.q_ohw = ohw; g.q_mg = exact ? (int)mg : 0;
   }
-  { static const bool no_xcd = false; g.xcd_map = no_xcd ? 0 : 1; }
+  g.xcd_map = 1;
   g.sPo = strides ? strides[0] : 0; g.sPi = strides ? strides[1] : 0; g.sQo = strides ? strides[2] : 0; g.sQi = strides ? strides[3] : 0;
   g.sOo = strides ? strides[4] : 0; g.sOi = strides ? strides[5] : 0;
   // P batches stay dword aligned; Q batches may start on any element (heads of odd width, d = 45: the plain-load kernels issue unaligned dword loads, which gfx950 serves)
@@ -1657,7 +1662,7 @@ static int gemm_tn_impl(int dtype, const void* P, long long ldp, const void* Q, 
   bool big = (I >= 128 && J >= 128) && ((long long)((I + 127) / 128) * ((J + 127) / 128) * nbatch >= 48 || M >= 32768);
   int r;
   // narrow-I long reductions (64-channel conv layers, the stem): a 64x128 tile re-reads P half as often as 64x64 (these launches are bound by L2/HBM traffic)
-  const bool wide = !big && I <= 64 && J >= 128 && M >= 32768 && dtype == AVEC_BF16 && !q_f32 && nbatch == 1 && aligned16(P) && aligned16(Q) && Iq % 8 == 0 && Jq % 8 == 0 &&
+  const bool wide = !big && I <= 64 && J >= 128 && M >= 32768 && dtype == AVEC_BF16 && !q_f32 && nbatch == 1 && avec_aligned16(P) && avec_aligned16(Q) && Iq % 8 == 0 && Jq % 8 == 0 &&
                     ldp % 8 == 0 && (q_mode != MODE_PLAIN || q_rows->ld % 8 == 0);      // (only the transposed-read kernel is instantiated for this shape in practice)
   if (dtype == AVEC_BF16) r = big ? launch_tn_tile<bf16, 128, 128>(g, q_mode, q_f32, nbatch, stream) : wide ? launch_tn_tile<bf16, 64, 128>(g, q_mode, q_f32, nbatch, stream)
                                                                                                     : launch_tn_tile<bf16, 64, 64>(g, q_mode, q_f32, nbatch, stream);
@@ -1692,9 +1697,8 @@ extern "C" int avec_gemm_tn_batched_store(int dtype, const void* P, long long ld
 
 extern "C" int avec_gemm_tn_batched_multi(int dtype, const avec_tn_batched_t* items, int n, hipStream_t stream) {
   AVEC_CHECK_ARG(items && n >= 1 && n <= AVEC_TN_MULTI_MAX, "gemm_tn_batched_multi: need 1..%d problems (got %d)", AVEC_TN_MULTI_MAX, n);
-  static const bool off = false;
   TnMulti m; m.n = 0; m.first[0] = 0;
-  if (!off) tn_collect = &m;
+  tn_collect = &m;
   int rc = 0;
   for (int k = 0; k < n && rc == 0; ++k) {               // a problem that does not take the common small-tile kernel is launched on its own right here
     const avec_tn_batched_t& t = items[k];
@@ -1705,10 +1709,7 @@ extern "C" int avec_gemm_tn_batched_multi(int dtype, const avec_tn_batched_t* it
   tn_collect = nullptr;
   if (rc) return rc;
   if (m.n > 0) {
-    const size_t lds = (size_t)2 * (64 + 64) * LDS_ROW;
-    avec_note_kernel("gemm_tn_multi_kernel<%d>", m.n);
-    if (int r = avec_lds_optin(gemm_tn_multi_kernel, lds)) return r;
-    hipLaunchKernelGGL(gemm_tn_multi_kernel, dim3((unsigned)m.first[m.n]), dim3(256), lds, stream, m);
+    if (int r = avec_launch(gemm_tn_multi_kernel, dim3((unsigned)m.first[m.n]), dim3(256), (size_t)2 * (64 + 64) * LDS_ROW, stream, {m}, "gemm_tn_multi_kernel<%d>", m.n)) return r;
     AVEC_LAUNCH_CHECK();
   }
   return 0;
@@ -1724,6 +1725,12 @@ static bool tn_item_ok(int dtype, const avec_tn_item_t& t) {
   if (t.p_colsum && (t.I % 4 || t.ldp % 4)) return false;
   return t.M < (1ll << 31) && t.ldp < (1ll << 31) && t.ldq < (1ll << 31) && t.ldo < (1ll << 31);
 }
+template <int BT>
+static int launch_tn_grouped(const TnGroup& grp, hipStream_t st) {
+  constexpr int STG = 2, KT = 64;       // ring of 2 x 64 reduction rows (2 x 64 rows and 4 x 32 rows measure the same, 3 stages are slower: profiles/r03_tn_grouped.txt)
+  return avec_launch(gemm_tn_tr_grouped_kernel<BT, STG, KT>, dim3((unsigned)grp.total), dim3(256), (size_t)STG * KT * (BT + BT) * 2, st, {grp},
+                     "gemm_tn_tr_grouped_kernel<%d,%d,%d>", BT, STG, KT);
+}
 extern "C" int avec_gemm_tn_grouped_ok(int dtype, const avec_tn_item_t* item) { return item && tn_item_ok(dtype, *item) ? 1 : 0; }
 
 extern "C" int avec_gemm_tn_grouped(int dtype, const avec_tn_item_t* items, int n, hipStream_t stream) {
@@ -1731,13 +1738,11 @@ extern "C" int avec_gemm_tn_grouped(int dtype, const avec_tn_item_t* items, int 
   for (int k = 0; k < n; ++k) AVEC_CHECK_ARG(tn_item_ok(dtype, items[k]), "gemm_tn_grouped: item %d is not eligible (bf16 operands, row strides >= widths, bias sums need I %% 4 == 0)", k);
   // tile size: 128x128 tiles read each operand byte half as often as 64x64 (these products are bound by L2 traffic), but a group must still cover the
   // chip: take the big tile when the group has enough of them
-  static const int bt_env = 0;
   long long t128 = 0;
   for (int k = 0; k < n; ++k) t128 += (long long)((items[k].I + 127) / 128) * ((items[k].J + 127) / 128);
-  const int BT = bt_env == 64 || bt_env == 128 ? bt_env : (t128 >= 96 ? 128 : 64);
+  const int BT = t128 >= 96 ? 128 : 64;
   // common reduction-slice length: the largest multiple of 64 rows (>= 256) that still yields ~wg_target workgroups over the whole group
-  static const long long wg_env = 0;
-  const long long wg_target = wg_env > 0 ? wg_env : 512;       // every slice costs I*J atomics: 256-512 beat 1536 by 0.2 ms in the step; with the lean DMA loop 512 beats 384 (21.14 vs 21.24 ms, two same-box sweeps)
+  const long long wg_target = 512;       // every slice costs I*J atomics: 256-512 beat 1536 by 0.2 ms in the step; with the lean DMA loop 512 beats 384 (21.14 vs 21.24 ms, two same-box sweeps)
   long long per = 256;
   for (long long cand = 8192; cand >= 256; cand -= 64) {
     long long wgs = 0;
@@ -1757,17 +1762,8 @@ extern "C" int avec_gemm_tn_grouped(int dtype, const avec_tn_item_t* items, int 
     first += t.gx * t.gy * t.split;
   }
   grp.total = first;
-  static const bool no_xcd = false;
-  grp.xcd_map = no_xcd ? 0 : 1;
-  static const int kt_env = 64;       // reduction rows per LDS tile
-  static const int stg_env = 2;
-  const int KT = kt_env == 32 ? 32 : 64, STG = (stg_env == 4 && KT == 32) ? 4 : 2;       // (2 x 64 rows and 4 x 32 rows measure the same, 3 stages are slower: profiles/r03_tn_grouped.txt)
-  const size_t lds = (size_t)STG * KT * (BT + BT) * 2;
-  avec_note_kernel("gemm_tn_tr_grouped_kernel<%d,%d,%d>", BT, STG, KT);
-#define TNG(BT_, S_, K_) do { if (BT == BT_ && STG == S_ && KT == K_) { if (int r = avec_lds_optin(gemm_tn_tr_grouped_kernel<BT_, S_, K_>, lds)) return r; \
-    hipLaunchKernelGGL((gemm_tn_tr_grouped_kernel<BT_, S_, K_>), dim3((unsigned)first), dim3(256), lds, stream, grp); } } while (0)
-  TNG(128, 2, 32); TNG(128, 2, 64); TNG(64, 2, 32); TNG(64, 2, 64); TNG(128, 4, 32); TNG(64, 4, 32);
-#undef TNG
+  grp.xcd_map = 1;
+  if (int r = BT == 128 ? launch_tn_grouped<128>(grp, stream) : launch_tn_grouped<64>(grp, stream)) return r;
   AVEC_LAUNCH_CHECK();
   return 0;
 }

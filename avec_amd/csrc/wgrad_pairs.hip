@@ -326,14 +326,12 @@ int wgrad3x3_pairs_grouped(const avec_wgrad3x3_item_t* items, int n, hipStream_t
     g.cum[i + 1] = g.cum[i] + (long long)kinds * g.stages[i] * g.wt[i];
     total_stages += (long long)kinds * g.stages[i];
   }
-  static const int wgs_env = 256;
-  const int grid = (int)(total_stages < wgs_env ? total_stages : wgs_env);
-  static const int ranges_env = 0;      // A/B: 1 = kind-major order (one range per layer)
+  const int grid = (int)(total_stages < 256 ? total_stages : 256);
   for (int i = 0; i < n; ++i) {      // ranges: one share ~ one kind over one range
     const int kinds = (items[i].C / 64) * (items[i].C / 128);
     const double shares = (double)grid * (double)(g.cum[i + 1] - g.cum[i]) / (double)g.cum[n];
     int R = (int)(shares / kinds + 0.5); if (R < 1) R = 1; if (R > g.stages[i]) R = g.stages[i];
-    g.ranges[i] = ranges_env > 0 ? (ranges_env < g.stages[i] ? ranges_env : g.stages[i]) : R;
+    g.ranges[i] = R;
   }
   if (int r = avec_lds_optin(wgrad3x3_pairs_grouped_kernel, WP_LDS)) return r;
   avec_note_kernel("wgrad3x3_pairs_grouped_kernel");
