@@ -291,6 +291,7 @@ extern "C" int avec_ctc_loss(const float* logits, const long long* in_lens, cons
   const size_t lds_fast = (3 * (size_t)T * Smax + T + 4 * (size_t)V + Smax) * 4;
   if (lds_fast <= 64 * 1024) {
     const int nw = ctc_waves((const void*)ctc_lds_kernel, lds_fast, V);
+    avec_note_kernel("ctc_lds_kernel w%d", nw);
     hipLaunchKernelGGL(ctc_lds_kernel, dim3(B), dim3(64 * nw), lds_fast + (size_t)(nw - 4) * V * 4, st, logits, in_lens, targets, tgt_lens, nll, mean_out, grad, B, T, V, Lmax, blank, zero_infinity);
     AVEC_LAUNCH_CHECK(); return 0;
   }
@@ -298,11 +299,13 @@ extern "C" int avec_ctc_loss(const float* logits, const long long* in_lens, cons
   static const bool no_alpha = getenv("AVEC_CTC_NO_ALPHA_LDS") != nullptr;
   if (lds_alpha <= 150 * 1024 && !no_alpha) {
     if (int r = avec_lds_optin(ctc_alpha_lds_kernel, lds_alpha)) return r;
+    avec_note_kernel("ctc_alpha_lds_kernel");
     hipLaunchKernelGGL(ctc_alpha_lds_kernel, dim3(B), dim3(256), lds_alpha, st, logits, in_lens, targets, tgt_lens, nll, mean_out, grad, B, T, V, Lmax, blank, zero_infinity);
     AVEC_LAUNCH_CHECK(); return 0;
   }
   size_t lds = (size_t)(2 * (2 * Lmax + 1) + V) * 4 + (size_t)(2 * Lmax + 1) * 4;
   AVEC_CHECK_ARG(lds <= 60 * 1024, "ctc_loss: label length %d too long for the LDS state buffers", Lmax);
+  avec_note_kernel("ctc_kernel");
   hipLaunchKernelGGL(ctc_kernel, dim3(B), dim3(64), lds, st, logits, in_lens, targets, tgt_lens, nll, mean_out, grad, workspace, B, T, V, Lmax, blank, zero_infinity);
   AVEC_LAUNCH_CHECK(); return 0;
 }
@@ -323,6 +326,7 @@ extern "C" int avec_ctc_loss_multi(int n_heads, const float* const* logits, cons
   }
   AVEC_CHECK_ARG(lds <= 64 * 1024, "ctc_loss_multi: a head does not fit the all-LDS kernel (use avec_ctc_loss per head)");
   const int nw = ctc_waves((const void*)ctc_lds_multi_kernel, lds, V);
+  avec_note_kernel("ctc_lds_multi_kernel w%d", nw);
   hipLaunchKernelGGL(ctc_lds_multi_kernel, dim3((unsigned)(n_heads * B)), dim3(64 * nw), lds + (size_t)(nw - 4) * V * 4, st, h, targets, tgt_lens, B, V, Lmax, blank, zero_infinity);
   AVEC_LAUNCH_CHECK(); return 0;
 }
@@ -385,13 +389,18 @@ extern "C" int avec_scale_by_scalar_multi(int n_tensors, const float* const* g, 
   AVEC_LAUNCH_CHECK(); return 0;
 }
 
-// argmax over the last dim (greedy CTC decoding, nnet/decoders.py:97-120): first maximal index, like torch.argmax
+// argmax over the last dim (greedy CTC decoding, nnet/decoders.py:97-120): first maximal index, like torch.argmax (a NaN counts as maximal, the first NaN wins)
+// true when candidate (z, v) replaces (best, bi).  bi starts at INT_MAX with best = -inf, so a lane that saw an element always holds an index < V.
+__device__ __forceinline__ bool argmax_takes(float z, int v, float best, int bi) {
+  const bool zn = z != z, bn = best != best;
+  return zn ? (!bn || v < bi) : (!bn && (z > best || (z == best && v < bi)));
+}
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, long long* __restrict__ out, long long M, int V) {
   const int lane = threadIdx.x & 63; const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   float best = -INFINITY; int bi = 0x7fffffff;
-  for (int v = lane; v < V; v += 64) { const float z = x[row * V + v]; if (z > best || (z == best && v < bi)) { best = z; bi = v; } }
-  for (int o = 32; o > 0; o >>= 1) { const float ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64); if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; } }
+  for (int v = lane; v < V; v += 64) { const float z = x[row * V + v]; if (argmax_takes(z, v, best, bi)) { best = z; bi = v; } }
+  for (int o = 32; o > 0; o >>= 1) { const float ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64); if (argmax_takes(ob, oi, best, bi)) { best = ob; bi = oi; } }
   if (lane == 0) out[row] = bi;
 }
 extern "C" int avec_argmax_rows(const float* x, long long* out, long long M, int V, hipStream_t st) {
