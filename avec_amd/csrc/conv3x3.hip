@@ -551,7 +551,7 @@ __device__ __forceinline__ void c3_glds16(const void* gsrc, unsigned lds_dst_uni
 typedef __attribute__((ext_vector_type(2))) unsigned c3_u32x2;
 __device__ __forceinline__ c3_u32x2 c3_lds_tr(unsigned lds_addr) { c3_u32x2 v; asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory"); return v; }
 #ifndef C3W_ABL
-#define C3W_ABL 0         // timing experiments on the 64-channel weight gradient (tools/build_abl_c3w.sh): 1 no MFMA, 2 no LDS-DMA, 4 no fragment reads, 8 no final atomics
+#define C3W_ABL 0         // timing experiment on the 64-channel weight gradient (tools/build_abl_c3w.sh): 64 in-kernel cycle counters
 #endif
 #define C3W_KROWS 512                       // reduction rows per image: H*(W+1) <= 512
 #define C3W_DBYTES (C3W_KROWS * 128)        // 65 536: dy image with the slab's row pitch
@@ -563,102 +563,7 @@ extern "C" int avec_c3w_debug(float* out) { return (int)hipMemcpyFromSymbol(out,
 #endif
 
 // bid / nwg: this workgroup's index among the nwg workgroups that share the product
-__device__ __forceinline__ void c3w_body(const C3WArgs& a, const int bid, const int nwg) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Xs = smem; char* Ds = smem + C3_SBYTES;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int H = a.H, W = a.W, PW = W + 1, HW = H * W, NPIX = (H + 2) * PW + 1;
-  typedef __attribute__((address_space(1))) const void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
-  // 128-byte rows, 16-byte chunk index XOR 4*((row >> 1) & 1): the 4 rows of a transposing read fall on distinct banks (as in gemm_tn_tr_kernel)
-  int xoff[9], doff[8];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const int S = (wave + 8 * i) * 64 + lane, row = S >> 3, c = (S & 7) ^ (4 * ((row >> 1) & 1));
-    const int py = (row - 1) / PW, px = (row - 1) - py * PW;
-    const bool in = row >= 1 && row < NPIX && py >= 1 && py <= H && px < W;
-    xoff[i] = in ? ((py - 1) * W + px) * 64 + c * 8 : -1;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int S = (wave + 8 * i) * 64 + lane, row = S >> 3, c = (S & 7) ^ (4 * ((row >> 1) & 1));
-    const int oy = row / PW, ox = row - oy * PW;
-    doff[i] = (oy < H && ox < W) ? (oy * W + ox) * 64 + c * 8 : -1;
-  }
-  // this wave's tiles: co half (wave >> 1) & 1, ci half wave & 1, taps (wave >> 2) + 2 j (j < 4) and, for waves 0..3, tap 8
-  const int cohalf = (wave >> 1) & 1, cihalf = wave & 1, tap0 = wave >> 2;
-  const bool five = wave < 4;
-  const int g4 = lane >> 4, t = lane & 15;
-  int offa[2], offb[5][2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int krow = 8 * (g4 >> 1) + 4 * h + (t >> 2);
-    const int cbA = cohalf * 32 + 16 * (g4 & 1), cbB = cihalf * 32 + 16 * (g4 & 1);
-    offa[h] = krow * 128 + ((((cbA >> 3) + ((t & 3) >> 1)) ^ (4 * ((krow >> 1) & 1))) << 4) + (t & 1) * 8;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const int tap = j < 4 ? tap0 + 2 * j : 8;
-      const int rowd = krow + (tap / 3) * PW + (tap % 3);
-      offb[j][h] = rowd * 128 + ((((cbB >> 3) + ((t & 3) >> 1)) ^ (4 * ((rowd >> 1) & 1))) << 4) + (t & 1) * 8;
-    }
-  }
-  c3_f32x16 acc[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-  const unsigned xs0 = (unsigned)(uintptr_t)(lptr_t)Xs, ds0 = (unsigned)(uintptr_t)(lptr_t)Ds;
-  for (long long n = bid; n < a.N; n += nwg) {
-    __syncthreads();                         // every wave is done with the previous image
-    const bf16* xi = a.x + n * HW * 64; const bf16* di = a.dy + n * HW * 64;
-    if (!(C3W_ABL & 2)) {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) c3_glds16(xoff[i] >= 0 ? (const void*)(xi + xoff[i]) : (const void*)c3_zero16, xs0 + (wave + 8 * i) * 1024);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) c3_glds16(doff[i] >= 0 ? (const void*)(di + doff[i]) : (const void*)c3_zero16, ds0 + (wave + 8 * i) * 1024);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    // (compiler-scheduled reads, two steps unrolled: for this 4-5 MFMA step the hand-made ladder of wgrad3x3_wide_kernel measured 20 % slower)
-#pragma unroll 2
-    for (int s = 0; s < C3W_KROWS / 16; ++s) {
-      const int so = s * 2048;
-      chunk16 fa, fb[5];
-      if (!(C3W_ABL & 4)) {
-        fa = c3_tr_read8(Ds + offa[0] + so, Ds + offa[1] + so);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fb[j] = c3_tr_read8(Xs + offb[j][0] + so, Xs + offb[j][1] + so);
-        if (five) fb[4] = c3_tr_read8(Xs + offb[4][0] + so, Xs + offb[4][1] + so);
-      } else {
-        fa.w[0] = fa.w[1] = fa.w[2] = fa.w[3] = (unsigned)(so + lane);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) fb[j].w[0] = fb[j].w[1] = fb[j].w[2] = fb[j].w[3] = (unsigned)(so * (j + 2) + lane);
-      }
-      if (!(C3W_ABL & 1)) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, fa), __builtin_bit_cast(c3_bf16x8, fb[j]), acc[j], 0, 0, 0);
-        if (five) acc[4] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, fa), __builtin_bit_cast(c3_bf16x8, fb[4]), acc[4], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) { if (j == 4 && !five) break; acc[j][0] += __uint_as_float(fa.w[0] ^ fb[j].w[0]); acc[j][1] += __uint_as_float(fa.w[3] ^ fb[j].w[3]); }
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    if (j == 4 && !five) break;
-    const int tap = j < 4 ? tap0 + 2 * j : 8;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = cohalf * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), ci = cihalf * 32 + (lane & 31);
-      if (!(C3W_ABL & 8) || acc[j][r] == 123.456f) atomicAdd(a.dw + (long long)co * 576 + tap * 64 + ci, acc[j][r]);
-    }
-  }
-}
-
-// Round 5: the same product with the next image ROLLING into the slab behind the k-steps.  In-kernel cycle counts of c3w_body (C3W_ABL 64, profiles/r05_c64_wgrad_ablation.txt):
+// The next image ROLLS into the slab behind the k-steps.  In-kernel cycle counts of a body that loads an image, waits and computes (profiles/r05_c64_wgrad_ablation.txt):
 // 42 % of the kernel is the wait for the image's LDS-DMA (at 6.3 TB/s over the chip -- the rate is fine, nothing runs under it), 58 % the 32 k-steps.  A second pair of
 // buffers does not fit (139 KB), but k-step s only reads dy rows [16 s, 16 s + 16) and slab rows [16 s, 16 s + 16 + 2 (W+1) + 2): after the g-th group of 8 steps the rows
 // below 128 (g + 1) are dead, and the next image's rows can land there.  Four batches per image -- rows [128 g, 128 g + 128) of both regions, the last one the slab's
@@ -780,17 +685,12 @@ __device__ __forceinline__ void c3w_roll_body(const C3WArgs& a, const int bid, c
     }
   }
 }
-#ifndef C3W_ROLL
-#define C3W_ROLL 1        // 0: one image per iteration, its DMA awaited with nothing under it (c3w_body)
-#endif
-__global__ __launch_bounds__(512) void wgrad3x3_c64_kernel(C3WArgs a) { if (C3W_ROLL) c3w_roll_body(a, (int)blockIdx.x, (int)gridDim.x); else c3w_body(a, (int)blockIdx.x, (int)gridDim.x); }
-// several 64-channel layers' weight gradients as ONE grid: the workgroups are shared out evenly, the final atomics (256 x 36 864 sums per launch) are paid once
+// one or several 64-channel layers' weight gradients as ONE grid: the workgroups are shared out evenly, the final atomics (256 x 36 864 sums per launch) are paid once
 struct C3WGroup { C3WArgs it[AVEC_WGRAD_GROUP_MAX]; int first[AVEC_WGRAD_GROUP_MAX + 1]; int n; };
 __global__ __launch_bounds__(512) void wgrad3x3_c64_grouped_kernel(C3WGroup grp) {
   int i = 0;
   while (i + 1 < grp.n && (int)blockIdx.x >= grp.first[i + 1]) ++i;
-  if (C3W_ROLL) c3w_roll_body(grp.it[i], (int)blockIdx.x - grp.first[i], grp.first[i + 1] - grp.first[i]);
-  else c3w_body(grp.it[i], (int)blockIdx.x - grp.first[i], grp.first[i + 1] - grp.first[i]);
+  c3w_roll_body(grp.it[i], (int)blockIdx.x - grp.first[i], grp.first[i + 1] - grp.first[i]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -933,8 +833,7 @@ __device__ __forceinline__ void c3ww_body(const C3WWArgs& a, const int bid, cons
     }
 }
 
-__global__ __launch_bounds__(512) void wgrad3x3_wide_kernel(C3WWArgs a) { c3ww_body(a, (int)blockIdx.x, (int)gridDim.x); }
-// several layers' weight gradients as ONE grid (the final fp32 atomics are ~30 % of a launch of its own: 256 workgroups x 73 728 sums whatever the layer; grouped,
+// one or several layers' weight gradients as ONE grid (the final fp32 atomics are ~30 % of a launch of its own: 256 workgroups x 73 728 sums whatever the layer; grouped,
 // the 256 workgroups are shared out by work and the atomics are paid once for all the layers)
 struct C3WWGroup { C3WWArgs it[AVEC_WGRAD_GROUP_MAX]; int first[AVEC_WGRAD_GROUP_MAX + 1]; int n; };
 __global__ __launch_bounds__(512) void wgrad3x3_wide_grouped_kernel(C3WWGroup grp) {
@@ -963,21 +862,10 @@ int wgrad3x3_pairs_grouped(const avec_wgrad3x3_item_t* items, int n, hipStream_t
 
 extern "C" int avec_wgrad3x3_c128(const void* x, const void* dy, float* dw, long long images, int C, int H, int W, hipStream_t st) {
   AVEC_CHECK_ARG(x && dy && dw && images > 0, "wgrad3x3_c128: null buffer");
-  if (wgrad3x3_pairs_supported(H, W, C)) {
-    avec_wgrad3x3_item_t it; it.x = x; it.dy = dy; it.dw = dw; it.images = images; it.C = C; it.H = H; it.W = W; it.reserved = 0;
-    return wgrad3x3_pairs_grouped(&it, 1, st);
-  }
-  C3WWArgs a; a.x = (const bf16*)x; a.dy = (const bf16*)dy; a.dw = dw; a.N = (int)images; a.H = H; a.W = W; a.C = C;
-  AVEC_CHECK_ARG(c3_wide_geometry(H, W, C, a.KP, a.RS, a.IT), "wgrad3x3_c128: %d channels, %dx%d images do not fit the slabs", C, H, W);
-  const size_t lds = (size_t)C3X_ROWS * 256 + C3X_KROWS * 128;
-  if (int r = avec_lds_optin(wgrad3x3_wide_kernel, lds)) return r;
-  const int kinds = (C / 64) * (C / 128);
-  const long long groups = (images + a.IT - 1) / a.IT;
-  long long per_kind = 256 / kinds; if (per_kind < 1) per_kind = 1; if (per_kind > groups) per_kind = groups;
-  avec_note_kernel("wgrad3x3_wide_kernel");
-  hipLaunchKernelGGL(wgrad3x3_wide_kernel, dim3((unsigned)(per_kind * kinds)), dim3(512), lds, st, a);
-  AVEC_LAUNCH_CHECK();
-  return 0;
+  int KP, RS, IT;
+  AVEC_CHECK_ARG(wgrad3x3_pairs_supported(H, W, C) || c3_wide_geometry(H, W, C, KP, RS, IT), "wgrad3x3_c128: %d channels, %dx%d images do not fit the slabs", C, H, W);
+  avec_wgrad3x3_item_t it; it.x = x; it.dy = dy; it.dw = dw; it.images = images; it.C = C; it.H = H; it.W = W; it.reserved = 0;
+  return avec_wgrad3x3_c128_grouped(&it, 1, st);      // a group of one: min(256 / kinds, image groups) sets of workgroup kinds
 }
 
 extern "C" int avec_wgrad3x3_c64_grouped(const avec_wgrad3x3_item_t* items, int n, hipStream_t st) {
@@ -1091,12 +979,6 @@ static int conv3x3_c64_impl(const void* x, const void* w, void* y, const void* r
 extern "C" int avec_wgrad3x3_c64(const void* x, const void* dy, float* dw, long long images, int H, int W, hipStream_t st) {
   AVEC_CHECK_ARG(x && dy && dw && images > 0, "wgrad3x3_c64: null buffer");
   AVEC_CHECK_ARG(avec_conv3x3_c64_supported(H, W, 64, 64, 3, 3, 1) && H * (W + 1) <= C3W_KROWS, "wgrad3x3_c64: %dx%d images do not fit the slab", H, W);
-  const size_t lds = C3_SBYTES + C3W_DBYTES;
-  if (int r = avec_lds_optin(wgrad3x3_c64_kernel, lds)) return r;
-  C3WArgs a; a.x = (const bf16*)x; a.dy = (const bf16*)dy; a.dw = dw; a.N = (int)images; a.H = H; a.W = W;
-  const int grid = (int)(images < 256 ? images : 256);
-  avec_note_kernel("wgrad3x3_c64_kernel");
-  hipLaunchKernelGGL(wgrad3x3_c64_kernel, dim3(grid), dim3(512), lds, st, a);
-  AVEC_LAUNCH_CHECK();
-  return 0;
+  avec_wgrad3x3_item_t it; it.x = x; it.dy = dy; it.dw = dw; it.images = images; it.C = 64; it.H = H; it.W = W; it.reserved = 0;
+  return avec_wgrad3x3_c64_grouped(&it, 1, st);       // a group of one: min(images, 256) workgroups
 }

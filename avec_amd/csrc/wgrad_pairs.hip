@@ -3,7 +3,7 @@
 //
 //     dW[co][kh][kw][ci] = sum over images, oy, ox of  dy[img][oy][ox][co] * x[img][oy + kh - 1][ox + kw - 1][ci]        (zero outside the image)
 //
-// The slab kernel of round 2/3 (conv3x3.hip: wgrad3x3_wide_kernel) flattens an image to rows of pitch W+1 and multiplies shifted views of it: every MFMA of a
+// The slab kernel of round 2/3 (conv3x3.hip: wgrad3x3_wide_grouped_kernel) flattens an image to rows of pitch W+1 and multiplies shifted views of it: every MFMA of a
 // K-step takes its own transposed x fragment (1.1 fragment reads per MFMA: the LDS pipe is the limit) and 16-44 % of the reduction rows are padding (3x3 images use
 // 9 of 16).  Here the reduction index is the IMAGE ROW  r = img * H + oy  (contiguous in memory, no padding), and the pixel position inside the row is unrolled:
 // for an output column ox and a tap (kh, kw) with 0 <= ox + kw - 1 < W

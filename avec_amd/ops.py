@@ -3,6 +3,7 @@
 Every Function writes parameter gradients straight into `param.grad` (accumulating; the flat gradient
 arena when the model owns one) and returns None for them, so the backward pass is a fixed sequence of
 HIP launches on the current stream (graph-capturable)."""
+import collections
 import ctypes
 import os
 
@@ -147,16 +148,12 @@ def empty(shape, dtype, ref):
 
 TN_MULTI = True                     # attention backward: dK, dV and dE as one launch (0: three)
 ATTN_ODD_VALU = False             # A/B: odd head widths take the VALU column pass of the attention backward (round 2)
-CAST_DEFER = True                   # fp32-input weight gradients: cast once and join the grouped launch (0: a launch of their own)
-TNG_ALIGNED_ONLY = False       # A/B: only 16-byte-aligned operands take the grouped weight-gradient launch
 
 
 def _chunk_readable(t, ld, width, rows):
     """rows of `width` 16-bit elements at stride `ld`: may the kernels read whole 8-element chunks behind the last row?"""
     if width % 8 == 0 and ld % 8 == 0 and t.data_ptr() % 16 == 0:
         return True
-    if TNG_ALIGNED_ONLY:
-        return False
     if ld >= (width + 7) // 8 * 8:
         return True
     st = t.untyped_storage()
@@ -234,7 +231,7 @@ def gemm_nt(A, W, out, M, N, K, *, rows=None, mode=ROWS_PLAIN, a_f32=False, ldw=
     return out
 
 
-# (The module-level switches of this file -- TN_MULTI, PREP_FUSE, LN_PAIR, RELU_BITMASK, STEM3P, ... -- are plain constants since round 6: the alternatives they select
+# (The module-level switches of this file -- TN_MULTI, LN_PAIR, RELU_BITMASK, CONVMOD_BN_FUSE, STEM3P, ... -- are plain constants: the alternatives they select
 # are kept for the parity tests that flip them in-process (tests/test_gpu_round3.py, test_gpu_round4.py, test_gpu_parity.py), not as environment switches.)
 # ---- deferred parameter gradients ------------------------------------------------------------------------------------------------------------
 # Weight gradients (dW = dY^T X), bias gradients and LayerNorm gamma/beta gradients only feed the optimizer: nothing in the backward chain waits for
@@ -243,18 +240,102 @@ def gemm_nt(A, W, out, M, N, K, *, rows=None, mode=ROWS_PLAIN, a_f32=False, ldw=
 # avec_layernorm_param_grads_grouped: one grid over the tiles of up to 32 / 40 products) when a queue fills, at the explicit flush points (end of the audio
 # branch, before an early gradient all-reduce) and by a final autograd callback when the backward pass ends.  ops.DEFER_WGRAD = False restores immediate launches.
 DEFER_WGRAD = os.environ.get("AVEC_DEFER_WGRAD", "1") != "0"
-_TN_WHY = False      # debugging aid: print every weight-gradient product that misses the grouped launch
-_TN_FLUSH_AT = TN_GROUP_MAX
-_DEFER = {"queues": {}, "task": -1}
+
+
+# one kind of queued launch: its ctypes item, the most items one launch takes, the grouped entry point (lib name) and the dtype argument in front of its items (a
+# callable, or None: the entry point takes none), the KERNEL_TIMER key (None: not timed), the ALGORITHMIC bytes of one item, and whether a push that fills a group
+# launches it at once
+_QueueKind = collections.namedtuple("_QueueKind", "item group_max launcher dtype timer_key abytes flush_when_full")
+
+
+def _wgrad3x3_bytes(it):
+    return 2.0 * 2 * it.images * it.H * it.W * it.C + 4.0 * 9 * it.C * it.C      # x, dy once (bf16) + dW once (fp32)
+
+
+# in launch order.  cw / cw64: 3x3 weight gradients of the wide ResNet layers / of the 64-channel layers, launched when the pass is through
+_QUEUE_KINDS = {
+    "tn": _QueueKind(TnItem, TN_GROUP_MAX, "gemm_tn_grouped", lambda: BF16, (1, ROWS_PLAIN), lambda it: 2.0 * it.M * (it.I + it.J) + 4.0 * it.I * it.J, True),      # P, Q once (bf16) + dW once (fp32)
+    "ln": _QueueKind(LnItem, LN_GROUP_MAX, "layernorm_param_grads_grouped", rt.dt, None, None, True),
+    "cw": _QueueKind(WgradItem, WGRAD_GROUP_MAX, "wgrad3x3_c128_grouped", None, (2, 2), _wgrad3x3_bytes, False),
+    "cw64": _QueueKind(WgradItem, WGRAD_GROUP_MAX, "wgrad3x3_c64_grouped", None, (2, 2), _wgrad3x3_bytes, False),
+}
 
 
 class _PendingGrads:
-    __slots__ = ("stream", "tn", "ln", "keep", "flops", "cw", "cw_flops", "cw64", "cw64_flops")
+    """the queued launches of one stream: items and algorithmic FLOPs per kind, and the operand tensors (`keep`) that must outlive the launches"""
+    __slots__ = ("stream", "items", "flops", "keep")
 
     def __init__(self, stream):
-        self.stream, self.tn, self.ln, self.keep, self.flops = stream, [], [], [], 0.0
-        self.cw, self.cw_flops = [], 0.0           # 3x3 weight gradients of the wide ResNet layers (avec_wgrad3x3_c128_grouped)
-        self.cw64, self.cw64_flops = [], 0.0       # ... of the 64-channel layers (avec_wgrad3x3_c64_grouped)
+        self.stream = stream
+        self.clear()
+
+    def clear(self):
+        self.items, self.flops, self.keep = {k: [] for k in _QUEUE_KINDS}, dict.fromkeys(_QUEUE_KINDS, 0.0), []
+
+    def push(self, kind, item, keep, flops=0.0):
+        self.items[kind].append(item)
+        self.keep += keep
+        self.flops[kind] += flops
+        if _QUEUE_KINDS[kind].flush_when_full and len(self.items[kind]) >= _QUEUE_KINDS[kind].group_max:
+            self.flush((kind,))
+
+    def flush(self, kinds=None):
+        """submit on the CURRENT stream (the queue's own stream during the pass; the caller's stream, which has joined every branch, at the end of it)"""
+        cur = torch.cuda.current_stream()
+        if cur.cuda_stream != self.stream.cuda_stream:
+            for t in self.keep:
+                t.record_stream(cur)
+        for kind in (_QUEUE_KINDS if kinds is None else kinds):
+            k, items = _QUEUE_KINDS[kind], self.items[kind]
+            if not items:
+                continue
+            ev = KERNEL_TIMER.start() if (k.timer_key is not None and KERNEL_TIMER.enabled) else None
+            for i in range(0, len(items), k.group_max):
+                chunk = items[i:i + k.group_max]
+                getattr(lib, k.launcher)(*(() if k.dtype is None else (k.dtype(),)), (k.item * len(chunk))(*chunk), len(chunk), rt.stream())
+            if ev is not None:
+                KERNEL_TIMER.stop(ev, k.timer_key, self.flops[kind], sum(k.abytes(it) for it in items))
+            self.items[kind], self.flops[kind] = [], 0.0
+        if not any(self.items.values()):
+            self.keep = []
+
+
+class _BackwardPass:
+    """everything one backward pass leaves between its autograd nodes"""
+    __slots__ = ("task", "queues", "prep", "ln2", "pos", "bn_ready")
+
+    def __init__(self, task):
+        self.task = task
+        self.queues = {}        # stream handle -> _PendingGrads
+        self.prep = {}          # address of a LayerNorm's dx -> the prepared gradient made with it (see _take_prep)
+        self.ln2 = {}           # address of a feed-forward module's dx -> the dx of the LayerNorm in front of it (see LN_PAIR)
+        self.pos = {}           # _PosGroupEntry -> [the group's shared dE accumulator, layers still to arrive] (see _pos_group_backward)
+        self.bn_ready = {}      # address of a ResNet block's dx -> the completed BatchNorm-backward request of the block in front (see ResNetBlockFn)
+
+    def pending(self):
+        """the queue of the current stream"""
+        st = torch.cuda.current_stream()
+        q = self.queues.get(st.cuda_stream)
+        if q is None:
+            q = self.queues[st.cuda_stream] = _PendingGrads(st)
+        return q
+
+
+_PASS = None
+
+
+def _pass():
+    """state of the backward pass that is running; None outside one"""
+    global _PASS
+    task = torch._C._current_graph_task_id()
+    if task == -1:
+        return None
+    if _PASS is None or _PASS.task != task:
+        # first use in this backward pass.  A state that is still here belongs to a pass that never reached its end-of-pass callback (it raised midway): its
+        # queued products, hand-overs and group counters belong to another batch and must not reach this step's gradients -- dropped as a whole
+        _PASS = _BackwardPass(task)
+        torch.autograd.Variable._execution_engine.queue_callback(_flush_at_end)      # flush whatever is left when the pass ends
+    return _PASS
 
 
 def _in_backward():
@@ -264,83 +345,27 @@ def _in_backward():
 def reset_backward_state():
     """forget everything a backward pass leaves between its nodes (queued parameter-gradient products, hand-over tables, position-group counters): called when a pass
     was aborted (a graph capture that failed midway) before the step is run again"""
-    for q in _DEFER["queues"].values():
-        q.tn, q.ln, q.keep, q.flops, q.cw, q.cw_flops, q.cw64, q.cw64_flops = [], [], [], 0.0, [], 0.0, [], 0.0
-    _DEFER["task"] = -1
-    _PREP_READY["task"], _PREP_READY["m"] = -1, {}
-    _LN2_READY["task"], _LN2_READY["m"] = -1, {}
-    for ent in _POS_CACHE.values():
-        ent[1].de_all, ent[1].remaining = None, ent[1].L
-
-
-def _pending():
-    st = torch.cuda.current_stream()
-    q = _DEFER["queues"].get(st.cuda_stream)
-    if q is None:
-        q = _DEFER["queues"][st.cuda_stream] = _PendingGrads(st)
-    task = torch._C._current_graph_task_id()
-    if _DEFER["task"] != task:                    # first queued item of this backward pass: flush whatever is left when the pass ends
-        if _DEFER["task"] != -1:                  # the previous pass never reached its end-of-pass callback (it raised midway): its queued products
-            for old in _DEFER["queues"].values():  # belong to another batch and must not be added to this step's gradients
-                old.tn, old.ln, old.keep, old.flops, old.cw, old.cw_flops, old.cw64, old.cw64_flops = [], [], [], 0.0, [], 0.0, [], 0.0
-        _DEFER["task"] = task
-        torch.autograd.Variable._execution_engine.queue_callback(_flush_at_end)
-    return q
-
-
-def _launch_pending(q, part=None):
-    """submit queue `q` on the CURRENT stream (its own stream during the pass; the caller's stream, which has joined every branch, at the end of it)"""
-    cur = torch.cuda.current_stream()
-    if cur.cuda_stream != q.stream.cuda_stream:
-        for t in q.keep:
-            t.record_stream(cur)
-    if q.tn and part in (None, "tn"):
-        ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
-        for i in range(0, len(q.tn), TN_GROUP_MAX):
-            chunk = q.tn[i:i + TN_GROUP_MAX]
-            lib.gemm_tn_grouped(BF16, (TnItem * len(chunk))(*chunk), len(chunk), rt.stream())
-        if ev is not None:
-            KERNEL_TIMER.stop(ev, (1, ROWS_PLAIN), q.flops, sum(2.0 * it.M * (it.I + it.J) + 4.0 * it.I * it.J for it in q.tn))      # P, Q once (bf16) + dW once (fp32)
-        q.tn, q.flops = [], 0.0
-    if q.ln and part in (None, "ln"):
-        for i in range(0, len(q.ln), LN_GROUP_MAX):
-            chunk = q.ln[i:i + LN_GROUP_MAX]
-            lib.layernorm_param_grads_grouped(rt.dt(), (LnItem * len(chunk))(*chunk), len(chunk), rt.stream())
-        q.ln = []
-    if q.cw and part in (None, "cw"):
-        ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
-        for i in range(0, len(q.cw), WGRAD_GROUP_MAX):
-            chunk = q.cw[i:i + WGRAD_GROUP_MAX]
-            lib.wgrad3x3_c128_grouped((WgradItem * len(chunk))(*chunk), len(chunk), rt.stream())
-        if ev is not None:
-            KERNEL_TIMER.stop(ev, (2, 2), q.cw_flops, sum(2.0 * 2 * it.images * it.H * it.W * it.C + 4.0 * 9 * it.C * it.C for it in q.cw))      # x, dy once (bf16) + dW once (fp32)
-        q.cw, q.cw_flops = [], 0.0
-    if q.cw64 and part in (None, "cw"):
-        ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
-        for i in range(0, len(q.cw64), WGRAD_GROUP_MAX):
-            chunk = q.cw64[i:i + WGRAD_GROUP_MAX]
-            lib.wgrad3x3_c64_grouped((WgradItem * len(chunk))(*chunk), len(chunk), rt.stream())
-        if ev is not None:
-            KERNEL_TIMER.stop(ev, (2, 2), q.cw64_flops, sum(2.0 * 2 * it.images * it.H * it.W * it.C + 4.0 * 9 * it.C * it.C for it in q.cw64))
-        q.cw64, q.cw64_flops = [], 0.0
-    if not q.tn and not q.ln and not q.cw and not q.cw64:
-        q.keep = []
+    global _PASS
+    _PASS = None
 
 
 def flush_param_grads(all_streams=False):
     """submit the queued parameter-gradient work of the current stream (all_streams: of every stream, on the current one)"""
-    if all_streams:
-        for q in list(_DEFER["queues"].values()):
-            _launch_pending(q)
+    if _PASS is None:
         return
-    q = _DEFER["queues"].get(torch.cuda.current_stream().cuda_stream)
+    if all_streams:
+        for q in list(_PASS.queues.values()):
+            q.flush()
+        return
+    q = _PASS.queues.get(torch.cuda.current_stream().cuda_stream)
     if q is not None:
-        _launch_pending(q)
+        q.flush()
 
 
 def _flush_at_end():
-    _DEFER["task"] = -1
+    global _PASS
     flush_param_grads(all_streams=True)
+    _PASS = None
 
 
 def gemm_tn(P, Q, O, M, I, J, *, ldp=None, q_rows=None, q_mode=ROWS_PLAIN, q_f32=False, ldo=None, dtype=None, p_colsum=None, side=False):
@@ -348,7 +373,7 @@ def gemm_tn(P, Q, O, M, I, J, *, ldp=None, q_rows=None, q_mode=ROWS_PLAIN, q_f32
     side=True (weight gradients): may be queued for a grouped launch (see above) / launched on the side stream (runtime.wgrad_fork)."""
     if q_rows is None:
         q_rows = rows_plain(J)
-    if side and q_mode == ROWS_PLAIN and q_f32 and CAST_DEFER and dtype is None and rt.compute_dtype() == "bf16" and _in_backward() and Q.dim() == 2 and Q.dtype == torch.float32:
+    if side and q_mode == ROWS_PLAIN and q_f32 and dtype is None and rt.compute_dtype() == "bf16" and _in_backward() and Q.dim() == 2 and Q.dtype == torch.float32:
         # fp32 activations (a layer fed by the residual stream): one cast launch, then the product joins the grouped launch like any other -- instead of a
         # launch of its own on the register-staged kernel plus a column-sum / col_finalize pair for its bias (same rounding: that kernel casts while staging)
         Qb = empty((Q.shape[0], J), rt.act_dtype(), Q)
@@ -360,16 +385,8 @@ def gemm_tn(P, Q, O, M, I, J, *, ldp=None, q_rows=None, q_mode=ROWS_PLAIN, q_f32
         it.ldp, it.ldq, it.ldo, it.M, it.I, it.J = (I if ldp is None else ldp), q_rows.ld, (J if ldo is None else ldo), M, I, J
         it.q_rows_out, it.q_rows_in, it.q_step = q_rows.rows_out, q_rows.rows_in, q_rows.step
         if lib.raw("avec_gemm_tn_grouped_ok")(BF16, _byref(it)) and _chunk_readable(P, it.ldp, I, M) and _chunk_readable(Q, it.ldq, J, M):
-            q = _pending()
-            q.tn.append(it)
-            q.keep += [P, Q]
-            q.flops += 2.0 * M * I * J
-            if len(q.tn) >= _TN_FLUSH_AT:
-                _launch_pending(q, "tn")
+            _pass().pending().push("tn", it, [P, Q], 2.0 * M * I * J)
             return
-    if _TN_WHY and side:
-        print("gemm_tn not deferred: M=%d I=%d J=%d q_mode=%d q_f32=%s dtype=%s in_backward=%s P%%16=%d Q%%16=%d ldp=%s ldq=%d step=%d Pdtype=%s Qdtype=%s" % (
-            M, I, J, q_mode, q_f32, dtype, _in_backward(), P.data_ptr() % 16, Q.data_ptr() % 16, ldp, q_rows.ld, q_rows.step, P.dtype, Q.dtype), flush=True)
     ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
     st = rt.stream()
     if side and not KERNEL_TIMER.enabled:
@@ -396,24 +413,18 @@ def layernorm_fwd(x, w, b, M, D, out_f32, eps):
 # (avec_layernorm_bwd_prep).  Forward: a module tags its output tensor with (alpha, drop_p, rng stream); the consumer module remembers the tag of its input.
 # Backward: the consumer's LayerNorm backward produces the prepared gradient and leaves it under dx's address; the producer module takes it if the address, the
 # backward pass, the shape and its own (alpha, drop_p, stream) all match, and launches grad_prep otherwise (gradient accumulated from several consumers, ...).
-PREP_FUSE = True
-_PREP_READY = {"task": -1, "m": {}}
-
-
 def _tag_prep(out, alpha, drop_p, sid):
-    if PREP_FUSE:
-        out._avec_prep = (float(alpha), float(drop_p), int(sid))
+    out._avec_prep = (float(alpha), float(drop_p), int(sid))
     return out
 
 
 def _prep_request(x):
-    return getattr(x, "_avec_prep", None) if PREP_FUSE else None
+    return getattr(x, "_avec_prep", None)
 
 
 def _take_prep(dy, M, N, alpha, drop_p, sid):
-    if _PREP_READY["task"] != torch._C._current_graph_task_id():
-        return None
-    r = _PREP_READY["m"].pop(dy.data_ptr(), None)
+    p = _pass()
+    r = None if p is None else p.prep.pop(dy.data_ptr(), None)
     if r is not None and r[1:] == (M, N, float(alpha), float(drop_p), int(sid)) and r[0].dtype == rt.act_dtype():
         return r[0]
     return None
@@ -425,26 +436,16 @@ def layernorm_bwd(dy, dy_f32, x, mean, rstd, w, b, M, D, dres=None, prep=None):
     gw, gb = grad_of(w), grad_of(b)
     if D <= 1024 and D % 4 == 0 and _in_backward():          # (the dx-only kernel and the grouped launch use 4-wide accesses) dx now (one wave per row); d(gamma), d(beta) with the other queued parameter gradients
         if prep is not None:
-            task = torch._C._current_graph_task_id()
-            if _PREP_READY["task"] != task:
-                _PREP_READY["task"], _PREP_READY["m"] = task, {}
             pt = empty((M, D), rt.act_dtype(), x)
             alpha, drop_p, sid = prep
             rng = rt.rng_state(x.device).data_ptr() if drop_p > 0 else None
             lib.layernorm_bwd_prep(rt.dt(), dy.data_ptr(), int(dy_f32), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), dx.data_ptr(), _p(dres),
                                    pt.data_ptr(), alpha, drop_p, rng, sid, M, D, rt.stream())
-            _PREP_READY["m"][dx.data_ptr()] = (pt, M, D, alpha, drop_p, sid)
+            _pass().prep[dx.data_ptr()] = (pt, M, D, alpha, drop_p, sid)
         else:
             lib.layernorm_bwd(rt.dt(), dy.data_ptr(), int(dy_f32), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), dx.data_ptr(), _p(dres),
                               None, None, M, D, rt.stream())
-        it = LnItem()
-        it.dy, it.x, it.mean, it.rstd, it.dgamma, it.dbeta = dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gw.data_ptr(), gb.data_ptr()
-        it.M, it.D, it.dy_f32 = M, D, int(dy_f32)
-        q = _pending()
-        q.ln.append(it)
-        q.keep += [dy, x, mean, rstd]
-        if len(q.ln) >= LN_GROUP_MAX:
-            _launch_pending(q, "ln")
+        defer_ln_param_grads(dy, dy_f32, x, mean, rstd, w, b, M, D)
         return dx
     lib.layernorm_bwd(rt.dt(), dy.data_ptr(), int(dy_f32), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), dx.data_ptr(), _p(dres),
                       gw.data_ptr(), gb.data_ptr(), M, D, rt.stream())
@@ -455,20 +456,15 @@ def layernorm_bwd_pair(dy2, x2, mean2, rstd2, w2, b2, dres2, x1, mean1, rstd1, w
     """LayerNorm backward of a module's pre-norm (dy2: act, residual gradient dres2) AND of the LayerNorm that produced its input (LayerNormFn ctx1; req1 = the prepared
     gradient wanted by the module in front of that one): one launch; returns dx2 and leaves dx1 for LayerNormFn.backward (see LN_PAIR)"""
     dx2, dx1 = empty((M, D), torch.float32, x2), empty((M, D), torch.float32, x2)
-    task = torch._C._current_graph_task_id()
     pt, alpha, drop_p, sid = None, 1.0, 0.0, 0
     if req1 is not None:
-        if _PREP_READY["task"] != task:
-            _PREP_READY["task"], _PREP_READY["m"] = task, {}
         pt = empty((M, D), rt.act_dtype(), x2)
         alpha, drop_p, sid = req1
-        _PREP_READY["m"][dx1.data_ptr()] = (pt, M, D, alpha, drop_p, sid)
+        _pass().prep[dx1.data_ptr()] = (pt, M, D, alpha, drop_p, sid)
     rng = rt.rng_state(x2.device).data_ptr() if (pt is not None and drop_p > 0) else None
     lib.layernorm_bwd2(rt.dt(), dy2.data_ptr(), x2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr(), w2.data_ptr(), dres2.data_ptr(), dx2.data_ptr(),
                        x1.data_ptr(), mean1.data_ptr(), rstd1.data_ptr(), w1.data_ptr(), dx1.data_ptr(), _p(pt), alpha, drop_p, rng, sid, M, D, rt.stream())
-    if _LN2_READY["task"] != task:
-        _LN2_READY["task"], _LN2_READY["m"] = task, {}
-    _LN2_READY["m"][dx2.data_ptr()] = (dx1, ctx1, dx2, dx2._version)
+    _pass().ln2[dx2.data_ptr()] = (dx1, ctx1, dx2, dx2._version)
     defer_ln_param_grads(dy2, False, x2, mean2, rstd2, w2, b2, M, D)
     return dx2
 
@@ -565,7 +561,6 @@ def linear(x, weight, bias, out_f32=True):
 # parameters and eps are the ones it was made for.  Backward: the feed-forward module's LayerNorm backward also runs the closing norm's (avec_layernorm_bwd2) and
 # leaves dx1 under the address of the gradient it returns; LayerNormFn.backward takes it if that very tensor comes back from autograd (one consumer), else computes.
 LN_PAIR = True
-_LN2_READY = {"task": -1, "m": {}}
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -596,8 +591,9 @@ class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, mean, rstd, w, b, M, D, shp, req = ctx.saved
-        if _LN2_READY["task"] == torch._C._current_graph_task_id():
-            r = _LN2_READY["m"].pop(dy.data_ptr(), None)
+        p = _pass()
+        if p is not None:
+            r = p.ln2.pop(dy.data_ptr(), None)
             # the feed-forward module behind has done this LayerNorm's backward already -- valid only if dy still IS its dx2 (same storage, not accumulated into since:
             # a second consumer of this norm's output makes autograd add its gradient in place, which bumps the version counter)
             if r is not None and r[1] is ctx and dy.dtype == torch.float32 and dy.is_contiguous() and (dy is r[2] or dy._base is r[2]) and r[2]._version == r[3]:
@@ -661,11 +657,7 @@ def defer_ln_param_grads(dy, dy_f32, x, mean, rstd, w, b, M, D):
     it.dy, it.x, it.mean, it.rstd, it.dgamma, it.dbeta = dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), grad_of(w).data_ptr(), grad_of(b).data_ptr()
     it.M, it.D, it.dy_f32 = M, D, int(dy_f32)
     if _in_backward() and D % 4 == 0 and D <= 1024:
-        q = _pending()
-        q.ln.append(it)
-        q.keep += [dy, x, mean, rstd]
-        if len(q.ln) >= LN_GROUP_MAX:
-            _launch_pending(q, "ln")
+        _pass().pending().push("ln", it, [dy, x, mean, rstd])
     else:
         lib.layernorm_param_grads_grouped(rt.dt(), (LnItem * 1)(it), 1, rt.stream())
 
@@ -755,17 +747,16 @@ def _attn_args(qkv, e, lens, len_div, mask, o, lse, B, H, T, d, D, q_full=0):
 # ONE product PE [2T-1][D] x W_all^T [D][L D] gives every block's E as a column slice, and in backward the L gradients dE_l accumulate in one [2T-1][L D] buffer that
 # takes ONE cast and ONE weight-gradient product when the last of them has arrived: 2 (L - 1) launches less per stage and pass.  Versioned by the arena's shadow
 # refresh counter (E follows the weights), per sequence length.
-POS_GROUP = True
 _POS_CACHE = {}
 
 
 class _PosGroupEntry:
-    __slots__ = ("e_all", "pe", "de_all", "remaining", "L", "D", "Tp")
+    __slots__ = ("e_all", "pe", "L", "D", "Tp")
 
 
 def _pos_group_entry(wp, Tp, D, device):
     """-> (entry, index of this layer inside its group) or (None, 0)"""
-    if not POS_GROUP or rt.compute_dtype() != "bf16":
+    if rt.compute_dtype() != "bf16":
         return None, 0
     grp = rt.fused_group(wp)
     if grp is None or len(grp.weights) < 2 or fp8.enabled():
@@ -783,27 +774,25 @@ def _pos_group_entry(wp, Tp, D, device):
         e.L, e.D, e.Tp, e.pe = L, D, Tp, rel_pos_table(Tp, D, device)
         e.e_all = empty((2 * Tp - 1, L * D), rt.act_dtype(), e.pe)
         gemm_nt(e.pe, grp.fwd, e.e_all, 2 * Tp - 1, L * D, D, bias=grp.bias)
-        e.de_all, e.remaining = None, L
         _POS_CACHE[key] = ent = (ver, e, grp)
         if len(_POS_CACHE) > 64:
             for k in list(_POS_CACHE)[:32]:
                 _POS_CACHE.pop(k, None)
-    if ent[1].remaining != ent[1].L or ent[1].de_all is not None:      # a backward pass that raised midway left its counters behind: a forward pass starts clean
-        ent[1].de_all, ent[1].remaining = None, ent[1].L
     return ent[1], idx
 
 
 def _pos_group_backward(entry, wp):
     """one layer of the group has accumulated its dE: when all have, cast once and queue ONE weight-gradient product for the whole group"""
-    entry.remaining -= 1
-    if entry.remaining > 0:
+    acc = _pass().pos[entry]
+    acc[1] -= 1
+    if acc[1] > 0:
         return
+    de_all = _pass().pos.pop(entry)[0]
     grp = rt.fused_group(wp)
     R, W = 2 * entry.Tp - 1, entry.L * entry.D
-    dea = empty((R, W), rt.act_dtype(), entry.de_all)
-    lib.cast_rows(rt.dt(), entry.de_all.data_ptr(), W, dea.data_ptr(), W, R, W, rt.stream())
+    dea = empty((R, W), rt.act_dtype(), de_all)
+    lib.cast_rows(rt.dt(), de_all.data_ptr(), W, dea.data_ptr(), W, R, W, rt.stream())
     gemm_tn(dea, entry.pe, grp.wgrad, R, W, entry.D, p_colsum=grp.bgrad, side=True)
-    entry.de_all, entry.remaining = None, entry.L
 
 
 class AttentionModuleFn(torch.autograd.Function):
@@ -891,9 +880,10 @@ class AttentionModuleFn(torch.autograd.Function):
         dqkv = empty((Mp, 3 * D), adt, dy)
         pg, pgi = ctx.pos_group
         if pg is not None:
-            if pg.de_all is None:                    # first layer of the group to reach its backward: the shared [2T-1][L D] accumulator (pre-zeroed pool)
-                pg.de_all = rt.zeros_scratch((2 * Tp - 1) * pg.L * D, dy.device).view(2 * Tp - 1, pg.L * D)
-            de = pg.de_all[:, pgi * D:(pgi + 1) * D]
+            acc = _pass().pos.get(pg)
+            if acc is None:                          # first layer of the group to reach its backward: the shared [2T-1][L D] accumulator (pre-zeroed pool)
+                acc = _pass().pos[pg] = [rt.zeros_scratch((2 * Tp - 1) * pg.L * D, dy.device).view(2 * Tp - 1, pg.L * D), pg.L]
+            de = acc[0][:, pgi * D:(pgi + 1) * D]
         else:
             de = rt.zeros_scratch((2 * Tp - 1) * D, dy.device).view(2 * Tp - 1, D)      # pre-zeroed pool: no fill launch per layer (-0.15 ms per step)
         a = _attn_args(qkv, e, lens, patch, mask, o, lse, B, H, Tp, d, D, T // patch if (patch > 1 and mask is None) else 0)
@@ -1510,31 +1500,21 @@ def conv2d_bwd(dy, x, weight, N, H, W, Cin, stride, OH, OW, need_dx=True, dx_res
     pad = (KH - 1) // 2
     M = N * OH * OW
     sh = rt.shadow(weight)
-    if _slab_conv(H, W, Cin, Cout, KH, KW, stride) and H * (W + 1) <= 512:
+    slab64 = _slab_conv(H, W, Cin, Cout, KH, KW, stride) and H * (W + 1) <= 512
+    wide = (not slab64 and SLAB_CONV and SLAB_WGRAD128 and rt.act_dtype() == torch.bfloat16 and
+            bool(lib.raw("avec_wgrad3x3_c128_supported")(H, W, Cin, Cout, KH, KW, stride)))
+    if slab64 or wide:
         if GROUP_WGRAD128 and _in_backward():
+            # queued: one grouped launch for all the layers of a kind when the backward pass is through (the final atomics of a launch of its own are ~30 % of it)
             it = WgradItem()
             it.x, it.dy, it.dw, it.images, it.C, it.H, it.W = x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, Cin, H, W
-            q = _pending()
-            q.cw64.append(it)
-            q.keep += [x, dy]
-            q.cw64_flops += 2.0 * M * Cout * KH * KW * Cin
+            _pass().pending().push("cw64" if slab64 else "cw", it, [x, dy], 2.0 * M * Cout * KH * KW * Cin)
         else:
             ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
-            lib.wgrad3x3_c64(x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, H, W, rt.stream())
-            if ev is not None:
-                KERNEL_TIMER.stop(ev, (2, 2), 2.0 * M * Cout * KH * KW * Cin)
-    elif SLAB_CONV and SLAB_WGRAD128 and rt.act_dtype() == torch.bfloat16 and bool(lib.raw("avec_wgrad3x3_c128_supported")(H, W, Cin, Cout, KH, KW, stride)):
-        if GROUP_WGRAD128 and _in_backward():
-            # queued: one grouped launch for all the wide layers when the backward pass is through (the final atomics of a launch of its own are ~30 % of it)
-            it = WgradItem()
-            it.x, it.dy, it.dw, it.images, it.C, it.H, it.W = x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, Cin, H, W
-            q = _pending()
-            q.cw.append(it)
-            q.keep += [x, dy]
-            q.cw_flops += 2.0 * M * Cout * KH * KW * Cin
-        else:
-            ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
-            lib.wgrad3x3_c128(x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, Cin, H, W, rt.stream())
+            if slab64:
+                lib.wgrad3x3_c64(x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, H, W, rt.stream())
+            else:
+                lib.wgrad3x3_c128(x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, Cin, H, W, rt.stream())
             if ev is not None:
                 KERNEL_TIMER.stop(ev, (2, 2), 2.0 * M * Cout * KH * KW * Cin)
     else:
@@ -1577,8 +1557,8 @@ class ResNetBlockFn(torch.autograd.Function):
 
     # BatchNorm-backward fusion across blocks: a block whose output feeds ONLY the next block (chain=True, set by nnet.ResNet) registers (y2, out, ss2) under its
     # output's address; the next block's backward folds the mask + (sum d, sum d*y2) reduction of that BatchNorm into the epilogue of the product that computes its
-    # input gradient and leaves the completed request under the gradient's address for the producer block's backward
-    _CHAIN, _READY = {}, {}
+    # input gradient and leaves the completed request under the gradient's address (in the pass state) for the producer block's backward
+    _CHAIN = {}
 
     @staticmethod
     def forward(ctx, x, _anchor, blk, training, chain=False):
@@ -1636,7 +1616,7 @@ class ResNetBlockFn(torch.autograd.Function):
         dout = dout.reshape(Mo, Cout).to(rt.act_dtype()).contiguous()
         assert training, "ResNetBlock backward is implemented for training-mode BatchNorm"
         ResNetBlockFn._CHAIN.pop(out.data_ptr(), None)
-        pre2 = ResNetBlockFn._READY.pop(dout.data_ptr(), None) if ctx.chain else None      # the consumer block already masked dout and reduced it against y2
+        pre2 = _pass().bn_ready.pop(dout.data_ptr(), None) if ctx.chain else None      # the consumer block already masked dout and reduced it against y2
         if pre2 is not None and pre2.y is not y2:
             raise RuntimeError("ResNetBlock backward: a fused BatchNorm-backward request does not belong to this block (the block output has another consumer?)")
         # the gradient that passed the block's final ReLU is needed twice more (second BatchNorm's backward above all, then as the residual branch's gradient): with the bit
@@ -1674,9 +1654,7 @@ class ResNetBlockFn(torch.autograd.Function):
             else:
                 dx = conv2d_bwd(dy1, x, conv1.weight, N, H, W, Cin, stride, OH, OW, need_dx=need_dx, dx_res=dres, bnb=fx)
         if fx is not None and fx.done:
-            if len(ResNetBlockFn._READY) > 64:
-                ResNetBlockFn._READY.clear()
-            ResNetBlockFn._READY[dx.data_ptr()] = fx
+            _pass().bn_ready[dx.data_ptr()] = fx
         return (dx.view(N, H, W, Cin) if dx is not None else None), None, None, None, None
 
 

@@ -1,4 +1,4 @@
-# experiment: ablated variants of the 64-channel weight gradient (C3W_ABL bits: 1 no MFMA, 2 no LDS-DMA, 4 no fragment reads, 8 no atomics) -> tools/_bin/libavec_c3wabl_<n>.so
+# experiment: instrumented variants of the 64-channel weight gradient (C3W_ABL bit 64: in-kernel cycle counters, read back with avec_c3w_debug) -> tools/_bin/libavec_c3wabl_<n>.so
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/_bin
