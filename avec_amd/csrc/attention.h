@@ -1,4 +1,8 @@
 // Shared argument block of the relative-position attention kernels (attention.hip: fp32 VALU kernels; attention_mfma.hip: bf16 MFMA kernels).
+// Precondition on q / k / v / e / dout: whatever lies between the end of a head's d channels and the end of the 16-channel group it ends in, INSIDE the tensor -- the
+// next head, the next tensor of a fused q | k | v row, a row-stride gap -- must be finite.  The MFMA kernels stage whole 16-byte chunks: those elements land in the
+// K / V / E pad channels, where they meet the zeroed pad channels of Q / dO (0 * NaN = NaN).  Only the one chunk that would run past the END of a tensor is replaced
+// by zeros + element loads, so nothing after a tensor's last row is read.  The VALU kernels read the d channels only.  tests/test_gpu_attention.py.
 #pragma once
 #include "common.h"
 #include "avec_hip.h"

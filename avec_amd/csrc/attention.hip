@@ -10,6 +10,7 @@
 //   bwd1 : dQ, same tiling as fwd
 //   bwd2 : dK, dV, dE; grid (key tiles, B*H, query segments of 64), lanes = keys, register accumulators
 #include "attention.h"
+#include <stdio.h>
 
 static constexpr int TQ = 32;    // query rows per workgroup (fwd / bwd1): 4 waves x RPW rows
 static constexpr int RPW = TQ / 4;
@@ -257,6 +258,7 @@ extern "C" int avec_relpos_attention_fwd(int dtype, const avec_attn_t* p, hipStr
   if (dtype == AVEC_BF16) { const int r = attn_mfma_fwd(a, st); if (r != 1) return r; }      // MFMA path; 1 = not applicable, fall through
   const int DP = a.d | 1; size_t lds = (size_t)(2 * TK + (TQ + TK - 1) + TQ) * DP * 4 + 4 * 64 * 4;
   dim3 grid((a.T + TQ - 1) / TQ, a.B * a.H);
+  avec_note_kernel("attn_rows<%s,fwd>", dtype == AVEC_BF16 ? "bf16" : "f32");
   if (dtype == AVEC_BF16) { if (int r = avec_lds_optin(attn_rows_kernel<bf16, false>, lds)) return r; hipLaunchKernelGGL((attn_rows_kernel<bf16, false>), grid, dim3(256), lds, st, a); }
   else { if (int r = avec_lds_optin(attn_rows_kernel<float, false>, lds)) return r; hipLaunchKernelGGL((attn_rows_kernel<float, false>), grid, dim3(256), lds, st, a); }
   AVEC_LAUNCH_CHECK(); return 0;
@@ -267,17 +269,21 @@ template <typename T> static int launch_bwd(AttnArgs& a, hipStream_t st) {
   size_t lds1 = (size_t)(2 * TK + (TQ + TK - 1) + 2 * TQ) * DP * 4 + 4 * 64 * 4;
   dim3 grid1((a.T + TQ - 1) / TQ, a.B * a.H);
   bool rows_done = false;
+  const bool cols = !(a.dsrel || a.Tk != a.T);     // (Tk != T: key/value cache attached -- only the probability / dQ row pass is defined)  with dsrel, dK/dV/dE are computed by the caller with avec_gemm_tn_batched on P / dS / dSrel (MFMA path)
+  AVEC_CHECK_ARG(!cols || a.d <= 96, "attention_bwd: the register-accumulating column pass serves d <= 96 (d=%d): pass dsrel and use avec_gemm_tn_batched", a.d);      // before the row pass: a rejected call launches nothing
   if (sizeof(T) == 2) { const int r = attn_mfma_bwd_rows(a, st); if (r == 0) rows_done = true; else if (r != 1) return r; }   // bf16 MFMA row pass
   if (!rows_done) {
     if (int r = avec_lds_optin(attn_rows_kernel<T, true>, lds1)) return r;
+    avec_note_kernel("attn_rows<%s,bwd>", sizeof(T) == 2 ? "bf16" : "f32");
     hipLaunchKernelGGL((attn_rows_kernel<T, true>), grid1, dim3(256), lds1, st, a);
   }
-  if (a.dsrel || a.Tk != a.T) return 0;            // (Tk != T: key/value cache attached -- only the probability / dQ row pass is defined)  dK/dV/dE are computed by the caller with avec_gemm_tn_batched on P / dS / dSrel (MFMA path)
+  if (!cols) return 0;
   size_t lds2 = (size_t)(2 * QC + 2 * 64) * DP * 4;
   const int ktiles = (a.T + 63) / 64, rtiles = (2 * a.T - 1 + 63) / 64;
   dim3 grid2(ktiles + rtiles, a.B * a.H);
-#define LB(DPAD) do { if (int r = avec_lds_optin(attn_bwd_cols_kernel<T, DPAD>, lds2)) return r; hipLaunchKernelGGL((attn_bwd_cols_kernel<T, DPAD>), grid2, dim3(256), lds2, st, a, ktiles); } while (0)
-  AVEC_CHECK_ARG(a.d <= 96, "attention_bwd: the register-accumulating column pass serves d <= 96 (d=%d): pass dsrel and use avec_gemm_tn_batched", a.d);
+  // the row pass's name + the column pass's: attn_rows<f32,bwd>+cols<96>, attn_mfma_bwd<128,7,0,4>+cols<64>
+#define LB(DPAD) do { char rows_[96]; snprintf(rows_, sizeof(rows_), "%s", avec_last_kernel()); avec_note_kernel("%s+cols<%d>", rows_, DPAD); \
+    if (int r = avec_lds_optin(attn_bwd_cols_kernel<T, DPAD>, lds2)) return r; hipLaunchKernelGGL((attn_bwd_cols_kernel<T, DPAD>), grid2, dim3(256), lds2, st, a, ktiles); } while (0)
   if (a.d <= 48) LB(48); else if (a.d <= 64) LB(64); else LB(96);
 #undef LB
   return 0;

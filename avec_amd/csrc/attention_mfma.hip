@@ -536,32 +536,38 @@ __global__ __launch_bounds__(ALIAS ? 128 : 256) void attn_mfma_bwd_kernel(AttnAr
 }
 
 static const bool g_mfma_off = getenv("AVEC_NO_MFMA_ATTN") != nullptr;
+// stage_rows_dma replaces the one chunk that runs past the end of a tensor in its LAST row.  A row stride below the head's padding (ld + d < dpad: rows of fewer than 15
+// elements) lets the chunks of the rows before it run past the end as well: such tensors go to the VALU kernels, which read the d channels only.
+static bool rows_too_short(long long ld, int d) { return ld + d < (d + 15) / 16 * 16; }
 
 int attn_mfma_fwd(const AttnArgs& a, hipStream_t st) {
-  if (g_mfma_off || a.mask || a.d > 96 || a.T > 32 * NTMAX || a.Tk != a.T) return 1;
+  if (g_mfma_off || a.mask || a.d > 96 || a.T > 32 * NTMAX || a.Tk != a.T || rows_too_short(a.ld, a.d) || rows_too_short(a.lde, a.d)) return 1;
   const int pitch = a.d <= 64 ? 128 : 256;
   const MfmaGeom G = mfma_geom(a.T, a.d, pitch, false);
   if (G.total > 160 * 1024) return 1;
   dim3 grid((a.T + 63) / 64, a.B * a.H);
-#define AVEC_LAUNCH_ATTN(KERNEL) do { if (int r = avec_lds_optin(KERNEL, G.total)) return r; hipLaunchKernelGGL(KERNEL, grid, dim3(G.alias ? 128 : 256), G.total, st, a, G); } while (0)
-#define AVEC_PICK_DKS(NAME, N, A) do { \
-    if (pitch == 128) { if (G.DKS == 4) AVEC_LAUNCH_ATTN((NAME<128, N, A, 4>)); else if (G.DKS == 3) AVEC_LAUNCH_ATTN((NAME<128, N, A, 3>)); else AVEC_LAUNCH_ATTN((NAME<128, N, A, 0>)); } \
-    else { if (G.DKS == 6) AVEC_LAUNCH_ATTN((NAME<256, N, A, 6>)); else AVEC_LAUNCH_ATTN((NAME<256, N, A, 0>)); } } while (0)
-#define AVEC_PICK_ATTN(NAME) do { \
-    if (a.T <= 224 && !G.alias) AVEC_PICK_DKS(NAME, 7, false); \
-    else if (!G.alias) AVEC_PICK_DKS(NAME, 12, false); \
-    else AVEC_PICK_DKS(NAME, 12, true); } while (0)
-  AVEC_PICK_ATTN(attn_mfma_fwd_kernel);
+// the instance is noted for avec_last_kernel as TAG<PITCH,NTM,ALIAS,DKS>, e.g. attn_mfma_fwd<128,7,0,4>
+#define AVEC_LAUNCH_ATTN(TAG, NAME, P, N, A, K) do { avec_note_kernel(TAG "<%d,%d,%d,%d>", P, N, (int)A, K); if (int r = avec_lds_optin(NAME<P, N, A, K>, G.total)) return r; \
+    hipLaunchKernelGGL((NAME<P, N, A, K>), grid, dim3(G.alias ? 128 : 256), G.total, st, a, G); } while (0)
+#define AVEC_PICK_DKS(TAG, NAME, N, A) do { \
+    if (pitch == 128) { if (G.DKS == 4) AVEC_LAUNCH_ATTN(TAG, NAME, 128, N, A, 4); else if (G.DKS == 3) AVEC_LAUNCH_ATTN(TAG, NAME, 128, N, A, 3); else AVEC_LAUNCH_ATTN(TAG, NAME, 128, N, A, 0); } \
+    else { if (G.DKS == 6) AVEC_LAUNCH_ATTN(TAG, NAME, 256, N, A, 6); else AVEC_LAUNCH_ATTN(TAG, NAME, 256, N, A, 0); } } while (0)
+#define AVEC_PICK_ATTN(TAG, NAME) do { \
+    if (a.T <= 224 && !G.alias) AVEC_PICK_DKS(TAG, NAME, 7, false); \
+    else if (!G.alias) AVEC_PICK_DKS(TAG, NAME, 12, false); \
+    else AVEC_PICK_DKS(TAG, NAME, 12, true); } while (0)
+  AVEC_PICK_ATTN("attn_mfma_fwd", attn_mfma_fwd_kernel);
   AVEC_LAUNCH_CHECK(); return 0;
 }
 
 int attn_mfma_bwd_rows(const AttnArgs& a, hipStream_t st) {
-  if (g_mfma_off || a.mask || a.d > 96 || a.T > 32 * NTMAX || a.Tk != a.T || !a.pbuf || !a.dsbuf || !a.dq || !a.dout) return 1;
+  if (g_mfma_off || a.mask || a.d > 96 || a.T > 32 * NTMAX || a.Tk != a.T || !a.pbuf || !a.dsbuf || !a.dq || !a.dout || rows_too_short(a.ld, a.d) || rows_too_short(a.lde, a.d) ||
+      rows_too_short(a.ldo, a.d)) return 1;
   const int pitch = a.d <= 64 ? 128 : 256;
   const MfmaGeom G = mfma_geom(a.T, a.d, pitch, true);
   if (G.total > 160 * 1024) return 1;
   dim3 grid((a.T + 63) / 64, a.B * a.H);
-  AVEC_PICK_ATTN(attn_mfma_bwd_kernel);
+  AVEC_PICK_ATTN("attn_mfma_bwd", attn_mfma_bwd_kernel);
 #undef AVEC_PICK_ATTN
 #undef AVEC_PICK_DKS
 #undef AVEC_LAUNCH_ATTN
