@@ -451,6 +451,33 @@ extern "C" int avec_adam_step(float* params, float* grads, float* exp_avg, float
 }
 
 // ---------------------------------------------------------------------------------------------
+// Weight averaging over the flat fp32 arenas (checkpoint averaging of Model.swa, the EMA model of Model.set_ema).
+//   mode 0: avg = p      mode 1: avg = avg + wp * (p - avg)      mode 2: avg = (wa * avg) + (wp * p)
+// Every product, difference and sum is ONE correctly rounded fp32 operation: contraction is switched off for this kernel's own expressions (hipcc contracts by
+// default; HIP's __fmul_rn / __fadd_rn are inline operators from a header compiled WITH contraction, so they would be fused all the same), so the result is a pure function of the inputs and equals the same lines written with
+// torch fp32 tensors bit for bit.  Memory bound either way: three arena-sized streams.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void weight_average_kernel(float* __restrict__ avg, const float* __restrict__ p, int mode, float wa, float wp, long long n4) {
+#pragma clang fp contract(off)
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    float pp[4], aa[4]; ld4<float>(p + i * 4, pp);
+    if (mode == 0) { st4<float>(avg + i * 4, pp); continue; }
+    ld4<float>(avg + i * 4, aa);
+    if (mode == 1) { for (int e = 0; e < 4; ++e) { const float d = pp[e] - aa[e]; const float w = wp * d; aa[e] = aa[e] + w; } }
+    else           { for (int e = 0; e < 4; ++e) { const float a = wa * aa[e]; const float b = wp * pp[e]; aa[e] = a + b; } }
+    st4<float>(avg + i * 4, aa);
+  }
+}
+extern "C" int avec_weight_average(float* avg, const float* p, int mode, float wa, float wp, long long n, hipStream_t st) {
+  AVEC_CHECK_ARG(avg && p && n > 0 && n % 4 == 0, "weight_average: bad arguments (n=%lld must be a positive multiple of 4)", n);
+  AVEC_CHECK_ARG(mode >= 0 && mode <= 2, "weight_average: mode %d (0: copy, 1: equal, 2: weighted sum)", mode);
+  AVEC_CHECK_ARG((const float*)avg + n <= p || p + n <= (const float*)avg, "weight_average: avg and p overlap");
+  long long n4 = n / 4; long long nb = (n4 + 255) / 256; if (nb > 8192) nb = 8192;
+  hipLaunchKernelGGL(weight_average_kernel, dim3((unsigned)nb), dim3(256), 0, st, avg, p, mode, wa, wp, n4);
+  AVEC_LAUNCH_CHECK(); return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // shadow refresh: for every GEMM weight (master fp32, logical [A][Tm][C]) write
 //   fwd shadow  (act) = same order                         -> NT forward   (rows = A, K = Tm*C)
 //   bwd shadow  (act) [C][Tm][A] (axes 0 and 2 swapped)    -> NT backward-data (rows = C, K = Tm*A)

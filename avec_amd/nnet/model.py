@@ -2,6 +2,8 @@
 the forward/backward are fused HIP sequences, the optimizer is one launch over the flat arena, and data parallelism is one process per
 GPU exchanging the flat gradient buffer (and BatchNorm statistics) over RCCL -- no DistributedDataParallel wrapper, no per-step buffer
 broadcast."""
+import copy
+import glob
 import os
 import time
 
@@ -49,6 +51,9 @@ class Model(Module):
                 self.register_forward_pre_hook(Model._pre_forward)
             if self.compiled and hasattr(self.optimizer, "attach_arena"):
                 self.optimizer.attach_arena(self.arena)
+        if self.ema_model is not None:
+            self.ema_model.to(device)
+            self._check_ema_layout()
         return out
 
     def cuda(self, device=None):
@@ -85,6 +90,72 @@ class Model(Module):
     def parallel_strategy(self):
         raise RuntimeError("single-process DataParallel is a legacy path of the reference (nnet/model.py:67-69); use one process per GPU")
 
+    # -- exponential moving average of the weights (nnet/model.py:71-78, 401-407) --------------------
+    def set_ema(self, ema_tau):
+        """Keep an evaluation copy of the model whose parameters follow  ema = tau * ema + (1 - tau) * model  after every optimizer step (one
+        ops.weight_average launch over the two flat arenas, inside the captured step when there is one).  Works before and after .to('cuda') / compile().
+        The copy lives outside the module tree (no state_dict keys), has its OWN ParamArena laid out like the model's, and no optimizer.  Its buffers are
+        the model's as of the last sync_ema_buffers() (save, fit's evaluation and this call do it); the reference copies them after every step, which is
+        the same observable state."""
+        # what must not be cloned: the arena (the copy gets its own), the optimizer and its moments, captured graphs, an earlier EMA model.  What is shared,
+        # as the reference's build() shares it: losses, loss weights, decoders, metrics, and the step counter the loss-weight schedules read
+        memo = {}
+        for name in ("arena", "optimizer", "ema_model", "_graph_cache"):
+            if self.__dict__.get(name) is not None:
+                memo[id(self.__dict__[name])] = None
+        for name in ("compiled_losses", "compiled_loss_weights", "compiled_metrics", "compiled_decoders", "losses", "loss_weights", "decoders", "metrics", "model_step"):
+            if self.__dict__.get(name) is not None:
+                memo[id(self.__dict__[name])] = self.__dict__[name]
+        ema = copy.deepcopy(self, memo)
+        src = dict(self.named_parameters())
+        for name, q in ema.named_parameters():
+            # a copied Parameter is a dense tensor of its own (not a view into this model's arena) without the attributes of the original: the GEMM weights
+            # need their shadow descriptors again before an arena can be built over them
+            sh = getattr(src[name], "_avec_shadow", None)
+            if sh is not None:
+                rt.register_weight(q, sh.A, sh.Tm, sh.C, sh.need_bwd, sh.Cp)
+        for m in ema.modules():
+            m._load_state_dict_post_hooks.clear()       # (the copied hooks mark THIS model's arena stale; the copy's arena registers its own)
+        ema.__dict__.pop("_graph_evictions", None)
+        ema.requires_grad_(False)
+        ema.eval()
+        if self.arena is not None:
+            ema.to(self.device)
+        object.__setattr__(self, "ema_model", ema)
+        self.ema_tau = float(ema_tau)
+        self.__dict__.pop("_graph_cache", None)          # steps captured so far have no EMA launch in them
+        self._check_ema_layout()
+
+    def _check_ema_layout(self):
+        a, b = self.arena, self.ema_model.arena
+        assert (a is None) == (b is None), "the EMA model must live where the model lives"
+        if a is None:
+            return
+        assert b is not a and b.master.data_ptr() != a.master.data_ptr(), "the EMA model needs a parameter arena of its own"
+        na, nb = {id(p): k for k, p in self.named_parameters()}, {id(p): k for k, p in self.ema_model.named_parameters()}
+        assert a.numel == b.numel and a.offsets == b.offsets and len(a.params) == len(b.params) and \
+            all(na[id(p)] == nb[id(q)] and p.shape == q.shape and p.stride() == q.stride() for p, q in zip(a.params, b.params)), \
+            "the EMA model's arena is not laid out like the model's"
+
+    def _update_ema(self):
+        """after the optimizer launch: ema = tau * ema + (1 - tau) * model over the flat arenas -- one launch, no host synchronisation, graph-capturable"""
+        ema = self.ema_model
+        if ema is None:
+            return
+        if self.arena is None:
+            raise RuntimeError("the EMA update runs on the flat parameter arenas on the GPU: move the model with Model.to('cuda') first")
+        ops.weight_average(ema.arena.master, self.arena.master, 2, self.ema_tau, 1.0 - self.ema_tau)
+        ema.arena.mark_dirty()
+
+    @torch.no_grad()
+    def sync_ema_buffers(self):
+        """the EMA model's buffers (BatchNorm running statistics, num_batches_tracked) become the model's.  The reference copies them after every step
+        (nnet/model.py:406-407); the copy is idempotent, so it is made where its result can be observed: before the EMA model is evaluated, saved or used."""
+        if self.ema_model is not None:
+            for target, buf in zip(self.ema_model.buffers(), self.buffers()):
+                target.copy_(buf)
+        return self.ema_model
+
     # -- compile / build (nnet/model.py:80-225) --------------------------------------------------
     def compile(self, losses, loss_weights=None, optimizer="Adam", metrics=None, decoders=None):
         self.optimizer = optim_dict[optimizer](params=self.parameters()) if isinstance(optimizer, str) else optimizer
@@ -113,6 +184,9 @@ class Model(Module):
         self.decoders = self.map_to_outputs(outputs, self.compiled_decoders)
         self.metrics = self.map_to_outputs(outputs, self.compiled_metrics)
         self.built = True
+        if self.ema_model is not None:          # nnet/model.py:158-164
+            ema = self.ema_model
+            ema.losses, ema.loss_weights, ema.decoders, ema.metrics, ema.built = self.losses, self.loss_weights, self.decoders, self.metrics, True
 
     def map_to_outputs(self, outputs, struct):
         """dict -> fill missing keys with None; list -> positional over the output order; single item -> every output."""
@@ -218,6 +292,7 @@ class Model(Module):
         if self.grad_max_norm is not None:
             self.add_info("grad_norm", self.clip_gradients(self.grad_max_norm))
         self.optimizer.step()
+        self._update_ema()
         self.optimizer.zero_grad()
         self.add_info("lr", float(self.optimizer.param_groups[0]["lr"]))
         self.add_info("step", int(self.model_step))
@@ -263,11 +338,13 @@ class Model(Module):
             rt.advance_rng(self.device)
             if not dist_mode:
                 self.optimizer.launch_step()
+                self._update_ema()
             elif state["in_graph"]:
                 self.arena._sync_collectives = True
                 self.arena.all_reduce_grads()
                 self.optimizer.grad_scale = 1.0 / self.world_size
                 self.optimizer.launch_step()
+                self._update_ema()
             return losses
 
         def finish():                                       # data parallel without captured collectives: average the gradients, then the optimizer launch
@@ -275,6 +352,7 @@ class Model(Module):
                 self.arena.all_reduce_grads()
                 self.optimizer.grad_scale = 1.0 / self.world_size
                 self.optimizer.launch_step()
+                self._update_ema()
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -339,6 +417,8 @@ class Model(Module):
             self.optimizer.prepare_step()
             graph.replay()
             finish()
+            if self.ema_model is not None:
+                self.ema_model.arena.mark_dirty()   # (the captured EMA launch rewrote its masters as well)
             if not dist_mode or state["in_graph"]:
                 self.arena.mark_dirty()             # host-side view of what the replay's closing Adam launch left behind: whatever runs next OUTSIDE the graph
             return static_losses                    # (evaluation, an eager step) must refresh the weight shadows first -- the captured refresh sits at the START of a replay
@@ -426,7 +506,7 @@ class Model(Module):
                 peer.active().check()            # (synchronises) a SyncBatchNorm exchange that lost a rank since the last check: raise instead of writing a checkpoint of skipped steps
         torch.save({"model_state_dict": self.state_dict(), "optimizer_state_dict": self.optimizer.state_dict() if save_optimizer else None,
                     "model_step": self.model_step, "is_distributed": self.is_distributed or self.is_parallel,
-                    "ema_model_state_dict": None, "grad_scaler_state_dict": None}, path)
+                    "ema_model_state_dict": None if self.ema_model is None else self.sync_ema_buffers().state_dict(), "grad_scaler_state_dict": None}, path)
 
     def load(self, path, load_optimizer=True, verbose=True, strict=True):
         ckpt = torch.load(path, map_location=self.device, weights_only=False)
@@ -439,6 +519,85 @@ class Model(Module):
             # fine-tuning from a checkpoint without its optimizer restarts the schedule at step 0 on zero moments
             self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
             self.model_step.fill_(ckpt["model_step"])
+        if ckpt.get("ema_model_state_dict") is not None and self.ema_model is not None:      # nnet/model.py:538-540
+            self.ema_model.load_state_dict(ckpt["ema_model_state_dict"])
+
+    # -- checkpoint averaging (nnet/model.py:944-1015) ------------------------------------------------
+    def average_checkpoints(self, paths, swa_type="equal", swa_decay=0.9):
+        """Load the checkpoints of `paths` in order (optimizer included, as the reference's swa does: model_step ends as the last one's) and leave their
+        average in the model: swa_type "equal" is the running mean  avg += (p - avg) / (k + 1), "exp" is  avg = (1 - swa_decay) * avg + swa_decay * p;  the
+        first checkpoint is copied.  On the GPU each checkpoint is ONE ops.weight_average launch from the flat master arena into a second flat buffer; a
+        model without an arena (CPU) takes the same formulas as separate torch fp32 operations, which give the same bits.
+        Parameters only are averaged.  Buffers (BatchNorm running statistics, num_batches_tracked) end as the LAST checkpoint's: that is what
+        torch.optim.swa_utils.AveragedModel(use_buffers=False), which the reference uses, leaves -- update_parameters copies the buffers on every call --
+        and why swa() refreshes the statistics afterwards."""
+        assert swa_type in ("equal", "exp"), "swa_type: equal or exp"
+        assert len(paths) > 0, "no checkpoint to average"
+        avg = None
+        with torch.no_grad():
+            for k, path in enumerate(paths):
+                self.load(path)
+                mode = 0 if k == 0 else (1 if swa_type == "equal" else 2)
+                wa, wp = (0.0, 1.0 / (k + 1)) if swa_type == "equal" else (1.0 - swa_decay, swa_decay)
+                if self.arena is not None:
+                    if avg is None:
+                        avg = torch.empty_like(self.arena.master)
+                    ops.weight_average(avg, self.arena.master, mode, wa, wp)
+                elif mode == 0:
+                    avg = [p.detach().clone() for p in self.parameters()]
+                else:
+                    for a, p in zip(avg, self.parameters()):
+                        if mode == 1:
+                            a.add_((p.detach() - a).mul_(wp))                     # three roundings, as the kernel's mode 1
+                        else:
+                            a.copy_(a.mul(wa).add_(p.detach().mul(wp)))           # alpha = 1: a plain sum of the two rounded products
+            if self.arena is not None:
+                self.arena.master.copy_(avg)
+                self.arena.mark_dirty()
+            else:
+                for a, p in zip(avg, self.parameters()):
+                    p.copy_(a)
+
+    def swa(self, dataset, callback_path, start_epoch, end_epoch, epochs_list=None, update_steps=None, swa_type="equal", swa_decay=0.9, precision=torch.float32):
+        """main.py -m swa: average checkpoints_epoch_{e}_step_*.ckpt of `callback_path` for e in epochs_list (or start_epoch .. end_epoch), refresh the BatchNorm
+        statistics with `update_steps` training-mode forward passes over `dataset` (no loss, no backward, no optimizer: the parameters do not move), and write
+        checkpoints_swa-{swa_type}-{first}-{last}.ckpt without the optimizer state."""
+        if not epochs_list:
+            epochs_list = list(range(int(start_epoch), int(end_epoch) + 1))
+        if self.rank == 0:
+            print("Stochastic Weight Averaging on checkpoints : {}".format(list(epochs_list)))
+        paths = []
+        for epoch in epochs_list:
+            pattern = os.path.join(callback_path, "checkpoints_epoch_{}_step_*.ckpt".format(epoch))
+            found = glob.glob(pattern)
+            if not found:
+                raise FileNotFoundError("no checkpoint matches " + pattern)
+            paths.append(found[0])
+        self.average_checkpoints(paths, swa_type=swa_type, swa_decay=swa_decay)
+        if self.rank == 0:
+            print("Updating Batch Normalization Statistics")
+        if update_steps is None:
+            update_steps = len(dataset)
+        self.train()
+        steps = 0
+        while steps < update_steps:
+            seen = steps
+            for batch in dataset:
+                inputs = self.transfer_to_device(batch["inputs"])
+                rt.set_compute_dtype(precision)
+                rt.reset_zero_pool(self.device)
+                Model._pre_forward(self, None)
+                with torch.no_grad():
+                    self.forward(inputs)
+                rt.advance_rng(self.device)        # dropout and SpecAugment are active, as in the reference: the next step draws other masks
+                steps += 1
+                if steps == update_steps:
+                    break
+            assert steps > seen, "swa: the dataset is empty"
+        if self.rank == 0:
+            self.save(os.path.join(callback_path, "checkpoints_swa-{}-{}-{}.ckpt".format(swa_type, epochs_list[0], epochs_list[-1])), save_optimizer=False)
+        if self.is_distributed:
+            torch.distributed.barrier()
 
     # -- loops (compact counterparts of nnet/model.py:668-942, 1047-1077) ----------------------------
     def fit(self, dataset_train, epochs, dataset_eval=None, eval_steps=None, verbose_eval=0, initial_epoch=0, callback_path=None, steps_per_epoch=None,
@@ -480,6 +639,11 @@ class Model(Module):
                     self.save(os.path.join(callback_path, "checkpoints_epoch_{}_step_{}.ckpt".format(epoch + 1, int(self.model_step))))
             if dataset_eval is not None and (epoch + 1) % eval_period_epoch == 0:
                 self.evaluate(dataset_eval, eval_steps)
+                if self.ema_model is not None:    # nnet/model.py:853-861
+                    res = self.sync_ema_buffers().evaluate(dataset_eval, eval_steps)
+                    if self.rank == 0:
+                        for r in (res if isinstance(res, list) else [res]):
+                            print("epoch %d ema eval:" % (epoch + 1), {k: round(v, 4) for k, v in r.items()})
             if self.is_distributed:
                 torch.distributed.barrier()       # ranks leave the epoch together (rank 0 wrote the checkpoint)
 

@@ -1883,6 +1883,18 @@ def argmax_rows(logits):
     return out
 
 
+def weight_average(avg, p, mode, wa=0.0, wp=0.0):
+    """One launch over two flat fp32 arenas of the same size (a multiple of 4 elements): mode 0 avg = p, mode 1 avg = avg + wp * (p - avg), mode 2
+    avg = (wa * avg) + (wp * p), every operation a single correctly rounded fp32 one (include/avec_hip.h).  In place on `avg`; graph-capturable."""
+    rt.require_gpu(avg)
+    rt.require_gpu(p)
+    if not (avg.dtype == p.dtype == torch.float32 and avg.dim() == p.dim() == 1 and avg.is_contiguous() and p.is_contiguous() and avg.numel() == p.numel()):
+        raise RuntimeError("weight_average: two flat contiguous fp32 buffers of the same size are needed (got %s %s and %s %s)"
+                           % (tuple(avg.shape), avg.dtype, tuple(p.shape), p.dtype))
+    lib.weight_average(avg.data_ptr(), p.data_ptr(), int(mode), float(wa), float(wp), avg.numel(), rt.stream())
+    return avg
+
+
 def ctc_beam_search(logits, lengths, beam, tmp=1.0, lm=None, alpha=0.6, beta=1.0):
     """CTC prefix beam search (blank 0) of logits [B, T, V] with lengths [B], optionally fused with an n-gram LM (avec_amd.ngram.NGramLM):
     one launch for the whole batch.  Returns tokens [B, beam, T] int32, out_len [B, beam] int32, score [B, beam] (ranking score, best first) and

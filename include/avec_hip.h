@@ -537,6 +537,13 @@ int avec_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
  * leaves parameters and moments untouched and only clears the gradient arena -- the step is skipped instead of poisoning the model state */
 int avec_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
                            float weight_decay, float grad_scale, int zero_grad, long long n, const int* skip_flag, hipStream_t stream);
+/* Weight averaging over two flat fp32 arenas of n elements (n > 0, n % 4 == 0; avg and p must not overlap), one launch, no atomics:
+ *   mode 0: avg = p                         the first checkpoint (torch.optim.swa_utils.AveragedModel with n_averaged == 0, nnet/model.py:948-967)
+ *   mode 1: avg = avg + wp * (p - avg)      swa_type "equal", wp = 1 / (n_averaged + 1); wa is ignored
+ *   mode 2: avg = (wa * avg) + (wp * p)     swa_type "exp" (nnet/model.py:950: wa = 1 - swa_decay, wp = swa_decay) and the EMA model's update
+ *                                           (nnet/model.py:403-405: param_target.mul_(tau); param_target.add_((1 - tau) * param_net), wa = tau, wp = 1 - tau)
+ * Every product, difference and sum is one correctly rounded fp32 operation (never contracted into an FMA): the result equals the same lines on torch fp32 tensors. */
+int avec_weight_average(float* avg, const float* p, int mode, float wa, float wp, long long n, hipStream_t stream);
 /* Compute-dtype copies of the GEMM weights (master fp32 [A][Tm][C]): fwd = same order, bwd = [C][Tm][A].  table entry = 10 x int64: src_off, fwd_off|-1,
  * bwd_off|-1, A, Tm, C, first_block, n_blocks = Tm*ceil(A/64)*ceil(C/64) (one workgroup per 64x64 tile and tap), C_pad (row stride of the fwd
  * shadow when Tm==1), bwd row pitch (0: Tm*A; larger when several weights share one [C][G*A] backward matrix, e.g. Q|K|V) */

@@ -1,10 +1,14 @@
 """Command-line entry point with the reference's interface (main.py:30-124 there):
 
-    python main.py -c <config.py> -m training|evaluation|eval_time|pass [-i checkpoint | --load_last] [--steps_per_epoch N] [--eval_steps N]
+    python main.py -c <config.py> -m training|evaluation|swa|eval_time|pass [-i checkpoint | --load_last] [--steps_per_epoch N] [--eval_steps N]
+    python main.py -c <config.py> -m swa --swa_epochs FIRST LAST | --swa_epochs_list E1 E2 ... [--swa_type equal|exp] [--steps_per_epoch N]
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 main.py -c <config.py> -d        (one process per GPU, RCCL)
 
 The config is a Python file that builds `model` (an nnet.Model, already compiled) and optionally `training_dataset`, `evaluation_dataset`,
-`callback_path`, `epochs`, `precision`, `accumulated_steps`, ... exactly like configs/LRS23/AV/EffConfInterCTC.py of the reference."""
+`callback_path`, `epochs`, `precision`, `accumulated_steps`, ... exactly like configs/LRS23/AV/EffConfInterCTC.py of the reference.
+
+-m swa averages the epoch checkpoints of `callback_path`, refreshes the BatchNorm statistics over `training_dataset` (--steps_per_epoch batches; default: one pass)
+and writes checkpoints_swa-<type>-<first>-<last>.ckpt there (Model.swa)."""
 import argparse
 import importlib.util
 import os
@@ -38,7 +42,7 @@ def run(args):
     cfg = args.config
     model = functions.load_model(args)
     dataset_train, dataset_eval = functions.load_datasets(args)
-    assert args.mode in ("training", "evaluation", "pass", "eval_time"), "modes: training, evaluation, eval_time, pass"
+    assert args.mode in ("training", "evaluation", "swa", "pass", "eval_time"), "modes: training, evaluation, swa, eval_time, pass"
     if args.mode == "training":
         initial_epoch = int(args.checkpoint.split("_")[2]) if args.checkpoint is not None else 0
         model.fit(dataset_train, epochs=getattr(cfg, "epochs", 1000), dataset_eval=dataset_eval, eval_steps=getattr(cfg, "eval_steps", args.eval_steps),
@@ -54,6 +58,10 @@ def run(args):
                                  recompute_metrics=getattr(cfg, "recompute_metrics", False))
             if args.rank == 0:
                 print("Evaluation:", {k: round(v, 4) for k, v in res.items()})
+    elif args.mode == "swa":
+        model.swa(dataset_train, callback_path=cfg.callback_path, start_epoch=args.swa_epochs[0] if args.swa_epochs else None,
+                  end_epoch=args.swa_epochs[1] if args.swa_epochs else None, epochs_list=args.swa_epochs_list, update_steps=args.steps_per_epoch,
+                  swa_type=args.swa_type, precision=getattr(cfg, "precision", torch.float32))
     elif args.mode == "eval_time":
         loaders = dataset_eval if isinstance(dataset_eval, list) else [dataset_eval]
         t = sum(model.eval_time(loader, eval_steps=getattr(cfg, "eval_steps", args.eval_steps)) for loader in loaders)
@@ -63,7 +71,7 @@ def run(args):
         torch.distributed.destroy_process_group()
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-c", "--config_file", type=str, default="configs/LRS23/AV/EffConfInterCTC.py")
     ap.add_argument("-m", "--mode", type=str, default="training")
@@ -82,7 +90,14 @@ def main():
     ap.add_argument("--verbose_eval", type=int, default=0)
     ap.add_argument("--eval_steps", type=int, default=None)
     ap.add_argument("--show_dict", action="store_true")
-    args = ap.parse_args()
+    ap.add_argument("--swa_epochs", nargs="+", default=None)            # start epoch, end epoch
+    ap.add_argument("--swa_epochs_list", nargs="+", default=None)       # or the epochs one by one
+    ap.add_argument("--swa_type", type=str, default="equal")            # equal | exp
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     # one process per GPU: ranks come from the launcher's environment (torchrun); -d without a launcher = a single-rank group
     args.world_size = int(os.environ.get("WORLD_SIZE", "1"))
     args.rank = int(os.environ.get("RANK", "0"))
