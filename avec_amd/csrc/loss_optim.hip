@@ -414,7 +414,10 @@ extern "C" int avec_argmax_rows(const float* x, long long* out, long long M, int
 // g <- g*gscale; g += wd*p; m,v updates; p -= lr * mhat / (sqrt(v)/sqrt(bc2) + eps);  optionally zero the gradient arena.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ state,
-                                                   float beta1, float beta2, float eps, float wd, float gscale, int zero_grad, long long n4, const int* __restrict__ skip_flag) {
+                                                   float beta1, float beta2, float eps, float wd, float gscale, int zero_grad, long long n4, const int* __restrict__ skip_flag,
+                                                   const float* __restrict__ clip) {
+  // clip (optional, device): avec_grad_norm's {norm, coef} pair -- the clip factor is folded into the gradient scale, the arena is not rescaled in a pass of its own
+  if (clip) gscale = gscale * clip[1];
   // skip_flag (optional, device): non-zero = this step's gradients are poisoned (a SyncBatchNorm peer exchange timed out and produced NaN sums):
   // parameters and moments stay untouched, the gradient arena is still cleared so that the next step starts clean
   if (skip_flag && *skip_flag != 0) {
@@ -438,16 +441,96 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
     if (zero_grad) st4<float>(g + i * 4, gg);
   }
 }
-extern "C" int avec_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
-                                      float weight_decay, float grad_scale, int zero_grad, long long n, const int* skip_flag, hipStream_t st) {
+extern "C" int avec_adam_step_clipped(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
+                                      float weight_decay, float grad_scale, int zero_grad, long long n, const int* skip_flag, const float* clip_dev, hipStream_t st) {
   AVEC_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && state_dev && n > 0 && n % 4 == 0, "adam_step: bad arguments (n=%lld must be a multiple of 4)", n);
   long long n4 = n / 4; long long nb = (n4 + 255) / 256; if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nb), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, state_dev, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, n4, skip_flag);
+  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nb), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, state_dev, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, n4, skip_flag,
+                     clip_dev);
   AVEC_LAUNCH_CHECK(); return 0;
+}
+extern "C" int avec_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
+                                      float weight_decay, float grad_scale, int zero_grad, long long n, const int* skip_flag, hipStream_t st) {
+  return avec_adam_step_clipped(params, grads, exp_avg, exp_avg_sq, state_dev, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, n, skip_flag, nullptr, st);
 }
 extern "C" int avec_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
                               float weight_decay, float grad_scale, int zero_grad, long long n, hipStream_t st) {
   return avec_adam_step_guarded(params, grads, exp_avg, exp_avg_sq, state_dev, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, n, nullptr, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Global L2 norm of the flat gradient arena and the clip factor of torch.nn.utils.clip_grad_norm_, in two launches without atomics:
+//   pass 1: grid-stride over 16-byte loads, GN_UNROLL of them in flight per lane; every element is widened to fp64 BEFORE it is squared (3e38^2 is finite there,
+//           1e-20^2 is not a subnormal), summed per lane, per wave (shuffles), per workgroup (LDS); one fp64 partial per workgroup goes to the workspace
+//   pass 2: one workgroup adds the partials in a fixed order in fp64, then  norm = fp32(sqrt(sum) * grad_scale),  coef = min(1, max_norm / (norm + 1e-6))
+// The grid of pass 1 depends on n alone, so the result is a pure function of the input: two launches give the same bits.
+// ---------------------------------------------------------------------------------------------
+constexpr int GN_BLOCKS_MAX = 2048, GN_UNROLL = 4;
+__device__ __forceinline__ double gn_block_sum(double s, double* lds) {
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) lds[w] = s;
+  __syncthreads();
+  return (lds[0] + lds[1]) + (lds[2] + lds[3]);            // (every thread: the same value, the same order)
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long long n4, double* __restrict__ partial) {
+  __shared__ double lds[4];
+  const long long stride = (long long)gridDim.x * 256;
+  double acc[GN_UNROLL];
+#pragma unroll
+  for (int u = 0; u < GN_UNROLL; ++u) acc[u] = 0.0;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + (GN_UNROLL - 1) * stride < n4; i += stride * GN_UNROLL) {      // all GN_UNROLL loads in range: no branch between them, so they are in flight together
+    float x[GN_UNROLL][4];
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u) ld4<float>(g + (i + u * stride) * 4, x[u]);
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const double d = (double)x[u][e]; acc[u] += d * d; }
+  }
+  for (int u = 0; i < n4; i += stride, ++u) {                               // the last, partial round: at most GN_UNROLL - 1 loads, into the same accumulators
+    float x[4]; ld4<float>(g + i * 4, x);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const double d = (double)x[e]; acc[u] += d * d; }
+  }
+  const double s = gn_block_sum((acc[0] + acc[1]) + (acc[2] + acc[3]), lds);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const double* __restrict__ partial, int n_partial, float grad_scale, float max_norm, int skip_nonfinite,
+                                                              const int* __restrict__ skip_in, float* __restrict__ stats, int* __restrict__ flag) {
+  __shared__ double lds[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_partial; i += 256) s += partial[i];
+  s = gn_block_sum(s, lds);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)(sqrt(s) * (double)grad_scale);
+  const bool finite = isfinite(norm);
+  float coef = 1.f;
+  if (finite && max_norm > 0.f && !isinf(max_norm)) coef = fminf(1.f, max_norm / (norm + 1e-6f));
+  stats[0] = norm; stats[1] = coef;
+  if (flag) {
+    const int skip = ((skip_in && *skip_in != 0) || (skip_nonfinite && !finite)) ? 1 : 0;
+    flag[0] = skip; flag[1] += skip;
+  }
+}
+extern "C" int avec_grad_norm_blocks(long long n) {
+  if (n <= 0) return 0;
+  const long long nb = ((n + 3) / 4 + 255) / 256;
+  return (int)(nb > GN_BLOCKS_MAX ? GN_BLOCKS_MAX : nb);
+}
+extern "C" long long avec_grad_norm_workspace_bytes(long long n) { return (long long)avec_grad_norm_blocks(n) * (long long)sizeof(double); }
+extern "C" int avec_grad_norm(const float* g, long long n, float grad_scale, float max_norm, int skip_nonfinite, const int* skip_in, void* workspace, long long workspace_bytes,
+                              float* stats, int* flag, hipStream_t st) {
+  AVEC_CHECK_ARG(g && (uintptr_t)g % 16 == 0 && n > 0 && n % 4 == 0, "grad_norm: bad arguments (a 16-byte aligned arena; n=%lld must be a positive multiple of 4)", n);
+  AVEC_CHECK_ARG(stats, "grad_norm: stats (the {norm, coef} pair) is NULL");
+  AVEC_CHECK_ARG(workspace && workspace_bytes >= avec_grad_norm_workspace_bytes(n) && (uintptr_t)workspace % 8 == 0,
+                 "grad_norm: workspace of %lld bytes, %lld needed (8-byte aligned)", workspace_bytes, avec_grad_norm_workspace_bytes(n));
+  const int nb = avec_grad_norm_blocks(n);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nb), dim3(256), 0, st, g, n / 4, (double*)workspace);
+  AVEC_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace, nb, grad_scale, max_norm, skip_nonfinite, skip_in, stats, flag);
+  AVEC_LAUNCH_CHECK(); return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

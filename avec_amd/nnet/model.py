@@ -28,6 +28,7 @@ class Model(Module):
         self.compiled, self.built = False, False
         self.name = name
         self.ema_model, self.ema_tau, self.grad_max_norm = None, 0.0, None
+        self.skip_nonfinite_steps = False      # skip an optimizer step whose global gradient norm is NaN or infinite (what the reference's GradScaler does under fp16)
         self.arena = None
         self.world_size = 1
 
@@ -285,18 +286,35 @@ class Model(Module):
         acc_step += 1
         if acc_step < accumulated_steps:
             return batch_losses, batch_metrics, acc_step
+        self._finish_optimizer_step()
+        return batch_losses, batch_metrics, 0
+
+    def _finish_optimizer_step(self):
+        """what follows the last micro-step's backward pass, as eager launches without host synchronisation: gradient all-reduce (data parallel), the global norm and
+        clip factor on the device (grad_max_norm / skip_nonfinite_steps: ops.grad_norm, read by the optimizer launch), the optimizer launch, the EMA launch, the infos.
+        The host never reads the guard's flag, so on a skipped step everything but the optimizer launch still happens: the scheduler and model_step advance, and
+        the EMA model takes one more step toward parameters that did not change.  infos["skipped_steps"] counts since the optimizer's flat state was allocated: it
+        is not saved in checkpoints and starts at 0 again after Adam.load_state_dict."""
         if self.is_distributed:
             # the reference all-reduces on every micro-batch (no no_sync); summing once per optimizer step is numerically the same
             self.arena.all_reduce_grads()
             self.optimizer.grad_scale = 1.0 / self.world_size
-        if self.grad_max_norm is not None:
-            self.add_info("grad_norm", self.clip_gradients(self.grad_max_norm))
-        self.optimizer.step()
+        guard = bool(getattr(self, "skip_nonfinite_steps", False))
+        clip = self.grad_max_norm is not None or guard
+        if clip:
+            if self.arena is None or not hasattr(self.optimizer, "launch_grad_norm"):
+                raise RuntimeError("gradient clipping and the non-finite guard run on the flat gradient arena on the GPU with nnet.Adam: move the model with Model.to('cuda') first")
+            stats = self.optimizer.launch_grad_norm(self.grad_max_norm, guard)
+            self.add_info("grad_norm", stats[0])              # device scalars: turned into numbers only where fit prints
+            if guard:
+                self.add_info("skipped_steps", self.optimizer.skipped_steps)
+            self.optimizer.step(clip=True)
+        else:
+            self.optimizer.step()
         self._update_ema()
         self.optimizer.zero_grad()
         self.add_info("lr", float(self.optimizer.param_groups[0]["lr"]))
         self.add_info("step", int(self.model_step))
-        return batch_losses, batch_metrics, 0
 
     def clip_gradients(self, max_norm):
         """global-norm clipping of the flat gradient arena (torch.nn.utils.clip_grad_norm_ semantics, nnet/model.py:381-383); returns the norm before clipping"""
@@ -451,38 +469,151 @@ class Model(Module):
             labels = torch.nn.functional.pad(labels, (0, Lp - labels.shape[1]))
         return [video, vlen, audio, alen], (labels, llen)
 
-    def graphed_train_step(self, inputs, targets, precision=torch.bfloat16, cache_size=8, bucket_frames=None):
-        """train_step through a cache of captured steps keyed by the batch shape (LRU, `cache_size` graphs: each holds its own activation pool).  Ragged LRS batches
-        (nnet/collate_fn.py pads to the batch maximum) repeat a small set of shapes once they are bucketed (`bucket_frames`, see pad_av_batch) or come from a
-        length-bucketed sampler.  Falls back to train_step when a step cannot be captured as is (scheduled loss weights, gradient clipping, data parallel without the
-        peer exchange)."""
-        from .schedulers import ConstantScheduler
+    def _graph_capturable(self):
+        """a step can be captured as is: constant loss weights (scheduled ones change a launch argument from step to step), and in data parallel capturable
+        SyncBatchNorm exchanges (the peer exchange, or RCCL over the nccl backend)"""
         from .. import peer
         lw = self.compiled_loss_weights
         const_w = isinstance(lw, ConstantScheduler) or (isinstance(lw, dict) and all(isinstance(v, ConstantScheduler) for v in lw.values())) \
             or (isinstance(lw, list) and all(isinstance(v, ConstantScheduler) for v in lw))
         capturable = (not self.is_distributed) or peer.active() is not None or \
             (torch.distributed.get_backend() == "nccl" and os.environ.get("AVEC_GRAPH_ALLREDUCE", "1") != "0")
-        if not const_w or self.grad_max_norm is not None or not capturable:
+        return const_w and capturable
+
+    def graphed_train_step(self, inputs, targets, precision=torch.bfloat16, cache_size=8, bucket_frames=None):
+        """train_step through a cache of captured steps keyed by the batch shape (LRU, `cache_size` graphs: each holds its own activation pool).  Ragged LRS batches
+        (nnet/collate_fn.py pads to the batch maximum) repeat a small set of shapes once they are bucketed (`bucket_frames`, see pad_av_batch) or come from a
+        length-bucketed sampler.  Falls back to train_step when a step cannot be captured as is (scheduled loss weights, data parallel without capturable
+        SyncBatchNorm exchanges).  With gradient clipping or the non-finite guard the step is graphed_micro_step's: forward + backward replayed, norm and optimizer
+        launches behind the replay."""
+        if not self._graph_capturable():
             return self.train_step(inputs, targets, precision=precision)[0]
+        if self.grad_max_norm is not None or getattr(self, "skip_nonfinite_steps", False):
+            return self.graphed_micro_step(inputs, targets, precision, 1, 0, cache_size=cache_size, bucket_frames=bucket_frames)[0]
         if bucket_frames and len(inputs) == 4 and inputs[0].dim() == 5 and isinstance(targets, (tuple, list)) and len(targets) == 2:
             inputs, targets = self.pad_av_batch(inputs, targets, bucket_frames)
         key = tuple((tuple(t.shape), str(t.dtype)) for t in list(inputs) + list(targets)) + (str(precision),)
         cache = self.__dict__.setdefault("_graph_cache", {})
         step = cache.pop(key, None)
         if step is None:
-            while len(cache) >= cache_size:
-                cache.pop(next(iter(cache)))                 # least recently used (dict order = recency)
-                ev = self.__dict__["_graph_evictions"] = self.__dict__.get("_graph_evictions", 0) + 1
-                if ev == 2 * cache_size:                     # every new shape costs an eager warm-up step, a capture and a private activation pool
-                    import warnings
-                    warnings.warn("graphed_train_step: %d captured steps evicted from a cache of %d -- the batch shapes do not repeat; bucket the batches "
-                                  "(graph_bucket_frames / a length-bucketed sampler, nnet/samplers.py) or raise graph_cache_size" % (ev, cache_size))
+            self._evict_graphs(cache, cache_size, "graphed_train_step")
             step = self.make_graphed_train_step(inputs, targets, precision=precision, warmup=1)      # (the warm-up pass is a real optimisation step on this batch)
             cache[key] = step
             return step.warm_losses
         cache[key] = step
         return step(inputs, targets)
+
+    def _evict_graphs(self, cache, cache_size, who):
+        while len(cache) >= cache_size:
+            cache.pop(next(iter(cache)))                 # least recently used (dict order = recency)
+            ev = self.__dict__["_graph_evictions"] = self.__dict__.get("_graph_evictions", 0) + 1
+            if ev == 2 * cache_size:                     # every new shape costs an eager warm-up step, a capture and a private activation pool
+                import warnings
+                warnings.warn("%s: %d captured steps evicted from a cache of %d -- the batch shapes do not repeat; bucket the batches "
+                              "(graph_bucket_frames / a length-bucketed sampler, nnet/samplers.py) or raise graph_cache_size" % (who, ev, cache_size))
+
+    # -- hipGraph replay of ONE micro-step (forward + backward): gradient accumulation, clipping and the non-finite guard keep the optimizer tail eager ---------
+    def make_graphed_micro_step(self, inputs, targets, precision, accumulated_steps):
+        """Run ONE real micro-step eagerly on this batch (it accumulates into the gradient arena like train_step's), then capture the same body into a hipGraph:
+        reset_zero_pool, forward, losses, (loss / accumulated_steps).backward(), advance_rng.  No optimizer, no EMA, no gradient all-reduce and no shadow refresh are
+        inside: the weight shadows are made fresh before the capture and before every replay (one eager launch after an optimizer step, nothing on the other
+        micro-steps).  Capturing executes nothing, so the arena is not touched twice.  Like every captured step it holds the modules' training / evaluation
+        modes as they were at the capture.  Returns micro(inputs, targets) -> losses (static device scalars) with .warm_losses, the eager pass's."""
+        dist_mode = self.is_distributed
+        rt.set_compute_dtype(precision)
+        static_in = [t.clone() for t in inputs]
+        static_tg = tuple(t.clone() for t in targets)
+        if dist_mode:
+            self.arena.arm_early_all_reduce(False)          # the gradient exchange follows the LAST replay (amortised over the micro-steps), never from inside the backward pass
+
+        def body():
+            rt.reset_zero_pool(self.device)
+            losses, _, _, _ = self.forward_model(static_in, static_tg, compute_metrics=False)
+            (losses["loss"] / accumulated_steps).backward()
+            rt.advance_rng(self.device)
+            return losses
+
+        # the eager pass on a side stream, as torch.cuda.graph's own warm-up advice: lazily created constants (DFT matrix, sinusoid tables, loss weights), kernel
+        # attributes and the allocator's blocks exist before the capture
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            warm = self._own_losses(body())
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        if dist_mode and torch.distributed.get_backend() == "nccl":
+            time.sleep(0.6)                                 # the process group's watchdog must have reaped every collective issued so far (see make_graphed_train_step)
+        self.arena.check_versions()
+        self.arena.ensure_fresh()                           # no refresh inside the graph
+        ops.invalidate_pos_cache()                          # the position projections, cached per refresh, are computed INSIDE the graph: every replay follows the weights
+        graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(graph):
+                static_losses = body()
+        except Exception:
+            ops.reset_backward_state()                      # an aborted capture leaves a half-run backward pass behind
+            raise
+        assert not self.arena.dirty, "the captured micro-step must not hold a shadow refresh"
+
+        def micro(new_inputs, new_targets):
+            for d, s_ in zip(static_in, new_inputs):
+                d.copy_(s_, non_blocking=True)
+            for d, s_ in zip(static_tg, new_targets):
+                d.copy_(s_, non_blocking=True)
+            if dist_mode:
+                self.arena.arm_early_all_reduce(False)
+            rt.set_compute_dtype(precision)
+            self.arena.check_versions()                     # (weights edited in place since the last pass: the forward pre-hook's check does not run inside a replay)
+            self.arena.ensure_fresh()
+            graph.replay()
+            return static_losses
+
+        micro.graph = graph
+        micro.warm_losses = warm
+        return micro
+
+    def _micro_fallback_reason(self, eval_training=False):
+        """why graphed_micro_step runs train_step instead of a captured micro-step, or None"""
+        from .. import fp8
+        if self.device.type != "cuda":
+            return "the model is not on a GPU"
+        if eval_training and self.compiled_metrics:
+            return "eval_training with compiled metrics needs the host on every step (pass eval_training=False / --no_eval_training)"
+        if fp8.enabled():
+            return "AVEC_FP8=1"
+        if not self._graph_capturable():
+            return "scheduled loss weights, or data parallel without capturable SyncBatchNorm exchanges"
+        return None
+
+    def graphed_micro_step(self, inputs, targets, precision=torch.bfloat16, accumulated_steps=1, acc_step=0, cache_size=8, bucket_frames=None, eval_training=False):
+        """One micro-step of train_step(accumulated_steps=k) from a cache of captured forward + backward passes keyed by batch shape, precision and k (LRU,
+        `cache_size` graphs, each with its own activation pool); returns (losses, acc_step) with acc_step = 0 after the optimizer step.  The first time a shape
+        appears the micro-step runs eagerly (a real micro-step) and is captured afterwards.  Behind the last micro-step's replay follow, as eager launches without
+        host synchronisation: the gradient all-reduce (data parallel), the norm / clip-factor launches (grad_max_norm, skip_nonfinite_steps), the optimizer and EMA
+        launches.  Falls back to train_step when the step cannot be captured as is: scheduled loss weights, eval_training with compiled metrics (they need the
+        host), AVEC_FP8=1, data parallel without capturable SyncBatchNorm exchanges."""
+        why = self._micro_fallback_reason(eval_training)
+        if why is not None:
+            self.__dict__["_micro_fallback"] = why           # (fit says so once: nobody should believe they are on the replay path)
+            losses, _, acc_step = self.train_step(inputs, targets, precision, None, accumulated_steps, acc_step, eval_training)
+            return losses, acc_step
+        if bucket_frames and len(inputs) == 4 and inputs[0].dim() == 5 and isinstance(targets, (tuple, list)) and len(targets) == 2:
+            inputs, targets = self.pad_av_batch(inputs, targets, bucket_frames)
+        key = tuple((tuple(t.shape), str(t.dtype)) for t in list(inputs) + list(targets)) + (str(precision), int(accumulated_steps))
+        cache = self.__dict__.setdefault("_micro_graph_cache", {})
+        micro = cache.pop(key, None)
+        if micro is None:
+            self._evict_graphs(cache, cache_size, "graphed_micro_step")
+            micro = self.make_graphed_micro_step(inputs, targets, precision, accumulated_steps)
+            losses = micro.warm_losses
+        else:
+            losses = self._own_losses(micro(inputs, targets))      # copies: the next replay refills the static outputs
+        cache[key] = micro
+        acc_step += 1
+        if acc_step < accumulated_steps:
+            return losses, acc_step
+        self._finish_optimizer_step()
+        return losses, 0
 
     @staticmethod
     def _own_losses(batch_losses):
@@ -604,8 +735,10 @@ class Model(Module):
             precision=torch.float32, accumulated_steps=1, eval_period_step=None, eval_period_epoch=1, saving_period_epoch=1, log_figure_period_step=None,
             log_figure_period_epoch=1, step_log_period=100, eval_training=True, grad_init_scale=65536.0, detect_anomaly=False, recompute_metrics=False,
             wandb_logging=False, verbose_progress_bar=1, keep_last_k=None, use_graphs=False, graph_bucket_frames=None, graph_cache_size=8):
-        """use_graphs: replay captured steps per batch shape (graphed_train_step) instead of eager launches; graph_bucket_frames: additionally zero-pad AV batches to
-        multiples of that many video frames so that few shapes occur (opt-in: changes the padding the BatchNorm statistics see)."""
+        """use_graphs: replay captured steps per batch shape instead of eager launches -- the whole step (graphed_train_step) when accumulated_steps == 1 without
+        clipping or the non-finite guard, else forward + backward per micro-step with the optimizer tail behind the last one (graphed_micro_step; with eval_training
+        and compiled metrics it runs eagerly: metrics need the host); graph_bucket_frames: additionally zero-pad AV batches to multiples of that many video frames so
+        that few shapes occur (opt-in: changes the padding the BatchNorm statistics see)."""
         if callback_path is not None and self.rank == 0:
             os.makedirs(callback_path, exist_ok=True)
         for epoch in range(initial_epoch, epochs):
@@ -620,7 +753,15 @@ class Model(Module):
             for step, batch in enumerate(dataset_train):
                 inputs = self.transfer_to_device(batch["inputs"])
                 targets = self.transfer_to_device(batch["targets"])
-                if use_graphs and accumulated_steps == 1 and self.device.type == "cuda":
+                micro = accumulated_steps > 1 or self.grad_max_norm is not None or getattr(self, "skip_nonfinite_steps", False)
+                if use_graphs and micro and self.device.type == "cuda":
+                    losses, acc_step = self.graphed_micro_step(inputs, targets, precision, accumulated_steps, acc_step, cache_size=graph_cache_size,
+                                                               bucket_frames=graph_bucket_frames, eval_training=eval_training)
+                    if "_micro_fallback" in self.__dict__ and not self.__dict__.get("_micro_fallback_said"):
+                        self.__dict__["_micro_fallback_said"] = True
+                        if self.rank == 0:
+                            print("use_graphs: training with eager launches, not replayed graphs -- " + self.__dict__["_micro_fallback"])
+                elif use_graphs and self.device.type == "cuda":
                     losses = self.graphed_train_step(inputs, targets, precision=precision, cache_size=graph_cache_size, bucket_frames=graph_bucket_frames)
                 else:
                     losses, _, acc_step = self.train_step(inputs, targets, precision, None, accumulated_steps, acc_step, eval_training)
@@ -630,7 +771,12 @@ class Model(Module):
                     if peer.active() is not None:
                         peer.active().check()            # a SyncBatchNorm peer exchange that lost a rank raises here (its sums were NaN from that step on)
                 if self.rank == 0 and step % step_log_period == 0:
-                    print("epoch %d step %d model_step %d loss %.4f" % (epoch + 1, step, int(self.model_step), float(losses["loss"].detach())))
+                    extra = ""
+                    if torch.is_tensor(self.infos.get("grad_norm")):       # device scalars of the last optimizer step: read (one synchronisation) only here
+                        extra += " grad_norm %.4f" % float(self.infos["grad_norm"])
+                    if torch.is_tensor(self.infos.get("skipped_steps")):
+                        extra += " skipped_steps %d" % int(self.infos["skipped_steps"])
+                    print("epoch %d step %d model_step %d loss %.4f%s" % (epoch + 1, step, int(self.model_step), float(losses["loss"].detach()), extra))
                 if steps_per_epoch is not None and step + 1 >= steps_per_epoch:
                     break
             if self.rank == 0:

@@ -3,6 +3,7 @@ HIP launch over the flat fp32 arenas (the reference's single-tensor path issues 
 import torch
 import torch.optim as optim
 
+from .. import ops
 from .. import runtime as rt
 from ..lib import lib
 from . import schedulers
@@ -25,7 +26,10 @@ class Adam(optim.Adam):
         self.arena = arena
         dev = arena.master.device
         self._flat = {"exp_avg": torch.zeros_like(arena.master), "exp_avg_sq": torch.zeros_like(arena.master),
-                      "state": torch.zeros(2, dtype=torch.float32, device=dev)}
+                      "state": torch.zeros(2, dtype=torch.float32, device=dev),
+                      # ops.grad_norm's outputs (clipping and the non-finite guard): {norm, coef}, {skip this step, steps skipped so far}, and its fp64 partial sums
+                      "clip_stats": torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev), "clip_flag": torch.zeros(2, dtype=torch.int32, device=dev),
+                      "clip_ws": ops.grad_norm_workspace(arena.numel, dev)}
         self._step_t = torch.tensor(0.0)
         for p, o in zip(arena.params, arena.offsets):
             st = self.state[p]
@@ -56,21 +60,46 @@ class Adam(optim.Adam):
         self._flat["state"].copy_(slot, non_blocking=True)
         ev.record()
 
-    def launch_step(self):
-        """device half: ONE kernel over the flat arenas (graph-capturable)"""
+    def launch_grad_norm(self, max_norm=None, skip_nonfinite=False):
+        """Global gradient norm (times grad_scale) and clip factor on the device, two launches (ops.grad_norm); the next launch_step(clip=True) applies the factor
+        and skips the update when the flag is raised (a non-finite norm under `skip_nonfinite`, or the peer exchange's error flag).  Returns the {norm, coef} pair."""
+        from .. import peer
+        px = peer.active()
+        f = self._flat
+        return ops.grad_norm(self.arena.grad, f["clip_ws"], f["clip_stats"], f["clip_flag"], self.grad_scale, max_norm, skip_nonfinite,
+                             px.err if px is not None else None)
+
+    @property
+    def grad_norm_stats(self):
+        """device fp32 pair {norm, coef} of the last launch_grad_norm"""
+        return self._flat["clip_stats"]
+
+    @property
+    def skipped_steps(self):
+        """device int32 scalar: optimizer steps skipped by the guard so far (reading it synchronises).  It lives beside the clip pair in the flat state that
+        attach_arena allocates: it is not part of state_dict, so a checkpoint does not hold it and load_state_dict (which attaches the arena again) starts it at 0"""
+        return self._flat["clip_flag"][1]
+
+    def launch_step(self, clip=False):
+        """device half: ONE kernel over the flat arenas (graph-capturable).  clip: read the clip factor and the skip flag launch_grad_norm left on the device"""
         g = self.param_groups[0]
-        self._launch(g)
+        self._launch(g, clip)
         self.arena.mark_dirty()
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, clip=False):
         self.prepare_step()
-        self.launch_step()
+        self.launch_step(clip)
         self._step_t.fill_(float(self.scheduler.model_step))     # one shared CPU scalar stands for every per-parameter "step"
         return None
 
-    def _launch(self, g):
+    def _launch(self, g, clip=False):
         from .. import peer
+        if clip:                      # (the peer exchange's error flag arrived in clip_flag through the norm launch's skip_in)
+            lib.adam_step_clipped(self.arena.master.data_ptr(), self.arena.grad.data_ptr(), self._flat["exp_avg"].data_ptr(), self._flat["exp_avg_sq"].data_ptr(),
+                                  self._flat["state"].data_ptr(), g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.grad_scale, 1,
+                                  self.arena.numel, self._flat["clip_flag"].data_ptr(), self._flat["clip_stats"].data_ptr(), rt.stream())
+            return
         px = peer.active()            # data parallel with the peer exchange: its device error flag guards the update (a lost rank -> NaN sums -> skipped step)
         lib.adam_step_guarded(self.arena.master.data_ptr(), self.arena.grad.data_ptr(), self._flat["exp_avg"].data_ptr(), self._flat["exp_avg_sq"].data_ptr(),
                               self._flat["state"].data_ptr(), g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.grad_scale, 1,

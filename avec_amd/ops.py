@@ -748,10 +748,19 @@ def _attn_args(qkv, e, lens, len_div, mask, o, lse, B, H, T, d, D, q_full=0):
 # takes ONE cast and ONE weight-gradient product when the last of them has arrived: 2 (L - 1) launches less per stage and pass.  Versioned by the arena's shadow
 # refresh counter (E follows the weights), per sequence length.
 _POS_CACHE = {}
+_POS_EPOCH = [0]
 
 
 class _PosGroupEntry:
-    __slots__ = ("e_all", "pe", "L", "D", "Tp")
+    __slots__ = ("e_all", "pe", "L", "D", "Tp", "capture")
+
+
+def invalidate_pos_cache():
+    """Forget every cached E: the next forward pass computes it again.  A capture that holds no shadow refresh (Model.make_graphed_micro_step) calls this first, so
+    that E is computed INSIDE its graph and follows the weights on every replay -- an entry built by an earlier capture lives in that graph's pool and is filled only
+    when that graph replays."""
+    _POS_CACHE.clear()
+    _POS_EPOCH[0] += 1
 
 
 def _pos_group_entry(wp, Tp, D, device):
@@ -772,12 +781,15 @@ def _pos_group_entry(wp, Tp, D, device):
         L = len(grp.weights)
         e = _PosGroupEntry()
         e.L, e.D, e.Tp, e.pe = L, D, Tp, rel_pos_table(Tp, D, device)
+        e.capture = _POS_EPOCH[0] if torch.cuda.is_current_stream_capturing() else None
         e.e_all = empty((2 * Tp - 1, L * D), rt.act_dtype(), e.pe)
         gemm_nt(e.pe, grp.fwd, e.e_all, 2 * Tp - 1, L * D, D, bias=grp.bias)
         _POS_CACHE[key] = ent = (ver, e, grp)
         if len(_POS_CACHE) > 64:
             for k in list(_POS_CACHE)[:32]:
                 _POS_CACHE.pop(k, None)
+    elif ent[1].capture is not None and torch.cuda.is_current_stream_capturing():
+        assert ent[1].capture == _POS_EPOCH[0], "E built inside one captured graph must not be served to a later capture"
     return ent[1], idx
 
 
@@ -1893,6 +1905,25 @@ def weight_average(avg, p, mode, wa=0.0, wp=0.0):
                            % (tuple(avg.shape), avg.dtype, tuple(p.shape), p.dtype))
     lib.weight_average(avg.data_ptr(), p.data_ptr(), int(mode), float(wa), float(wp), avg.numel(), rt.stream())
     return avg
+
+
+def grad_norm_workspace(n, device):
+    """the fp64 partial sums of ops.grad_norm for an arena of n elements (a few KB: one per workgroup of the first launch)"""
+    return torch.empty(max(int(lib.raw("avec_grad_norm_workspace_bytes")(int(n))), 8) // 8, dtype=torch.float64, device=device)
+
+
+def grad_norm(grad, workspace, stats, flag, grad_scale=1.0, max_norm=None, skip_nonfinite=False, skip_in=None):
+    """Global L2 norm of the flat fp32 gradient arena times `grad_scale`, and torch.nn.utils.clip_grad_norm_'s factor for `max_norm` (None: 1), on the device:
+    stats (fp32 [2]) = {norm, coef}, flag (int32 [2]) = {skip this step, steps skipped so far} (include/avec_hip.h).  Two launches, no atomics, no host
+    synchronisation, graph-capturable; the optimizer launch reads both (Adam.launch_step(clip=True))."""
+    rt.require_gpu(grad)
+    if not (grad.dtype == torch.float32 and grad.dim() == 1 and grad.is_contiguous() and stats.dtype == torch.float32 and stats.numel() >= 2
+            and flag.dtype == torch.int32 and flag.numel() >= 2 and (skip_in is None or skip_in.dtype == torch.int32)):
+        raise RuntimeError("grad_norm: a flat contiguous fp32 arena, fp32 stats[2] and int32 flag[2] are needed (got %s %s, %s, %s)"
+                           % (tuple(grad.shape), grad.dtype, stats.dtype, flag.dtype))
+    lib.grad_norm(grad.data_ptr(), grad.numel(), float(grad_scale), 0.0 if max_norm is None else float(max_norm), int(bool(skip_nonfinite)), _p(skip_in),
+                  workspace.data_ptr(), workspace.numel() * workspace.element_size(), stats.data_ptr(), flag.data_ptr(), rt.stream())
+    return stats
 
 
 def ctc_beam_search(logits, lengths, beam, tmp=1.0, lm=None, alpha=0.6, beta=1.0):

@@ -537,6 +537,22 @@ int avec_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
  * leaves parameters and moments untouched and only clears the gradient arena -- the step is skipped instead of poisoning the model state */
 int avec_adam_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
                            float weight_decay, float grad_scale, int zero_grad, long long n, const int* skip_flag, hipStream_t stream);
+/* Global L2 norm of a flat fp32 arena (16-byte aligned, n > 0, n % 4 == 0) and the clip factor of torch.nn.utils.clip_grad_norm_ (nnet/model.py:381-383), on the
+ * device: no host synchronisation, no atomics, and the same bits from every launch on the same input.  Two launches: every workgroup of the first stores one fp64
+ * partial sum of squares (each element is widened to fp64 before it is squared) into `workspace` (avec_grad_norm_workspace_bytes(n) bytes, 8-byte aligned;
+ * avec_grad_norm_blocks(n) = that launch's workgroups, capped), one workgroup of the second adds them in a fixed order and writes
+ *   stats[0] = norm = fp32(sqrt(sum) * grad_scale)      stats[1] = coef = min(1, max_norm / (norm + 1e-6f))  in fp32
+ * max_norm <= 0, infinite or NaN: coef = 1 (the norm alone).  A norm that is not finite also gives coef = 1.
+ * flag (optional, int[2]):  flag[0] = (skip_in && *skip_in != 0) || (skip_nonfinite && !isfinite(norm));  flag[1] += flag[0], the running count of skipped steps.
+ * skip_in (optional): another device flag to pass on, e.g. the SyncBatchNorm peer exchange's error flag.  Argument errors are reported before any launch. */
+long long avec_grad_norm_workspace_bytes(long long n);
+int avec_grad_norm_blocks(long long n);
+int avec_grad_norm(const float* g, long long n, float grad_scale, float max_norm, int skip_nonfinite, const int* skip_in, void* workspace, long long workspace_bytes,
+                   float* stats, int* flag, hipStream_t stream);
+/* avec_adam_step_guarded with the clip factor read on the device: clip_dev (optional) = avec_grad_norm's `stats`; the kernel scales the gradient by
+ * fp32(grad_scale * clip_dev[1]) where it used grad_scale.  NULL: avec_adam_step_guarded, bit for bit.  skip_flag takes avec_grad_norm's `flag`. */
+int avec_adam_step_clipped(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* state_dev, float beta1, float beta2, float eps,
+                           float weight_decay, float grad_scale, int zero_grad, long long n, const int* skip_flag, const float* clip_dev, hipStream_t stream);
 /* Weight averaging over two flat fp32 arenas of n elements (n > 0, n % 4 == 0; avg and p must not overlap), one launch, no atomics:
  *   mode 0: avg = p                         the first checkpoint (torch.optim.swa_utils.AveragedModel with n_averaged == 0, nnet/model.py:948-967)
  *   mode 1: avg = avg + wp * (p - avg)      swa_type "equal", wp = 1 / (n_averaged + 1); wa is ignored

@@ -1,11 +1,15 @@
 """Command-line entry point with the reference's interface (main.py:30-124 there):
 
     python main.py -c <config.py> -m training|evaluation|swa|eval_time|pass [-i checkpoint | --load_last] [--steps_per_epoch N] [--eval_steps N]
+    python main.py -c <config.py> -m training --use_graphs [--graph_bucket_frames N] [--graph_cache_size N] [--no_eval_training]
     python main.py -c <config.py> -m swa --swa_epochs FIRST LAST | --swa_epochs_list E1 E2 ... [--swa_type equal|exp] [--steps_per_epoch N]
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 main.py -c <config.py> -d        (one process per GPU, RCCL)
 
 The config is a Python file that builds `model` (an nnet.Model, already compiled) and optionally `training_dataset`, `evaluation_dataset`,
 `callback_path`, `epochs`, `precision`, `accumulated_steps`, ... exactly like configs/LRS23/AV/EffConfInterCTC.py of the reference.
+
+--use_graphs replays captured steps per batch shape (Model.fit(use_graphs=True)): the whole step when the config has accumulated_steps = 1 and no clipping, else
+forward + backward per micro-step with the optimizer tail behind the last one; a config with metrics needs --no_eval_training for the latter (metrics need the host).
 
 -m swa averages the epoch checkpoints of `callback_path`, refreshes the BatchNorm statistics over `training_dataset` (--steps_per_epoch batches; default: one pass)
 and writes checkpoints_swa-<type>-<first>-<last>.ckpt there (Model.swa)."""
@@ -50,7 +54,10 @@ def run(args):
                   precision=getattr(cfg, "precision", torch.float32), accumulated_steps=getattr(cfg, "accumulated_steps", 1),
                   eval_period_epoch=getattr(cfg, "eval_period_epoch", args.eval_period_epoch),
                   saving_period_epoch=getattr(cfg, "saving_period_epoch", args.saving_period_epoch), step_log_period=args.step_log_period,
-                  eval_training=getattr(cfg, "eval_training", not args.no_eval_training))
+                  eval_training=getattr(cfg, "eval_training", not args.no_eval_training),
+                  use_graphs=args.use_graphs or bool(getattr(cfg, "use_graphs", False)),
+                  graph_bucket_frames=args.graph_bucket_frames if args.graph_bucket_frames is not None else getattr(cfg, "graph_bucket_frames", None),
+                  graph_cache_size=args.graph_cache_size if args.graph_cache_size is not None else getattr(cfg, "graph_cache_size", 8))
     elif args.mode == "evaluation":
         loaders = dataset_eval if isinstance(dataset_eval, list) else [dataset_eval]
         for loader in loaders:
@@ -93,6 +100,9 @@ def build_parser():
     ap.add_argument("--swa_epochs", nargs="+", default=None)            # start epoch, end epoch
     ap.add_argument("--swa_epochs_list", nargs="+", default=None)       # or the epochs one by one
     ap.add_argument("--swa_type", type=str, default="equal")            # equal | exp
+    ap.add_argument("--use_graphs", action="store_true")                # replay captured steps per batch shape (Model.fit); absent: the config's `use_graphs`
+    ap.add_argument("--graph_bucket_frames", type=int, default=None)    # zero-pad AV batches to multiples of N video frames; absent: the config's `graph_bucket_frames`
+    ap.add_argument("--graph_cache_size", type=int, default=None)       # captured steps kept per model (LRU); absent: the config's `graph_cache_size`, else 8
     return ap
 
 
