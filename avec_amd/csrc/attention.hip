@@ -296,3 +296,136 @@ extern "C" int avec_relpos_attention_bwd(int dtype, const avec_attn_t* p, hipStr
   if (r) return r;
   AVEC_LAUNCH_CHECK(); return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Streaming form (nnet.ConformerStreamSession): the Tq queries of one chunk per utterance slot attend over the band  0 <= p_i - p_j <= L  of a causal stack,
+//     scores[i][j] = scale * q_i . (k_j + E[p_i - p_j]),      E [L + 1][lde]: row delta = pos_layer(PE(delta)) -- the offline table's row (T - 1) - (i - j), the same for every T.
+// Keys and values: the last L cached frames, then the chunk's own (read from the fused q | k | v rows).  The band comes from indices; a key outside it, or older than the
+// slot's restart (position < 0), is left out of the softmax -- the same sum as the offline kernel's, where such a key contributes exp(-1e9 - m) = 0 exactly.
+// Ring cache per slot: cap = L + Tq rows of H * d channels (act dtype), frame p in row p mod cap.  Slot b starts at p0 = reset[b] ? 0 : pos[b] / div and takes
+// n = ceil(chunk_len[b] / div) frames.  Window column c (0 <= c < cap) is the frame at position p0 - L + c: c < L from the ring, else chunk row c - L; query i keeps
+// column c iff 0 <= i + L - c <= L.  The workgroup of a query tile appends ITS rows (i < n) to the ring: frame p0 + i lands on the row that held frame p0 + i - cap,
+// older than p0 - L, which no query of this launch reads ((i + L - c) mod cap != 0 for 0 <= c < L) -- the tiles of a (slot, head) need no synchronisation.
+// grid (ceil(Tq / 32), B * H); online softmax, fp32 accumulation, lanes = keys (scores) then lanes = channels (P.V), as attn_rows_kernel.
+// ------------------------------------------------------------------------------------------------
+struct AttnStream {
+  const void *q, *k, *v; long long ld; const void* e; long long lde; void *kc, *vc;
+  const long long* pos; const unsigned char* reset; const long long* clen; int div;
+  void* o; long long ldo; int B, H, Tq, d, L; float scale;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void attn_stream_kernel(AttnStream a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int d = a.d, DP = d | 1, Tq = a.Tq, L = a.L, cap = L + Tq;
+  float* Ks = sm; float* Vs = Ks + TK * DP; float* Es = Vs + TK * DP; float* Qs = Es + (TQ + TK - 1) * DP; float* Ps = Qs + TQ * DP;      // Ps [TQ][64]
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
+  const int i0 = blockIdx.x * TQ;
+  long long p0 = (a.reset && a.reset[b]) ? 0 : a.pos[b] / a.div; if (p0 < 0) p0 = 0;
+  int n = Tq;
+  if (a.clen) { const long long c = (a.clen[b] + a.div - 1) / a.div; n = c < 0 ? 0 : (c > Tq ? Tq : (int)c); }
+  const long long ldc = (long long)a.H * d;
+  const T* qp = (const T*)a.q + (long long)b * Tq * a.ld + h * d;
+  const T* kp = (const T*)a.k + (long long)b * Tq * a.ld + h * d;
+  const T* vp = (const T*)a.v + (long long)b * Tq * a.ld + h * d;
+  T* kcb = (T*)a.kc + (long long)b * cap * ldc + h * d;
+  T* vcb = (T*)a.vc + (long long)b * cap * ldc + h * d;
+  const T* ep = (const T*)a.e + h * d;
+  for (int r = w; r < TQ; r += 4) {
+    const int i = i0 + r; const bool ok = i < Tq;
+    for (int c = lane; c < d; c += 64) Qs[r * DP + c] = ok ? ldf(qp + (long long)i * a.ld + c) : 0.f;
+    if (ok && i < n) {
+      const long long crow = (p0 + i) % cap;
+      for (int c = lane; c < d; c += 64) { kcb[crow * ldc + c] = kp[(long long)i * a.ld + c]; vcb[crow * ldc + c] = vp[(long long)i * a.ld + c]; }
+    }
+  }
+  float m_run[RPW], l_run[RPW], acc[RPW][NCS];
+#pragma unroll
+  for (int rr = 0; rr < RPW; ++rr) { m_run[rr] = -INFINITY; l_run[rr] = 0.f; for (int u = 0; u < NCS; ++u) acc[rr][u] = 0.f; }
+  const int i_last = min(i0 + TQ, Tq) - 1;
+  const bool wave_live = i0 + w * RPW < Tq;                    // (a chunk shorter than the tile leaves whole waves without a query)
+  for (int c0 = i0; c0 <= i_last + L; c0 += TK) {
+    __syncthreads();
+    for (int r = w; r < TK; r += 4) {
+      const int c = c0 + r; bool ok = c <= i_last + L; const T *kr = kp, *vr = vp;
+      if (c < L) { const long long p = p0 - L + c; ok = ok && p >= 0; const long long row = ok ? p % cap : 0; kr = kcb + row * ldc; vr = vcb + row * ldc; }
+      else { const int ci = c - L; ok = ok && ci < Tq; const long long row = ok ? ci : 0; kr = kp + row * a.ld; vr = vp + row * a.ld; }
+      for (int ch = lane; ch < d; ch += 64) { Ks[r * DP + ch] = ok ? ldf(kr + ch) : 0.f; Vs[r * DP + ch] = ok ? ldf(vr + ch) : 0.f; }
+    }
+    const int dmin = i0 + L - c0 - (TK - 1);                    // Es row r holds E[dmin + r]
+    for (int r = w; r < TQ + TK - 1; r += 4) {
+      const int dl = dmin + r; const bool ok = dl >= 0 && dl <= L; const T* er = ep + (long long)(ok ? dl : 0) * a.lde;
+      for (int ch = lane; ch < d; ch += 64) Es[r * DP + ch] = ok ? ldf(er + ch) : 0.f;
+    }
+    __syncthreads();
+    if (wave_live) {
+      const int c = c0 + lane;
+#pragma unroll
+      for (int rr = 0; rr < RPW; ++rr) {
+        const int ri = w * RPW + rr, i = i0 + ri; const int dl = i + L - c;
+        const bool keep = i < Tq && dl >= 0 && dl <= L && (c >= L || p0 - L + c >= 0);
+        const float* qrow = Qs + ri * DP; const float* krow = Ks + lane * DP; const float* erow = Es + (ri + TK - 1 - lane) * DP;
+        float s = 0.f;
+        for (int ch = 0; ch < d; ++ch) s += qrow[ch] * (krow[ch] + erow[ch]);
+        s *= a.scale;
+        const float tmax = wave_max(keep ? s : -INFINITY);
+        const float m_new = fmaxf(m_run[rr], tmax);
+        float pval = 0.f;
+        if (m_new != -INFINITY) {                               // (no kept key so far in this row: nothing to rescale, nothing to add)
+          const float alpha = (m_run[rr] == -INFINITY) ? 0.f : __expf(m_run[rr] - m_new);
+          pval = keep ? __expf(s - m_new) : 0.f;
+          l_run[rr] = l_run[rr] * alpha + wave_sum(pval);
+          for (int u = 0; u < NCS; ++u) acc[rr][u] *= alpha;
+          m_run[rr] = m_new;
+        }
+        Ps[ri * 64 + lane] = pval;
+      }
+    }
+    __syncthreads();
+    if (wave_live) {
+#pragma unroll
+      for (int rr = 0; rr < RPW; ++rr) {
+        const float* prow = Ps + (w * RPW + rr) * 64;
+        for (int jj = 0; jj < TK; ++jj) {
+          const float pj = prow[jj];
+#pragma unroll
+          for (int u = 0; u < NCS; ++u) if (lane + 64 * u < d) acc[rr][u] += pj * Vs[jj * DP + lane + 64 * u];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < RPW; ++rr) {
+    const int i = i0 + w * RPW + rr;
+    if (i >= Tq) continue;
+    const float inv = 1.f / l_run[rr];                          // l > 0: a query always keeps its own frame
+    T* op = (T*)a.o + ((long long)b * Tq + i) * a.ldo + h * d;
+#pragma unroll
+    for (int u = 0; u < NCS; ++u) if (lane + 64 * u < d) stf(op + lane + 64 * u, acc[rr][u] * inv);
+  }
+}
+
+extern "C" long long avec_relpos_attention_stream_state_bytes(int dtype, int B, int H, int d, int L, int Tq) {
+  if (B <= 0 || H <= 0 || d <= 0 || L < 0 || Tq <= 0) return 0;
+  return (long long)B * (L + Tq) * H * d * (dtype == AVEC_BF16 ? 2 : 4);
+}
+extern "C" int avec_relpos_attention_stream(int dtype, const void* q, const void* k, const void* v, long long ld, const void* e, long long lde, void* kcache, void* vcache,
+                                            long long cache_bytes, const long long* pos, const unsigned char* reset, const long long* chunk_len, int div, void* o, long long ldo,
+                                            int B, int H, int Tq, int d, int L, float scale, hipStream_t st) {
+  AVEC_CHECK_ARG(q && k && v && e && kcache && vcache && pos && o, "relpos_attention_stream: null pointer (q, k, v, e, kcache, vcache, pos and o are required)");
+  AVEC_CHECK_ARG(B > 0 && H > 0 && Tq > 0 && L >= 0 && div > 0 && d > 0 && d <= 64 * NCS, "relpos_attention_stream: bad dims B=%d H=%d Tq=%d d=%d L=%d div=%d (d <= %d)", B, H, Tq, d, L, div, 64 * NCS);
+  AVEC_CHECK_ARG(ld >= (long long)H * d && ldo >= (long long)H * d && lde >= (long long)H * d, "relpos_attention_stream: row strides ld=%lld ldo=%lld lde=%lld below H * d = %d", ld, ldo, lde, H * d);
+  const long long need = avec_relpos_attention_stream_state_bytes(dtype, B, H, d, L, Tq);
+  AVEC_CHECK_ARG(cache_bytes >= need, "relpos_attention_stream: key / value rings of %lld bytes each, %lld needed (avec_relpos_attention_stream_state_bytes)", cache_bytes, need);
+  const uintptr_t em = dtype == AVEC_BF16 ? 1 : 3;             // element accesses only (odd head widths): element alignment
+  AVEC_CHECK_ARG(!(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)e | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)o) & em) && !(((uintptr_t)pos | (uintptr_t)chunk_len) & 7),
+                 "relpos_attention_stream: misaligned pointer (tensors: element size, pos / chunk_len: 8 bytes)");
+  AVEC_CHECK_ARG(kcache != vcache, "relpos_attention_stream: kcache and vcache must be two buffers");
+  AttnStream a{q, k, v, ld, e, lde, kcache, vcache, pos, reset, chunk_len, div, o, ldo, B, H, Tq, d, L, scale};
+  const int DP = d | 1; const size_t lds = (size_t)(2 * TK + (TQ + TK - 1) + TQ) * DP * 4 + (size_t)TQ * 64 * 4;
+  dim3 grid((Tq + TQ - 1) / TQ, B * H);
+  avec_note_kernel("attn_stream<%s>", dtype == AVEC_BF16 ? "bf16" : "f32");
+  if (dtype == AVEC_BF16) { if (int r = avec_lds_optin(attn_stream_kernel<bf16>, lds)) return r; hipLaunchKernelGGL((attn_stream_kernel<bf16>), grid, dim3(256), lds, st, a); }
+  else { if (int r = avec_lds_optin(attn_stream_kernel<float>, lds)) return r; hipLaunchKernelGGL((attn_stream_kernel<float>), grid, dim3(256), lds, st, a); }
+  AVEC_LAUNCH_CHECK(); return 0;
+}

@@ -382,3 +382,111 @@ extern "C" int avec_dwconv_glu_bwd(int dtype, const void* dc, const void* u, con
   AVEC_LAUNCH_CHECK();
   return dw_finish(plan, dw, dbias, C, K, st);
 }
+
+// ================================================================================================================================================================
+// Streaming form (nnet.ConformerStreamSession): GLU -> causal depthwise conv (stride s) -> eval-mode BatchNorm scale / shift -> Swish of ONE chunk of Tq frames per
+// utterance slot, on the concatenation [carried left context | chunk].  The carried context is the last K - 1 rows of u (pre-GLU, 2C channels, act dtype) of the
+// slot: the convolution reads exactly the operands avec_glu_dwconv_fwd reads offline, taps in the same order, fp32 accumulation.
+//   slot b starts at stage position p0 = reset[b] ? 0 : pos[b] / div and takes n = ceil(chunk_len[b] / div) (<= Tq) frames; a context row whose position
+//   p0 - (K - 1) + r is negative is absent (a zero GLU output: the causal zero padding) whatever the buffer holds -- a reset costs no memset.
+//   output row o (< To = Tq / s) is the frame at chunk position o * s = global position p0 + o * s (a multiple of s, where the offline To = (T - 1) / s + 1 puts it).
+//   new context = the last K - 1 rows of [old context | first n chunk rows]; rows at or beyond n never enter it.
+// Workgroup = (128-channel slab, slot): it owns the slab's columns of the slot's context rows alone.  State ordering: every read of the old context (the GLU staging
+// pass and the rows that move up into the new context, kept in registers) happens BEFORE the workgroup barrier, every write of the new context AFTER it, and no
+// other workgroup touches these columns of this slot: in place without a race.
+// ================================================================================================================================================================
+template <typename T>
+__global__ __launch_bounds__(256) void glu_dwconv_stream_kernel(const T* __restrict__ u, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ ss,
+                                                                T* __restrict__ out, T* state, const long long* __restrict__ pos, const unsigned char* __restrict__ reset,
+                                                                const long long* __restrict__ clen, int div, int Tq, int C, int K, int stride, int To) {
+  extern __shared__ __attribute__((aligned(16))) float gs[];         // [(K - 1) + Tq][128] GLU outputs, row r = chunk position r - (K - 1)
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5; const int col = (blockIdx.x * 32 + tx) * 4; const int b = blockIdx.y;
+  const int Hn = K - 1;
+  long long p0 = (reset && reset[b]) ? 0 : pos[b] / div; if (p0 < 0) p0 = 0;
+  int n = Tq;
+  if (clen) { long long c = (clen[b] + div - 1) / div; n = c < 0 ? 0 : (c > Tq ? Tq : (int)c); }
+  const bool live = col < C; const int cc = live ? col : 0;
+  float ww[KMAX][4], bb[4] = {0.f, 0.f, 0.f, 0.f}, sc[4], sh[4];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) { if (k < K) ld4<float>(w + (long long)k * C + cc, ww[k]); else ww[k][0] = ww[k][1] = ww[k][2] = ww[k][3] = 0.f; }
+  if (bias) ld4<float>(bias + cc, bb);
+  ld4<float>(ss + cc, sc); ld4<float>(ss + C + cc, sh);
+  T* const sb = state + (long long)b * Hn * 2 * C;
+  const T* const ub = u + (long long)b * Tq * 2 * C;
+  for (int r = ty; r < Hn + Tq; r += 8) {
+    const bool ctx = r < Hn; const bool ok = live && (!ctx || p0 - Hn + r >= 0);
+    const T* row = ctx ? sb + (long long)r * 2 * C : ub + (long long)(r - Hn) * 2 * C;
+    float a[4], g[4]; ld4<T>(row + cc, a); ld4<T>(row + C + cc, g);
+    *(float4*)(gs + r * 128 + tx * 4) = ok ? make_float4(a[0] * sigmoidf_(g[0]), a[1] * sigmoidf_(g[1]), a[2] * sigmoidf_(g[2]), a[3] * sigmoidf_(g[3])) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  // new context row r = old row r + n (while that is a context row) or chunk row n - Hn + r: at most two rows per thread, read before the barrier
+  float na[2][4], nb[2][4];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = ty + 8 * q;
+    if (r < Hn && n > 0) {
+      const int src = r + n; const T* row = src < Hn ? sb + (long long)src * 2 * C : ub + (long long)(src - Hn) * 2 * C;
+      ld4<T>(row + cc, na[q]); ld4<T>(row + C + cc, nb[q]);
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = ty + 8 * q;
+    if (r < Hn && n > 0) { st4<T>(sb + (long long)r * 2 * C + col, na[q]); st4<T>(sb + (long long)r * 2 * C + C + col, nb[q]); }
+  }
+  for (int o = ty; o < To; o += 8) {
+    float acc[4] = {bb[0], bb[1], bb[2], bb[3]};
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if (k < K) {
+        const float4 g = *(const float4*)(gs + (o * stride + k) * 128 + tx * 4);
+        acc[0] += ww[k][0] * g.x; acc[1] += ww[k][1] * g.y; acc[2] += ww[k][2] * g.z; acc[3] += ww[k][3] * g.w;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = swishf_(acc[e] * sc[e] + sh[e]);
+    st4<T>(out + ((long long)b * To + o) * C + col, acc);
+  }
+}
+
+extern "C" long long avec_glu_dwconv_stream_state_bytes(int dtype, int B, int C, int K) {
+  if (B <= 0 || C <= 0 || K <= 0) return 0;
+  return (long long)B * (K - 1) * 2 * C * (dtype == AVEC_BF16 ? 2 : 4);
+}
+extern "C" int avec_glu_dwconv_stream(int dtype, const void* u, const float* w, const float* bias, const float* ss, void* out, void* state, long long state_bytes,
+                                      const long long* pos, const unsigned char* reset, const long long* chunk_len, int div, int B, int Tq, int C, int K, int stride, hipStream_t st) {
+  AVEC_CHECK_ARG(u && w && ss && out && pos, "glu_dwconv_stream: null pointer (u, w, ss, out and pos are required)");
+  AVEC_CHECK_ARG(B > 0 && Tq > 0 && div > 0 && stride > 0 && Tq % stride == 0, "glu_dwconv_stream: bad dims B=%d Tq=%d div=%d stride=%d (Tq must be a multiple of the stride)", B, Tq, div, stride);
+  AVEC_CHECK_ARG(C > 0 && C % 4 == 0, "glu_dwconv_stream: C=%d must be a positive multiple of 4 (4-channel vector accesses)", C);
+  AVEC_CHECK_ARG(K > 0 && K <= KMAX, "glu_dwconv_stream: kernel size K=%d outside 1..%d", K, KMAX);
+  AVEC_CHECK_ARG(K == 1 || state, "glu_dwconv_stream: null state (K=%d needs %d context rows per slot)", K, K - 1);
+  AVEC_CHECK_ARG(state_bytes >= avec_glu_dwconv_stream_state_bytes(dtype, B, C, K), "glu_dwconv_stream: state of %lld bytes, %lld needed (avec_glu_dwconv_stream_state_bytes)",
+                 state_bytes, avec_glu_dwconv_stream_state_bytes(dtype, B, C, K));
+  // 16-byte aligned bases: with C % 4 == 0 every fp32 access is then a whole aligned 16-byte chunk and every bf16 access an aligned 8-byte one (4 channels)
+  AVEC_CHECK_ARG(avec_aligned16(u) && avec_aligned16(w) && avec_aligned16(bias) && avec_aligned16(ss) && avec_aligned16(out) && avec_aligned16(state),
+                 "glu_dwconv_stream: u, w, bias, ss, out and state must be 16-byte aligned");
+  AVEC_CHECK_ARG((((uintptr_t)pos) & 7) == 0 && (((uintptr_t)chunk_len) & 7) == 0, "glu_dwconv_stream: pos and chunk_len must be 8-byte aligned (int64)");
+  const size_t lds = (size_t)(K - 1 + Tq) * 128 * sizeof(float);
+  AVEC_CHECK_ARG(lds <= 48 * 1024, "glu_dwconv_stream: chunk of %d frames too long (K - 1 + Tq <= 96)", Tq);
+  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)B);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(glu_dwconv_stream_kernel<T>, grid, dim3(256), lds, st, (const T*)u, w, bias, ss, (T*)out, (T*)state, pos, reset, chunk_len, div, Tq, C, K, stride, Tq / stride));
+  AVEC_LAUNCH_CHECK();
+  return 0;
+}
+// end of a push: pos[b] = (reset[b] ? 0 : pos[b]) + min(chunk_len[b], full)   (chunk_len NULL: full), then reset[b] = 0: the flags are consumed, the caller sets only
+// those of the next push (no clearing copy or memset after a restart).  One launch per push whether or not a slot restarts; the last reader of pos / reset in the push.
+__global__ void stream_advance_kernel(long long* pos, unsigned char* reset, const long long* clen, long long full, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  long long c = clen ? clen[b] : full; c = c < 0 ? 0 : (c > full ? full : c);
+  pos[b] = ((reset && reset[b]) ? 0 : pos[b]) + c;
+  if (reset) reset[b] = 0;
+}
+extern "C" int avec_stream_advance(long long* pos, unsigned char* reset, const long long* chunk_len, long long full, int B, hipStream_t st) {
+  AVEC_CHECK_ARG(pos && B > 0 && full > 0 && (((uintptr_t)pos) & 7) == 0 && (((uintptr_t)chunk_len) & 7) == 0, "stream_advance: bad arguments (B=%d full=%lld)", B, full);
+  hipLaunchKernelGGL(stream_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, pos, reset, chunk_len, full, B);
+  AVEC_LAUNCH_CHECK();
+  return 0;
+}

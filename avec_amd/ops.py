@@ -2204,3 +2204,70 @@ def lm_rescore(model, ids, lens, beam_score, alpha, beta, B):
     best = torch.empty(B, dtype=torch.int64, device=dev)
     lib.lm_rescore_select(neural.data_ptr(), lens.data_ptr(), beam.data_ptr(), float(alpha), float(beta), B, K, total.data_ptr(), best.data_ptr(), rt.stream())
     return best, total.view(B, K), neural.view(B, K)
+
+
+# ============================================================================================
+# Streaming encoder (nnet.ConformerStreamSession): the two stateful kernels of a causal Conformer stack run chunk by chunk (include/avec_hip.h)
+# ============================================================================================
+def _stream_ctl(name, pos, reset, chunk_len, B):
+    if not (pos.dtype == torch.int64 and pos.is_cuda and pos.is_contiguous() and pos.numel() == B):
+        raise ValueError("%s: pos must be a contiguous int64 tensor [%d] on the device" % (name, B))
+    if reset is not None and not (reset.device == pos.device and reset.is_contiguous() and reset.numel() == B and reset.dtype in (torch.uint8, torch.bool)):
+        raise ValueError("%s: reset must be a contiguous uint8 / bool mask [%d] on the device" % (name, B))
+    if chunk_len is not None and not (chunk_len.dtype == torch.int64 and chunk_len.device == pos.device and chunk_len.is_contiguous() and chunk_len.numel() == B):
+        raise ValueError("%s: chunk_len must be a contiguous int64 tensor [%d] on the device" % (name, B))
+
+
+def glu_dwconv_stream_state(B, C, K, device):
+    """zero-filled left context of ops.glu_dwconv_stream: [B, K - 1, 2C] in the activation dtype"""
+    return torch.zeros(B, K - 1, 2 * C, dtype=rt.act_dtype(), device=device)
+
+
+def glu_dwconv_stream(u, w, bias, ss, state, pos, reset=None, chunk_len=None, div=1, stride=1):
+    """One chunk of the convolution module's middle: Swish(BatchNorm_eval(depthwise_causal(GLU([carried context | u])))) in one launch.  u [B, Tq, 2C] act (the
+    pointwise conv's output), w the depthwise weight (tap-major [K][C] in memory), ss the eval-mode scale | shift of the BatchNorm ([>= 2C] fp32, ops.bn_finalize),
+    state [B, K - 1, 2C] act, updated in place; pos / reset / chunk_len / div as include/avec_hip.h.  Returns [B, Tq / stride, C] act.  No synchronisation."""
+    rt.require_gpu(u)
+    B, Tq, C2 = u.shape
+    C, K = C2 // 2, w.shape[-1]
+    adt = rt.act_dtype()
+    if not (u.dtype == adt and u.is_contiguous() and state.dtype == adt and state.is_contiguous() and ss.dtype == torch.float32 and ss.numel() >= 2 * C):
+        raise ValueError("glu_dwconv_stream: u and state contiguous in the activation dtype %s, ss fp32 [>= 2C] (got %s, %s, %s)" % (adt, u.dtype, state.dtype, ss.dtype))
+    _stream_ctl("glu_dwconv_stream", pos, reset, chunk_len, B)
+    if Tq % stride:
+        raise ValueError("glu_dwconv_stream: %d frames per chunk is not a multiple of the stride %d" % (Tq, stride))
+    out = empty((B * (Tq // stride), C), adt, u)
+    lib.glu_dwconv_stream(rt.dt(), u.data_ptr(), w.data_ptr(), _p(bias), ss.data_ptr(), out.data_ptr(), state.data_ptr() if state.numel() else None,
+                          state.numel() * state.element_size(), pos.data_ptr(), _p(reset), _p(chunk_len), int(div), B, Tq, C, K, int(stride), rt.stream())
+    return out.view(B, Tq // stride, C)
+
+
+def relpos_attention_stream_state(B, H, d, L, Tq, device):
+    """the key and value rings of ops.relpos_attention_stream: two [B, L + Tq, H * d] tensors in the activation dtype"""
+    return (torch.zeros(B, L + Tq, H * d, dtype=rt.act_dtype(), device=device), torch.zeros(B, L + Tq, H * d, dtype=rt.act_dtype(), device=device))
+
+
+def relpos_attention_stream(qkv, e, kcache, vcache, pos, reset=None, chunk_len=None, div=1, *, B, H, L):
+    """Relative-position attention of one chunk over the band 0 <= p_i - p_j <= L.  qkv [B * Tq, 3D] act (the fused q | k | v projection of the chunk), e [L + 1, D] act
+    (row delta = pos_layer(PE(delta)), possibly a column slice), kcache / vcache [B, L + Tq, D] act rings (the chunk's rows are appended).  Returns o [B * Tq, D] act."""
+    rt.require_gpu(qkv)
+    M, D3 = qkv.shape
+    D, Tq = D3 // 3, M // B
+    d, adt = D // H, rt.act_dtype()
+    if not (qkv.dtype == adt and qkv.is_contiguous() and e.dtype == adt and e.shape[0] == L + 1 and e.stride(1) == 1 and kcache.dtype == adt and vcache.dtype == adt
+            and kcache.is_contiguous() and vcache.is_contiguous() and tuple(kcache.shape) == tuple(vcache.shape) == (B, L + Tq, D) and B * Tq == M and H * d == D):
+        raise ValueError("relpos_attention_stream: qkv [B Tq, 3D], e [L + 1, D], kcache / vcache [B, L + Tq, D] in the activation dtype %s (got %s %s, %s %s, %s %s)"
+                         % (adt, tuple(qkv.shape), qkv.dtype, tuple(e.shape), e.dtype, tuple(kcache.shape), kcache.dtype))
+    _stream_ctl("relpos_attention_stream", pos, reset, chunk_len, B)
+    o = empty((M, D), adt, qkv)
+    esz = qkv.element_size()
+    lib.relpos_attention_stream(rt.dt(), qkv.data_ptr(), qkv.data_ptr() + D * esz, qkv.data_ptr() + 2 * D * esz, 3 * D, e.data_ptr(), e.stride(0), kcache.data_ptr(), vcache.data_ptr(),
+                                kcache.numel() * esz, pos.data_ptr(), _p(reset), _p(chunk_len), int(div), o.data_ptr(), D, B, H, Tq, d, L, 1.0 / d ** 0.5, rt.stream())
+    return o
+
+
+def stream_advance(pos, reset, chunk_len, full):
+    """end of a push: pos = (reset ? 0 : pos) + min(chunk_len, full) in place, and the reset flags are cleared (consumed); one launch"""
+    _stream_ctl("stream_advance", pos, reset, chunk_len, pos.numel())
+    lib.stream_advance(pos.data_ptr(), _p(reset), _p(chunk_len), int(full), pos.numel(), rt.stream())
+    return pos

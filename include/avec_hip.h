@@ -309,6 +309,30 @@ typedef struct avec_attn {
 int avec_relpos_attention_fwd(int dtype, const avec_attn_t* args, hipStream_t stream);
 int avec_relpos_attention_bwd(int dtype, const avec_attn_t* args, hipStream_t stream);
 
+/* ---- streaming encoder (nnet.ConformerStreamSession; avec_amd/csrc/convmod.hip, attention.hip) ---------------------------------------------------------------
+ * A causal Conformer stack run chunk by chunk: everything row-wise reuses the offline entry points; these two carry the depthwise convolution's left context
+ * and the attention's keys / values across launches in caller-owned buffers.  The library keeps no pointers between calls; nothing here synchronises.
+ * Common arguments: pos [B] int64 on the device = frames (at the stack's input rate) slot b has taken since its restart, BEFORE this chunk; reset [B] bytes
+ * (NULL: none): a set slot restarts from position 0 before the chunk -- whatever its buffers hold is then older than the restart and counts as absent (no memset);
+ * chunk_len [B] int64 (NULL: the whole chunk) = input-rate frames of the chunk the slot takes; div = product of the strides in front of this stage.  At this
+ * stage a slot starts at p0 = pos / div and takes n = ceil(chunk_len / div) <= Tq rows; rows at or beyond n are computed from what was passed and never reach the
+ * carried state.  avec_stream_advance ends a push: pos = (reset ? 0 : pos) + min(chunk_len, full), then clears the reset flags (they are consumed).
+ *
+ * avec_glu_dwconv_stream: GLU -> causal depthwise conv (K <= 16 taps, stride s, w tap-major [K][C], optional bias) -> y * ss[c] + ss[C + c] (eval-mode BatchNorm,
+ *   the scale | shift of avec_bn_finalize) -> Swish, one launch.  u [B][Tq][2C] act -> out [B][Tq / s][C] act, output row o = chunk row o * s.  state: per slot the
+ *   last K - 1 rows of u ([B][K - 1][2C] act, avec_glu_dwconv_stream_state_bytes), updated in place.  C % 4 == 0, all bases 16-byte aligned, K - 1 + Tq <= 96.
+ * avec_relpos_attention_stream: the chunk's Tq queries over the band 0 <= p_i - p_j <= L:  scores = scale * q_i . (k_j + E[p_i - p_j]), E [L + 1][lde] (row delta =
+ *   pos_layer(PE(delta))); q / k / v rows of the chunk with row stride ld, head h in columns [h * d, (h + 1) * d); kcache / vcache: rings of L + Tq rows of H * d channels
+ *   per slot (act, avec_relpos_attention_stream_state_bytes EACH), frame p in row p mod (L + Tq); the chunk's first n rows are appended.  o [B * Tq][ldo] act.  d <= 192. */
+long long avec_glu_dwconv_stream_state_bytes(int dtype, int B, int C, int K);
+int avec_glu_dwconv_stream(int dtype, const void* u, const float* w, const float* bias, const float* ss, void* out, void* state, long long state_bytes,
+                           const long long* pos, const unsigned char* reset, const long long* chunk_len, int div, int B, int Tq, int C, int K, int stride, hipStream_t stream);
+long long avec_relpos_attention_stream_state_bytes(int dtype, int B, int H, int d, int L, int Tq);
+int avec_relpos_attention_stream(int dtype, const void* q, const void* k, const void* v, long long ld, const void* e, long long lde, void* kcache, void* vcache,
+                                 long long cache_bytes, const long long* pos, const unsigned char* reset, const long long* chunk_len, int div, void* o, long long ldo,
+                                 int B, int H, int Tq, int d, int L, float scale, hipStream_t stream);
+int avec_stream_advance(long long* pos, unsigned char* reset, const long long* chunk_len, long long full, int B, hipStream_t stream);
+
 /* ---- front-ends (avec_amd/csrc/frontend.hip) ------------------------------------------------ */
 /* AudioPreprocessing (nnet/preprocessing.py:57-85; torchaudio Spectrogram/MelScale restated): frames -> [DFT via avec_gemm_nt fp32] -> power/mel/log */
 int avec_mel_frames(const float* audio, const float* window, float* frames, int B, long long L, int n_fft, int win, int hop, hipStream_t stream);
