@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from .. import ops
 from .. import runtime as rt
+from .captured import CapturedStep, StepCache
 from .decoders import decoder_dict
 from .losses import loss_dict
 from .metrics import metric_dict
@@ -31,6 +32,8 @@ class Model(Module):
         self.skip_nonfinite_steps = False      # skip an optimizer step whose global gradient norm is NaN or infinite (what the reference's GradScaler does under fp16)
         self.arena = None
         self.world_size = 1
+        self.captured_steps = StepCache()      # graphed_train_step / graphed_micro_step: captured steps per batch shape
+        self.eager_fallback, self._eager_fallback_said = None, False       # why graphed_micro_step ran train_step instead (fit says so once)
 
     @staticmethod
     def _pre_forward(model, _args):
@@ -98,10 +101,10 @@ class Model(Module):
         The copy lives outside the module tree (no state_dict keys), has its OWN ParamArena laid out like the model's, and no optimizer.  Its buffers are
         the model's as of the last sync_ema_buffers() (save, fit's evaluation and this call do it); the reference copies them after every step, which is
         the same observable state."""
-        # what must not be cloned: the arena (the copy gets its own), the optimizer and its moments, captured graphs, an earlier EMA model.  What is shared,
-        # as the reference's build() shares it: losses, loss weights, decoders, metrics, and the step counter the loss-weight schedules read
+        # what must not be cloned: the arena (the copy gets its own), the optimizer and its moments, an earlier EMA model, captured steps (a StepCache copies as an
+        # empty one).  What is shared, as the reference's build() shares it: losses, loss weights, decoders, metrics, and the step counter the loss-weight schedules read
         memo = {}
-        for name in ("arena", "optimizer", "ema_model", "_graph_cache"):
+        for name in ("arena", "optimizer", "ema_model"):
             if self.__dict__.get(name) is not None:
                 memo[id(self.__dict__[name])] = None
         for name in ("compiled_losses", "compiled_loss_weights", "compiled_metrics", "compiled_decoders", "losses", "loss_weights", "decoders", "metrics", "model_step"):
@@ -117,14 +120,13 @@ class Model(Module):
                 rt.register_weight(q, sh.A, sh.Tm, sh.C, sh.need_bwd, sh.Cp)
         for m in ema.modules():
             m._load_state_dict_post_hooks.clear()       # (the copied hooks mark THIS model's arena stale; the copy's arena registers its own)
-        ema.__dict__.pop("_graph_evictions", None)
         ema.requires_grad_(False)
         ema.eval()
         if self.arena is not None:
             ema.to(self.device)
         object.__setattr__(self, "ema_model", ema)
         self.ema_tau = float(ema_tau)
-        self.__dict__.pop("_graph_cache", None)          # steps captured so far have no EMA launch in them
+        self.captured_steps.clear()                      # whole steps captured so far have no EMA launch in them
         self._check_ema_layout()
 
     def _check_ema_layout(self):
@@ -278,7 +280,7 @@ class Model(Module):
         rt.set_compute_dtype(precision)
         rt.reset_zero_pool(self.device)
         if self.is_distributed and self.arena is not None:       # overlap part of the gradient exchange with the backward pass of the last micro-step
-            self.arena.arm_early_all_reduce(acc_step + 1 >= accumulated_steps and os.environ.get("AVEC_EARLY_ALLREDUCE", "1") != "0")
+            self.arena.arm_early_all_reduce(acc_step + 1 >= accumulated_steps and rt.early_all_reduce_enabled())
         batch_losses, batch_metrics, _, _ = self.forward_model(inputs, targets, compute_metrics=eval_training)
         (batch_losses["loss"] / accumulated_steps).backward()
         rt.advance_rng(self.device)
@@ -290,31 +292,37 @@ class Model(Module):
         return batch_losses, batch_metrics, 0
 
     def _finish_optimizer_step(self):
-        """what follows the last micro-step's backward pass, as eager launches without host synchronisation: gradient all-reduce (data parallel), the global norm and
-        clip factor on the device (grad_max_norm / skip_nonfinite_steps: ops.grad_norm, read by the optimizer launch), the optimizer launch, the EMA launch, the infos.
+        """what follows the last micro-step's backward pass, as eager launches without host synchronisation: the optimizer's host half (scheduler, {step, lr} to the
+        device), the device half (_launch_optimizer_tail, with the global norm and clip factor under grad_max_norm / skip_nonfinite_steps), the infos.
         The host never reads the guard's flag, so on a skipped step everything but the optimizer launch still happens: the scheduler and model_step advance, and
         the EMA model takes one more step toward parameters that did not change.  infos["skipped_steps"] counts since the optimizer's flat state was allocated: it
         is not saved in checkpoints and starts at 0 again after Adam.load_state_dict."""
+        guard = bool(self.skip_nonfinite_steps)
+        clip = self.grad_max_norm is not None or guard
+        if clip and (self.arena is None or not hasattr(self.optimizer, "launch_grad_norm")):
+            raise RuntimeError("gradient clipping and the non-finite guard run on the flat gradient arena on the GPU with nnet.Adam: move the model with Model.to('cuda') first")
+        self.optimizer.prepare_step()
+        stats = self._launch_optimizer_tail(clip)
+        if clip:
+            self.add_info("grad_norm", stats[0])              # device scalars: turned into numbers only where fit prints
+            if guard:
+                self.add_info("skipped_steps", self.optimizer.skipped_steps)
+        self.optimizer.zero_grad()
+        self.add_info("lr", float(self.optimizer.param_groups[0]["lr"]))
+        self.add_info("step", int(self.model_step))
+
+    def _launch_optimizer_tail(self, clip=False):
+        """device half of an optimizer step, graph-capturable (no host synchronisation, no host state but the arenas' dirty marks): gradient all-reduce (data parallel;
+        the 1 / world factor goes into the optimizer launch), the global norm and clip factor on the device when `clip` (ops.grad_norm, read by the optimizer launch),
+        the optimizer launch, the EMA launch.  optimizer.prepare_step() must have run since the last one.  Returns the norm launch's {norm, coef} pair or None."""
         if self.is_distributed:
             # the reference all-reduces on every micro-batch (no no_sync); summing once per optimizer step is numerically the same
             self.arena.all_reduce_grads()
             self.optimizer.grad_scale = 1.0 / self.world_size
-        guard = bool(getattr(self, "skip_nonfinite_steps", False))
-        clip = self.grad_max_norm is not None or guard
-        if clip:
-            if self.arena is None or not hasattr(self.optimizer, "launch_grad_norm"):
-                raise RuntimeError("gradient clipping and the non-finite guard run on the flat gradient arena on the GPU with nnet.Adam: move the model with Model.to('cuda') first")
-            stats = self.optimizer.launch_grad_norm(self.grad_max_norm, guard)
-            self.add_info("grad_norm", stats[0])              # device scalars: turned into numbers only where fit prints
-            if guard:
-                self.add_info("skipped_steps", self.optimizer.skipped_steps)
-            self.optimizer.step(clip=True)
-        else:
-            self.optimizer.step()
+        stats = self.optimizer.launch_grad_norm(self.grad_max_norm, bool(self.skip_nonfinite_steps)) if clip else None
+        self.optimizer.launch_step(clip)
         self._update_ema()
-        self.optimizer.zero_grad()
-        self.add_info("lr", float(self.optimizer.param_groups[0]["lr"]))
-        self.add_info("step", int(self.model_step))
+        return stats
 
     def clip_gradients(self, max_norm):
         """global-norm clipping of the flat gradient arena (torch.nn.utils.clip_grad_norm_ semantics, nnet/model.py:381-383); returns the norm before clipping"""
@@ -331,75 +339,48 @@ class Model(Module):
           replay.  Requires the peer exchange (otherwise every BatchNorm layer needs a host-issued collective: use train_step)."""
         from .. import peer
         dist_mode = self.is_distributed
+        nccl = dist_mode and torch.distributed.get_backend() == "nccl"
         # RCCL collectives are capturable: over the nccl backend the WHOLE data-parallel step -- SyncBatchNorm exchanges (peer writes, or RCCL when the peer exchange is
         # off / refused), the range-wise gradient all-reduce (fusion + audio-visual ranges when the gradient crosses the fusion inputs, the audio encoder's from the audio
-        # branch's stream beside the visual backward, the visual encoder's at the end) and the Adam launch -- is ONE hipGraph.  AVEC_GRAPH_ALLREDUCE=0: all-reduce and
-        # Adam follow the replay (the round-3 behaviour; also what gloo debugging runs use).
-        in_graph = dist_mode and torch.distributed.get_backend() == "nccl" and os.environ.get("AVEC_GRAPH_ALLREDUCE", "1") != "0"
+        # branch's stream beside the visual backward, the visual encoder's at the end) and the Adam launch -- is ONE hipGraph, unless rt.graph_all_reduce_enabled() says no.
+        in_graph = nccl and rt.graph_all_reduce_enabled()
         assert not dist_mode or in_graph or peer.active() is not None, "graph capture of a data-parallel step needs capturable SyncBatchNorm exchanges (RCCL, or the peer exchange); use train_step"
         rt.set_compute_dtype(precision)
-        warmup = max(int(warmup), 1)                        # lazily created constants (DFT matrix, sinusoid tables, loss weights) must exist before the capture
-        static_in = [t.clone() for t in inputs]
-        static_tg = tuple(t.clone() for t in targets)
+        cap = CapturedStep(inputs, targets)
         if dist_mode:
             self.arena.arm_early_all_reduce(False)          # (armed per pass inside body() when the collectives are captured)
-        state = {"in_graph": in_graph}
+        tail_in_graph = [not dist_mode or in_graph]         # else (data parallel without captured collectives) the optimizer tail follows the replay
 
         def body():
             rt.reset_zero_pool(self.device)
-            if dist_mode and state["in_graph"]:
-                self.arena.arm_early_all_reduce(os.environ.get("AVEC_EARLY_ALLREDUCE", "1") != "0", sync=True)
-            losses, _, _, _ = self.forward_model(static_in, static_tg, compute_metrics=False)
+            if dist_mode and tail_in_graph[0]:
+                self.arena.arm_early_all_reduce(rt.early_all_reduce_enabled(), sync=True)     # sync holds until the tail's all_reduce_grads: every collective is captured
+            losses, _, _, _ = self.forward_model(cap.inputs, cap.targets, compute_metrics=False)
             ops.stamp("loss_done:f")
             losses["loss"].backward()
             ops.stamp("bwd_done:b")
             rt.advance_rng(self.device)
-            if not dist_mode:
-                self.optimizer.launch_step()
-                self._update_ema()
-            elif state["in_graph"]:
-                self.arena._sync_collectives = True
-                self.arena.all_reduce_grads()
-                self.optimizer.grad_scale = 1.0 / self.world_size
-                self.optimizer.launch_step()
-                self._update_ema()
+            if tail_in_graph[0]:
+                self._launch_optimizer_tail()
             return losses
 
-        def finish():                                       # data parallel without captured collectives: average the gradients, then the optimizer launch
-            if dist_mode and not state["in_graph"]:
-                self.arena.all_reduce_grads()
-                self.optimizer.grad_scale = 1.0 / self.world_size
-                self.optimizer.launch_step()
-                self._update_ema()
+        def run(inner):                                     # one optimisation step around the eager body (warm-up) or the replay
+            self.optimizer.prepare_step()                   # (the optimizer's device-side {step, lr} pair is written OUTSIDE the graph, before every pass)
+            losses = inner()
+            if not tail_in_graph[0]:
+                self._launch_optimizer_tail()
+            return losses
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        warm = None
-        with torch.cuda.stream(side):
-            for _ in range(warmup):             # warm-up on a side stream: lazy kernel attributes, caches, allocator
-                self.optimizer.prepare_step()
-                warm = body()
-                finish()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        # data parallel: the process group's watchdog thread polls the events of collectives it still tracks (hipEventQuery, every ~100 ms); under a "global"-mode capture
-        # such a poll is a capture violation and aborts the process, and in "thread_local" mode HIP reports the backward pass's collectives (issued from the autograd
-        # thread) as not capturing, so they ARE tracked and their captured events get polled.  So: global mode, and the watchdog's list drained before the capture starts
-        # (everything issued so far has completed -- synchronize above -- and is reaped within one watchdog period).
-        gkw = {}
-        if dist_mode and torch.distributed.get_backend() == "nccl":
-            torch.cuda.synchronize()
-            time.sleep(0.6)
+        # lazily created constants (DFT matrix, sinusoid tables, loss weights) must exist before the capture: at least one eager pass
+        warm = cap.warm_up(lambda: run(body), max(int(warmup), 1))
         cap_err = None
         try:
-            with torch.cuda.graph(graph, **gkw):        # (the optimizer's device-side {step, lr} pair exists since the warm-up; each replay is preceded by prepare_step)
-                static_losses = body()
+            cap.capture(body, drain=nccl)
         except Exception as e:
-            if not (dist_mode and state["in_graph"]):
+            if not in_graph:
                 raise
             cap_err = e
-        if dist_mode and state["in_graph"]:
+        if in_graph:
             # the fallback must be the SAME on every rank: a rank that keeps captured collectives beside one that issues them eagerly is a collective mismatch
             flag = torch.tensor([0.0 if cap_err is None else 1.0], device=self.device)
             torch.cuda.synchronize()
@@ -407,18 +388,14 @@ class Model(Module):
             torch.cuda.synchronize()
             if cap_err is None and float(flag.item()) > 0:
                 cap_err = RuntimeError("another rank could not capture the collectives")
+                ops.reset_backward_state()                  # (as the ranks whose capture was aborted)
         if cap_err is not None:
-            e = cap_err
-            ops.reset_backward_state()                  # the aborted capture left a half-run backward pass behind: queued weight gradients, hand-over tags, group counters
             # the collectives could not be captured on this stack: capture forward + backward only (peer-write SyncBatchNorm), all-reduce + Adam after each replay
-            print("[avec_amd] rank %d: capture with in-graph RCCL collectives failed (%s: %s); capturing forward + backward only" % (self.rank, type(e).__name__, e), flush=True)
-            state["in_graph"] = False
+            print("[avec_amd] rank %d: capture with in-graph RCCL collectives failed (%s: %s); capturing forward + backward only"
+                  % (self.rank, type(cap_err).__name__, cap_err), flush=True)
+            tail_in_graph[0] = False
             self.arena.arm_early_all_reduce(False)
-            torch.cuda.synchronize()
-            time.sleep(0.6)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, **gkw):
-                static_losses = body()
+            cap.capture(body, drain=True)
 
         replays = [0]
 
@@ -428,24 +405,19 @@ class Model(Module):
             if px is not None and replays[0] % 100 == 0:
                 px.check()                          # (synchronises) a lost rank: the guarded Adam launch skipped those steps, say so instead of training on
             if new_inputs is not None:
-                for d, s_ in zip(static_in, new_inputs):
-                    d.copy_(s_, non_blocking=True)
-                for d, s_ in zip(static_tg, new_targets):
-                    d.copy_(s_, non_blocking=True)
-            self.optimizer.prepare_step()
-            graph.replay()
-            finish()
+                cap.load(new_inputs, new_targets)
+            losses = run(cap.replay)
             if self.ema_model is not None:
                 self.ema_model.arena.mark_dirty()   # (the captured EMA launch rewrote its masters as well)
-            if not dist_mode or state["in_graph"]:
+            if tail_in_graph[0]:
                 self.arena.mark_dirty()             # host-side view of what the replay's closing Adam launch left behind: whatever runs next OUTSIDE the graph
-            return static_losses                    # (evaluation, an eager step) must refresh the weight shadows first -- the captured refresh sits at the START of a replay
+            return losses                           # (evaluation, an eager step) must refresh the weight shadows first -- the captured refresh sits at the START of a replay
 
         if dist_mode:
-            self.arena.arm_early_all_reduce(os.environ.get("AVEC_EARLY_ALLREDUCE", "1") != "0")      # later eager train_steps keep their overlapped exchange
-        step.graph = graph
-        step.collectives_in_graph = bool(dist_mode and state["in_graph"])
-        step.warm_losses = {k: v.detach().clone() for k, v in warm.items()} if warm is not None else None
+            self.arena.arm_early_all_reduce(rt.early_all_reduce_enabled())      # later eager train_steps keep their overlapped exchange
+        step.graph = cap.graph
+        step.collectives_in_graph = bool(dist_mode and tail_in_graph[0])
+        step.warm_losses = {k: v.detach().clone() for k, v in warm.items()}
         return step
 
     # -- hipGraph replay for ragged training batches: one captured step per batch SHAPE --------------------------------------------------------------------
@@ -476,41 +448,32 @@ class Model(Module):
         lw = self.compiled_loss_weights
         const_w = isinstance(lw, ConstantScheduler) or (isinstance(lw, dict) and all(isinstance(v, ConstantScheduler) for v in lw.values())) \
             or (isinstance(lw, list) and all(isinstance(v, ConstantScheduler) for v in lw))
-        capturable = (not self.is_distributed) or peer.active() is not None or \
-            (torch.distributed.get_backend() == "nccl" and os.environ.get("AVEC_GRAPH_ALLREDUCE", "1") != "0")
+        capturable = (not self.is_distributed) or peer.active() is not None or (torch.distributed.get_backend() == "nccl" and rt.graph_all_reduce_enabled())
         return const_w and capturable
 
+    def _cached_step(self, kind, make, inputs, targets, precision, cache_size, bucket_frames, *extra):
+        """the captured step of `kind` ("step" / "micro") for this batch's shape from self.captured_steps, captured by make(inputs, targets) when the shape is new
+        -> (inputs, targets as the captured step takes them: bucketed when `bucket_frames`, see pad_av_batch; the step; whether it was made just now)"""
+        if bucket_frames and len(inputs) == 4 and inputs[0].dim() == 5 and isinstance(targets, (tuple, list)) and len(targets) == 2:
+            inputs, targets = self.pad_av_batch(inputs, targets, bucket_frames)
+        key = (kind,) + tuple((tuple(t.shape), str(t.dtype)) for t in list(inputs) + list(targets)) + (str(precision),) + extra
+        who = {"step": "graphed_train_step", "micro": "graphed_micro_step"}[kind]
+        step, made = self.captured_steps.get_or_make(key, lambda: make(inputs, targets), cache_size, who)
+        return inputs, targets, step, made
+
     def graphed_train_step(self, inputs, targets, precision=torch.bfloat16, cache_size=8, bucket_frames=None):
-        """train_step through a cache of captured steps keyed by the batch shape (LRU, `cache_size` graphs: each holds its own activation pool).  Ragged LRS batches
-        (nnet/collate_fn.py pads to the batch maximum) repeat a small set of shapes once they are bucketed (`bucket_frames`, see pad_av_batch) or come from a
-        length-bucketed sampler.  Falls back to train_step when a step cannot be captured as is (scheduled loss weights, data parallel without capturable
+        """train_step through the cache of captured steps keyed by the batch shape (self.captured_steps: LRU, `cache_size` graphs, each with its own activation pool).
+        Ragged LRS batches (nnet/collate_fn.py pads to the batch maximum) repeat a small set of shapes once they are bucketed (`bucket_frames`, see pad_av_batch) or
+        come from a length-bucketed sampler.  Falls back to train_step when a step cannot be captured as is (scheduled loss weights, data parallel without capturable
         SyncBatchNorm exchanges).  With gradient clipping or the non-finite guard the step is graphed_micro_step's: forward + backward replayed, norm and optimizer
         launches behind the replay."""
         if not self._graph_capturable():
             return self.train_step(inputs, targets, precision=precision)[0]
-        if self.grad_max_norm is not None or getattr(self, "skip_nonfinite_steps", False):
+        if self.grad_max_norm is not None or self.skip_nonfinite_steps:
             return self.graphed_micro_step(inputs, targets, precision, 1, 0, cache_size=cache_size, bucket_frames=bucket_frames)[0]
-        if bucket_frames and len(inputs) == 4 and inputs[0].dim() == 5 and isinstance(targets, (tuple, list)) and len(targets) == 2:
-            inputs, targets = self.pad_av_batch(inputs, targets, bucket_frames)
-        key = tuple((tuple(t.shape), str(t.dtype)) for t in list(inputs) + list(targets)) + (str(precision),)
-        cache = self.__dict__.setdefault("_graph_cache", {})
-        step = cache.pop(key, None)
-        if step is None:
-            self._evict_graphs(cache, cache_size, "graphed_train_step")
-            step = self.make_graphed_train_step(inputs, targets, precision=precision, warmup=1)      # (the warm-up pass is a real optimisation step on this batch)
-            cache[key] = step
-            return step.warm_losses
-        cache[key] = step
-        return step(inputs, targets)
-
-    def _evict_graphs(self, cache, cache_size, who):
-        while len(cache) >= cache_size:
-            cache.pop(next(iter(cache)))                 # least recently used (dict order = recency)
-            ev = self.__dict__["_graph_evictions"] = self.__dict__.get("_graph_evictions", 0) + 1
-            if ev == 2 * cache_size:                     # every new shape costs an eager warm-up step, a capture and a private activation pool
-                import warnings
-                warnings.warn("%s: %d captured steps evicted from a cache of %d -- the batch shapes do not repeat; bucket the batches "
-                              "(graph_bucket_frames / a length-bucketed sampler, nnet/samplers.py) or raise graph_cache_size" % (who, ev, cache_size))
+        make = lambda i, t: self.make_graphed_train_step(i, t, precision=precision, warmup=1)      # (the warm-up pass is a real optimisation step on this batch)
+        inputs, targets, step, made = self._cached_step("step", make, inputs, targets, precision, cache_size, bucket_frames)
+        return step.warm_losses if made else step(inputs, targets)
 
     # -- hipGraph replay of ONE micro-step (forward + backward): gradient accumulation, clipping and the non-finite guard keep the optimizer tail eager ---------
     def make_graphed_micro_step(self, inputs, targets, precision, accumulated_steps):
@@ -520,55 +483,38 @@ class Model(Module):
         micro-steps).  Capturing executes nothing, so the arena is not touched twice.  Like every captured step it holds the modules' training / evaluation
         modes as they were at the capture.  Returns micro(inputs, targets) -> losses (static device scalars) with .warm_losses, the eager pass's."""
         dist_mode = self.is_distributed
-        rt.set_compute_dtype(precision)
-        static_in = [t.clone() for t in inputs]
-        static_tg = tuple(t.clone() for t in targets)
-        if dist_mode:
-            self.arena.arm_early_all_reduce(False)          # the gradient exchange follows the LAST replay (amortised over the micro-steps), never from inside the backward pass
+        cap = CapturedStep(inputs, targets)
 
         def body():
             rt.reset_zero_pool(self.device)
-            losses, _, _, _ = self.forward_model(static_in, static_tg, compute_metrics=False)
+            losses, _, _, _ = self.forward_model(cap.inputs, cap.targets, compute_metrics=False)
             (losses["loss"] / accumulated_steps).backward()
             rt.advance_rng(self.device)
             return losses
 
-        # the eager pass on a side stream, as torch.cuda.graph's own warm-up advice: lazily created constants (DFT matrix, sinusoid tables, loss weights), kernel
-        # attributes and the allocator's blocks exist before the capture
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            warm = self._own_losses(body())
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        if dist_mode and torch.distributed.get_backend() == "nccl":
-            time.sleep(0.6)                                 # the process group's watchdog must have reaped every collective issued so far (see make_graphed_train_step)
-        self.arena.check_versions()
-        self.arena.ensure_fresh()                           # no refresh inside the graph
-        ops.invalidate_pos_cache()                          # the position projections, cached per refresh, are computed INSIDE the graph: every replay follows the weights
-        graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(graph):
-                static_losses = body()
-        except Exception:
-            ops.reset_backward_state()                      # an aborted capture leaves a half-run backward pass behind
-            raise
+        def settle(fresh=True):                             # before every pass
+            if dist_mode:
+                self.arena.arm_early_all_reduce(False)      # the gradient exchange follows the LAST replay (amortised over the micro-steps), never from inside the backward pass
+            rt.set_compute_dtype(precision)
+            if fresh:                                       # no refresh inside the graph (the eager pass brings its own)
+                self.arena.check_versions()                 # (weights edited in place since the last pass: the forward pre-hook's check does not run inside a replay)
+                self.arena.ensure_fresh()
+
+        def before_capture():
+            settle()
+            ops.invalidate_pos_cache()                      # the position projections, cached per refresh, are computed INSIDE the graph: every replay follows the weights
+
+        settle(fresh=False)
+        warm = cap.warm_up(lambda: self._own_losses(body()))
+        cap.capture(body, drain=dist_mode and torch.distributed.get_backend() == "nccl", before=before_capture)
         assert not self.arena.dirty, "the captured micro-step must not hold a shadow refresh"
 
         def micro(new_inputs, new_targets):
-            for d, s_ in zip(static_in, new_inputs):
-                d.copy_(s_, non_blocking=True)
-            for d, s_ in zip(static_tg, new_targets):
-                d.copy_(s_, non_blocking=True)
-            if dist_mode:
-                self.arena.arm_early_all_reduce(False)
-            rt.set_compute_dtype(precision)
-            self.arena.check_versions()                     # (weights edited in place since the last pass: the forward pre-hook's check does not run inside a replay)
-            self.arena.ensure_fresh()
-            graph.replay()
-            return static_losses
+            cap.load(new_inputs, new_targets)
+            settle()
+            return cap.replay()
 
-        micro.graph = graph
+        micro.graph = cap.graph
         micro.warm_losses = warm
         return micro
 
@@ -594,21 +540,12 @@ class Model(Module):
         host), AVEC_FP8=1, data parallel without capturable SyncBatchNorm exchanges."""
         why = self._micro_fallback_reason(eval_training)
         if why is not None:
-            self.__dict__["_micro_fallback"] = why           # (fit says so once: nobody should believe they are on the replay path)
+            self.eager_fallback = why                        # (fit says so once: nobody should believe they are on the replay path)
             losses, _, acc_step = self.train_step(inputs, targets, precision, None, accumulated_steps, acc_step, eval_training)
             return losses, acc_step
-        if bucket_frames and len(inputs) == 4 and inputs[0].dim() == 5 and isinstance(targets, (tuple, list)) and len(targets) == 2:
-            inputs, targets = self.pad_av_batch(inputs, targets, bucket_frames)
-        key = tuple((tuple(t.shape), str(t.dtype)) for t in list(inputs) + list(targets)) + (str(precision), int(accumulated_steps))
-        cache = self.__dict__.setdefault("_micro_graph_cache", {})
-        micro = cache.pop(key, None)
-        if micro is None:
-            self._evict_graphs(cache, cache_size, "graphed_micro_step")
-            micro = self.make_graphed_micro_step(inputs, targets, precision, accumulated_steps)
-            losses = micro.warm_losses
-        else:
-            losses = self._own_losses(micro(inputs, targets))      # copies: the next replay refills the static outputs
-        cache[key] = micro
+        make = lambda i, t: self.make_graphed_micro_step(i, t, precision, accumulated_steps)
+        inputs, targets, micro, made = self._cached_step("micro", make, inputs, targets, precision, cache_size, bucket_frames, int(accumulated_steps))
+        losses = micro.warm_losses if made else self._own_losses(micro(inputs, targets))      # copies: the next replay refills the static outputs
         acc_step += 1
         if acc_step < accumulated_steps:
             return losses, acc_step
@@ -753,14 +690,14 @@ class Model(Module):
             for step, batch in enumerate(dataset_train):
                 inputs = self.transfer_to_device(batch["inputs"])
                 targets = self.transfer_to_device(batch["targets"])
-                micro = accumulated_steps > 1 or self.grad_max_norm is not None or getattr(self, "skip_nonfinite_steps", False)
+                micro = accumulated_steps > 1 or self.grad_max_norm is not None or self.skip_nonfinite_steps
                 if use_graphs and micro and self.device.type == "cuda":
                     losses, acc_step = self.graphed_micro_step(inputs, targets, precision, accumulated_steps, acc_step, cache_size=graph_cache_size,
                                                                bucket_frames=graph_bucket_frames, eval_training=eval_training)
-                    if "_micro_fallback" in self.__dict__ and not self.__dict__.get("_micro_fallback_said"):
-                        self.__dict__["_micro_fallback_said"] = True
+                    if self.eager_fallback is not None and not self._eager_fallback_said:
+                        self._eager_fallback_said = True
                         if self.rank == 0:
-                            print("use_graphs: training with eager launches, not replayed graphs -- " + self.__dict__["_micro_fallback"])
+                            print("use_graphs: training with eager launches, not replayed graphs -- " + self.eager_fallback)
                 elif use_graphs and self.device.type == "cuda":
                     losses = self.graphed_train_step(inputs, targets, precision=precision, cache_size=graph_cache_size, bucket_frames=graph_bucket_frames)
                 else:

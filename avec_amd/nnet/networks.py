@@ -7,6 +7,7 @@ import torch.nn as nn
 from .. import ops
 from .. import runtime as rt
 from . import attentions, blocks, layers, modules, normalizations, preprocessing, transforms
+from .captured import CapturedStep
 
 
 class ResNet(nn.Module):
@@ -400,18 +401,11 @@ class ConformerStreamSession:
             D0 = self.stack.conformer_blocks[0].ff_module1.layers[0].normalized_shape[0]
             x = torch.zeros(self.B, self.Tc, D0, dtype=torch.float32, device=dev)
             self._upload([True] * self.B, None, None)
+            cap = CapturedStep()
             with torch.cuda.device(dev):
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):                      # warm-up: weight shadows, lazy kernel attributes, allocator
-                        self._run(x)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    out = self._run(x)
-        self._graph, self._static = graph, (x, out)
+                cap.warm_up(lambda: self._run(x), 2)        # weight shadows, lazy kernel attributes, allocator
+                cap.capture(lambda: self._run(x))
+        self._graph, self._static = cap.graph, (x, cap.outputs)
         self._first = True
         self._short = [False] * self.B
         return self
@@ -571,7 +565,7 @@ class AudioVisualEfficientConformerEncoder(nn.Module):
                 if torch.is_tensor(t) and t.is_cuda:
                     t.record_stream(main)
         arena = rt.arena_of(self.fusion_module) if audio.is_cuda else None
-        if arena is not None and getattr(arena, "_early_armed", False):
+        if arena is not None and arena._early_armed:
             # distributed training: when the gradient reaches these two tensors, the fusion module / audio-visual encoder / head gradients are final ->
             # their all-reduce starts while the two encoders are still back-propagating; the audio encoder's follows when its own backward ends
             r_f, r_h = arena.range_of(self.fusion_module), arena.range_of(self.head) if not isinstance(self.head, nn.Identity) else arena.range_of(self.audio_visual_encoder)

@@ -39,7 +39,7 @@ class Adam(optim.Adam):
             st["exp_avg_sq"] = self._flat["exp_avg_sq"][o:o + n].as_strided(p.shape, p.stride())
 
     def prepare_step(self):
-        """host half of step(): advance the scheduler, publish {step, lr} to the device scalar pair the kernel reads"""
+        """host half of step(), never inside a graph: advance the scheduler, publish {step, lr} to the device scalar pair the kernel reads"""
         lr = self.scheduler.step()
         for group in self.param_groups:
             group["lr"] = lr
@@ -59,6 +59,7 @@ class Adam(optim.Adam):
         slot[1] = float(lr)
         self._flat["state"].copy_(slot, non_blocking=True)
         ev.record()
+        self._step_t.fill_(float(self.scheduler.model_step))     # one shared CPU scalar stands for every per-parameter "step" (state_dict)
 
     def launch_grad_norm(self, max_norm=None, skip_nonfinite=False):
         """Global gradient norm (times grad_scale) and clip factor on the device, two launches (ops.grad_norm); the next launch_step(clip=True) applies the factor
@@ -90,7 +91,6 @@ class Adam(optim.Adam):
     def step(self, closure=None, clip=False):
         self.prepare_step()
         self.launch_step(clip)
-        self._step_t.fill_(float(self.scheduler.model_step))     # one shared CPU scalar stands for every per-parameter "step"
         return None
 
     def _launch(self, g, clip=False):

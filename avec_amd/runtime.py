@@ -203,9 +203,21 @@ class _GradBoundaryFn(torch.autograd.Function):
 
 def grad_boundary(x, arena, lo, hi):
     """mark `x` as an input of the sub-network whose parameters live in arena[lo:hi) (distributed training only)"""
-    if arena is None or not getattr(arena, "_early_armed", False) or not x.requires_grad:
+    if arena is None or not arena._early_armed or not x.requires_grad:
         return x
     return _GradBoundaryFn.apply(x, arena, lo, hi)
+
+
+def early_all_reduce_enabled():
+    """data parallel: start the gradient all-reduce of finished arena ranges from inside the backward pass (ParamArena.early_all_reduce); "0" leaves the whole
+    exchange to all_reduce_grads().  Read when asked, so a run may change it between steps."""
+    return os.environ.get("AVEC_EARLY_ALLREDUCE", "1") != "0"
+
+
+def graph_all_reduce_enabled():
+    """data parallel over the nccl backend: capture the gradient all-reduce and the optimizer launch into the whole-step graph; "0": both follow the replay
+    (also what gloo debugging runs get)."""
+    return os.environ.get("AVEC_GRAPH_ALLREDUCE", "1") != "0"
 
 
 def arena_of(module):
@@ -387,6 +399,7 @@ class ParamArena:
         self._shadow_dtype = None
         self.dirty = True
         self._vstamp = None
+        self._early_armed, self._early, self._sync_collectives = False, [], False      # data parallel: see arm_early_all_reduce
         # any load_state_dict on the model OR on one of its sub-modules (the reference configs transplant the LRW front-end this way,
         # configs/LRS23/AV/EffConfInterCTC.py:70-75) rewrites master weights: the compute-dtype shadows must follow
         for m in module.modules():
@@ -541,12 +554,12 @@ class ParamArena:
     def early_all_reduce(self, lo, hi):
         """Start the gradient all-reduce of arena range [lo, hi) now (its gradients are final), on the current stream, asynchronously: the exchange
         of the audio-visual encoder's and the audio encoder's gradients overlaps the rest of the backward pass.  No-op unless armed by train_step."""
-        if not getattr(self, "_early_armed", False) or hi <= lo:
+        if not self._early_armed or hi <= lo:
             return
         import torch.distributed as dist
         from . import ops
         ops.flush_param_grads()                   # queued weight / LayerNorm gradients of this stream belong to the range: they must be in the arena first
-        if getattr(self, "_sync_collectives", False):
+        if self._sync_collectives:
             # inside a hipGraph capture: a blocking collective is enqueued on the calling stream's communicator in program order and becomes part of the graph
             # (no work handle to wait for on the host); from the audio branch's stream it runs beside the visual branch's backward
             dist.all_reduce(self.grad[lo:hi], op=dist.ReduceOp.SUM, async_op=False, group=collective_group())
@@ -555,17 +568,19 @@ class ParamArena:
         self._early.append((lo, hi, dist.all_reduce(self.grad[lo:hi], op=dist.ReduceOp.SUM, async_op=True, group=collective_group())))
 
     def arm_early_all_reduce(self, flag, sync=False):
+        """Before a backward pass.  flag: early_all_reduce() starts its ranges from inside the pass.  sync: every collective up to and including the next
+        all_reduce_grads() is a blocking call in program order (what a hipGraph capture records); all_reduce_grads() disarms both."""
         self._early_armed, self._early, self._sync_collectives = bool(flag), [], bool(sync)
 
     def all_reduce_grads(self, bucket_bytes=64 << 20):
         """DDP gradient averaging: sum over ranks in large contiguous buckets (RCCL over xGMI); the 1/world factor is
         folded into the Adam kernel's grad_scale.  Ranges already started by early_all_reduce() are only waited for."""
-        early = sorted(getattr(self, "_early", []), key=lambda t: t[0])
+        early = sorted(self._early, key=lambda t: t[0])
         pos = 0
         if os.environ.get("AVEC_DIAG_SKIP_GRAD_ALLREDUCE") == "1":      # diagnostics only (two ranks sharing one GPU over gloo: isolates compute + SyncBatchNorm exchange cost)
             early = []
             pos = self.numel
-        sync = getattr(self, "_sync_collectives", False)
+        sync = self._sync_collectives
         for lo, hi, _ in early + [(self.numel, self.numel, None)]:
             if lo > pos:
                 all_reduce_flat(self.grad[pos:lo], bucket_bytes, sync=sync)

@@ -254,8 +254,8 @@ def test_accumulated_gradient_replayed_against_eager(ctx):
     assert se == sg == 2, (se, sg)
     for a, b in zip(le, lg):
         assert abs(a - b) < 2e-2 * abs(a), (le, lg)
-    assert len(ctx.model.__dict__["_micro_graph_cache"]) == 2, "six micro-steps over two shapes: exactly two captured graphs"
-    assert len(ctx.model.__dict__.get("_graph_cache", {})) == 0
+    assert ctx.model.captured_steps.count("micro") == 2, "six micro-steps over two shapes: exactly two captured graphs"
+    assert ctx.model.captured_steps.count("step") == 0
 
 
 def test_same_batch_accumulated_four_times_is_the_gradient_of_one_captured_step(ctx):
@@ -286,34 +286,34 @@ def _fit_batches(ctx, n):
 def test_fit_with_graphs_takes_the_captured_micro_step_when_accumulating(ctx):
     m = ctx.model
     ctx.reset()
-    m.__dict__.pop("_micro_graph_cache", None)
+    m.captured_steps.clear("micro")
     m.fit(_fit_batches(ctx, 4), epochs=1, precision=torch.float32, accumulated_steps=2, use_graphs=True)
     torch.cuda.synchronize()
-    assert len(m.__dict__.get("_micro_graph_cache", {})) == 2, "fit(use_graphs=True, accumulated_steps=2) did not go through graphed_micro_step"
+    assert m.captured_steps.count("micro") == 2, "fit(use_graphs=True, accumulated_steps=2) did not go through graphed_micro_step"
     assert int(m.model_step) == 2
     assert bool(torch.isfinite(m.arena.master).all()) and not bool(m.arena.grad.any()), "the optimizer launch cleared the gradient arena"
-    m.__dict__.pop("_micro_graph_cache", None)           # (captured with every module in training mode, SpecAugment included: not for the other tests)
+    m.captured_steps.clear("micro")           # (captured with every module in training mode, SpecAugment included: not for the other tests)
 
 
 def test_fit_with_graphs_and_clipping_takes_the_captured_micro_step(ctx):
     m = ctx.model
     ctx.reset()
-    m.__dict__.pop("_micro_graph_cache", None)
+    m.captured_steps.clear("micro")
     m.grad_max_norm = 1.0
     m.fit(_fit_batches(ctx, 4), epochs=1, precision=torch.float32, accumulated_steps=1, use_graphs=True)
     torch.cuda.synchronize()
-    assert len(m.__dict__.get("_micro_graph_cache", {})) == 2 and len(m.__dict__.get("_graph_cache", {})) == 0
+    assert m.captured_steps.count("micro") == 2 and m.captured_steps.count("step") == 0
     assert int(m.model_step) == 4
     norm = float(m.infos["grad_norm"])
     assert norm == norm and norm > 0
     # graphed_train_step itself no longer falls back to eager launches with clipping set
-    m.__dict__.pop("_micro_graph_cache", None)           # (fit's graphs were captured with every module in training mode, SpecAugment included)
+    m.captured_steps.clear("micro")           # (fit's graphs were captured with every module in training mode, SpecAugment included)
     ctx.reset()
     m.grad_max_norm = 1.0
-    before = len(m.__dict__.get("_micro_graph_cache", {}))
+    before = m.captured_steps.count("micro")
     m.graphed_train_step(*ctx.batches[0], precision=torch.float32)
-    assert len(m.__dict__["_micro_graph_cache"]) == before + 1 and int(m.model_step) == 1 and len(m.__dict__.get("_graph_cache", {})) == 0
-    m.__dict__.pop("_micro_graph_cache", None)
+    assert m.captured_steps.count("micro") == before + 1 and int(m.model_step) == 1 and m.captured_steps.count("step") == 0
+    m.captured_steps.clear("micro")
 
 
 def test_fit_says_once_when_it_cannot_replay(ctx, capsys):
@@ -327,9 +327,8 @@ def test_fit_says_once_when_it_cannot_replay(ctx, capsys):
         m.compiled_metrics = metrics
     assert m._micro_fallback_reason(eval_training=True) is None, "without compiled metrics there is nothing for the host to compute"
     ctx.reset()
-    m.__dict__.pop("_micro_graph_cache", None)
-    for key in ("_micro_fallback", "_micro_fallback_said"):
-        m.__dict__.pop(key, None)
+    m.captured_steps.clear("micro")
+    m.eager_fallback, m._eager_fallback_said = None, False
     m._micro_fallback_reason = lambda eval_training=False: "for the sake of this test"
     try:
         m.fit(_fit_batches(ctx, 4), epochs=1, precision=torch.float32, accumulated_steps=2, use_graphs=True)
@@ -338,9 +337,8 @@ def test_fit_says_once_when_it_cannot_replay(ctx, capsys):
     torch.cuda.synchronize()
     said = [line for line in capsys.readouterr().out.splitlines() if line.startswith("use_graphs: training with eager launches")]
     assert len(said) == 1 and said[0].endswith("for the sake of this test"), said
-    assert len(m.__dict__.get("_micro_graph_cache", {})) == 0 and int(m.model_step) == 2
-    for key in ("_micro_fallback", "_micro_fallback_said"):
-        m.__dict__.pop(key, None)
+    assert m.captured_steps.count("micro") == 0 and int(m.model_step) == 2
+    m.eager_fallback, m._eager_fallback_said = None, False
 
 
 def test_clipping_scales_the_gradient_the_optimizer_sees(ctx):

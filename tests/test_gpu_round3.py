@@ -86,7 +86,7 @@ def test_graphed_train_step_cache_on_ragged_batches():
                     l = model.graphed_train_step(inp, tgt, precision=torch.float32)
                 losses.append(float(l["loss"].detach()))
             torch.cuda.synchronize()
-            out[mode] = (losses, int(model.model_step), len(model.__dict__.get("_graph_cache", {})))
+            out[mode] = (losses, int(model.model_step), model.captured_steps.count("step"))
     finally:
         avec_amd.set_compute_dtype("f32")
     assert out["eager"][1] == out["graphs"][1] == 6

@@ -172,6 +172,27 @@ def test_set_ema_on_a_cpu_model_and_checkpoint_key(tmp_path):
         m._update_ema()                                                                          # the update itself is a HIP launch over the arenas: no CPU stand-in
 
 
+def test_set_ema_leaves_no_captured_step_in_either_model():
+    """a captured step replays launches on the model's own buffers: the EMA copy must not get one (nor a copy of one), and the model's own whole-step graphs
+    hold no EMA launch, so they go as well"""
+    class Entry:
+        copies = 0
+
+        def __deepcopy__(self, memo):
+            Entry.copies += 1
+            return Entry()
+
+    m = _model()
+    entry, made = m.captured_steps.get_or_make(("micro", ((2, 3), "torch.float32"), "torch.float32", 2), Entry, 8, "test")
+    assert made and m.captured_steps.count() == m.captured_steps.count("micro") == 1
+    m.set_ema(0.9)
+    assert Entry.copies == 0, "set_ema deep-copied a captured step"
+    assert m.ema_model.captured_steps is not m.captured_steps
+    assert m.ema_model.captured_steps.count() == 0 and m.ema_model.captured_steps.evictions == 0
+    assert m.captured_steps.count() == 0
+    assert m.ema_model.eager_fallback is None
+
+
 def test_weight_average_argument_errors_before_any_hip_call():
     from avec_amd.lib import declared_functions, lib
     assert len(declared_functions()["avec_weight_average"][1]) == 7

@@ -109,7 +109,7 @@ def main():
                 fn()
             torch.cuda.synchronize()
             times[name].append((time.perf_counter() - t0) / args.iters * 1e3)
-    row = {"group": "optimizer_step", "B": B, "frames": 100, "k": k, "dtype": "bf16", "clip": args.clip, "single_clipped": False, "graphs_cached": len(model.__dict__.get("_micro_graph_cache", {}))}
+    row = {"group": "optimizer_step", "B": B, "frames": 100, "k": k, "dtype": "bf16", "clip": args.clip, "single_clipped": False, "graphs_cached": model.captured_steps.count("micro")}
     for name, v in times.items():
         row[name + "_ms"], row[name + "_max_ms"] = round(min(v), 2), round(max(v), 2)
     print(json.dumps(row))

@@ -64,11 +64,11 @@ def main():
         def stem_apply(mel, *a, **k):
             out = a0(mel, *a, **k); taps.append(("stem_in", mel)); taps.append(("stem_out", out)); return out
         _ops.AudioStemFn.apply = stem_apply
-    if world > 1 and os.environ.get("AVEC_EARLY_ALLREDUCE", "1") != "0":
+    if world > 1 and avec_amd.runtime.early_all_reduce_enabled():
         model.arena.arm_early_all_reduce(True)               # as train_step does: two arena ranges are exchanged while backward is still running
     losses, _, _, _ = model.forward_model(inputs, targets, compute_metrics=False)
     losses["loss"].backward()
-    early = [(lo, hi) for lo, hi, _ in getattr(model.arena, "_early", [])]
+    early = [(lo, hi) for lo, hi, _ in model.arena._early]
     if log:
         torch.cuda.synchronize()
         name_of_ = {id(m_): n_ for n_, m_ in model.named_modules()}

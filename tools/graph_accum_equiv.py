@@ -74,7 +74,7 @@ def main():
     grads = (model.optimizer._flat["exp_avg"].detach().float() / (1.0 - beta1) - wd * master0).cpu()      # flat, laid out like the parameter arena
     names = {id(p): name for name, p in model.named_parameters()}
     layout = [[names[id(p)], int(o), p.numel()] for p, o in zip(model.arena.params, model.arena.offsets)]
-    torch.save({"grads": grads, "layout": layout, "losses": losses, "step": int(model.model_step), "cached": len(model.__dict__.get("_micro_graph_cache", {})),
+    torch.save({"grads": grads, "layout": layout, "losses": losses, "step": int(model.model_step), "cached": model.captured_steps.count("micro"),
                 "peer": peer.active() is not None, "world": model.world_size}, args.out)
     torch.distributed.barrier()
     torch.distributed.destroy_process_group()
