@@ -455,6 +455,243 @@ class AudioEfficientConformerEncoder(nn.Module):
             x = self.head(x)
         return x, lengths, inter
 
+    def stream_front(self, batch_size, chunk_frames):
+        """An AudioFrontStreamSession: waveform chunks -> the 180-wide features the back-end consumes, with the offline front-end's arithmetic."""
+        return AudioFrontStreamSession(self, batch_size, chunk_frames)
+
+    def stream(self, batch_size, chunk_frames):
+        """An AudioStreamSession: waveform chunks -> logits, the front session + back_end.stream() + head (the back-end's refusals are ConformerInterCTC.stream()'s)."""
+        return AudioStreamSession(self, batch_size, chunk_frames)
+
+
+def _flag_mask(flags, B):
+    """reset / last as passed to a push (None, a list of slot indices, or a host bool mask [B]) -> a bool list [B]"""
+    if flags is None:
+        return [False] * B
+    r = flags.cpu().tolist() if torch.is_tensor(flags) else list(flags)
+    if len(r) == B and all(isinstance(v, bool) for v in r):
+        return r
+    mask = [False] * B
+    for k in r:
+        mask[int(k)] = True
+    return mask
+
+
+class AudioFrontStreamSession:
+    """AudioEfficientConformerEncoder.stream_front(): the audio front-end (log-mel -> Conv2d + BatchNorm2d + Swish stem -> Linear) run on waveform chunks.  The frames a
+    slot has produced after any sequence of pushes equal the offline front-end's frames on the samples pushed so far (and, once the utterance has ended, on the whole
+    utterance: both STFT reflections and both zero paddings of the stem included), up to the DFT GEMM's tile choice.  Mel frame f reads samples [160 f - 200, 160 f + 200),
+    stem frame t reads mel frames 2t - 1, 2t, 2t + 1: with n samples heard E(n) = 0 if n < 360 else (n - 40) // 320 frames exist, Ta // 320 + 1 at the end.  Schedule:
+    first_samples = 320 Tc + 40 in an utterance's first push, chunk_samples = 320 Tc in every later one; every push but the last then yields exactly Tc frames, the last at
+    most Tc + 1.  The carried state is a sample tail of fewer than 720 samples per slot, a counter and an `ended` flag, on the device (ops.audio_stream_state); nothing
+    is added to the module tree or the state_dict."""
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        self.enc, self.B, self.Tc = enc, int(batch_size), int(chunk_frames)
+        self._check(enc)
+        if self.B < 1:
+            raise ValueError("stream_front: batch_size %d" % self.B)
+        if self.Tc < 2:
+            raise ValueError("stream_front: chunk_frames = %d: a push of %d samples would be shorter than one %d-sample analysis window; at least 2 frames (80 ms) per push"
+                             % (self.Tc, 2 * self.hop * self.Tc, self.win))
+        self.first_samples, self.chunk_samples = 2 * self.hop * self.Tc + (self.win // 2 - self.hop), 2 * self.hop * self.Tc
+        self.Tmax = self.Tc + 2                    # any count up to first_samples, at the end of an utterance too, gives at most Tc + 2 frames
+        self.state = None
+        self._n = [0] * self.B                     # host mirror of the device counters (None: unknown after a push with device-tensor counts)
+        self._ended = [False] * self.B
+        self._first = True
+        self._ns_up = None                         # what self.nsamp holds
+        self._graph = self._static = None
+
+    def _check(self, enc):
+        if enc.training:
+            raise RuntimeError("stream_front: the encoder is in training mode (SpecAugment and BatchNorm batch statistics are not functions of the past): call .eval() first")
+        pre = enc.audio_preprocessing
+        if pre.normalize:
+            raise NotImplementedError("stream_front: AudioPreprocessing(normalize=True) is not streamed: the stem's zero padding would have to become (0 - mean) / std columns")
+        conv, bn = enc.subsampling_module.layers[0][0], enc.subsampling_module.layers[0][1]
+        if not (bn.track_running_stats and bn.running_mean is not None):
+            raise NotImplementedError("stream_front: the stem's BatchNorm keeps no running statistics")
+        self.n_fft, self.win, self.hop, self.n_mels = pre.n_fft, pre.win_length, pre.hop_length, pre.n_mels
+        if self.win // 2 < self.hop or self.win % 2:
+            raise NotImplementedError("stream_front: window %d / hop %d: the schedule needs an even window of at least two hops" % (self.win, self.hop))
+        if tuple(conv.weight.shape[1:]) != (1, 3, 3):
+            raise NotImplementedError("stream_front: the stem is not a 3x3 convolution of one input channel")
+
+    def _ready(self, n):
+        a = self.hop + self.win // 2
+        return 0 if n < a else (n - a) // (2 * self.hop) + 1
+
+    def _allocate(self, dev):
+        B = self.B
+        bn = self.enc.subsampling_module.layers[0][1]
+        self.state = ops.audio_stream_state(B, dev)
+        self.nsamp = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.reset_flags = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self.last_flags = torch.zeros(B, dtype=torch.uint8, device=dev)
+        st = ops.BNState(bn.num_features, self.state)
+        ops.bn_finalize(bn, st, 1, False)              # eval mode: scale | shift from the running statistics
+        self.ss = st.ss
+
+    def _run(self, wave):
+        enc, pre = self.enc, self.enc.audio_preprocessing
+        conv, lin = enc.subsampling_module.layers[0][0], enc.linear
+        B, Tmax = self.B, self.Tmax
+        kw = dict(n_fft=self.n_fft, win=self.win, hop=self.hop)
+        frames, out_len, meta = ops.mel_frames_stream(wave, pre.Spectrogram.window, self.state, self.nsamp, self.reset_flags, self.last_flags, Tmax=Tmax, **kw)
+        mel = ops.mel_from_frames(frames, pre._dft_matrix(wave.device), pre.MelScale.fb, B, 2 * Tmax + 1, self.n_mels)
+        a = ops.audio_stem_stream(mel, conv.weight, conv.bias, self.ss, out_len, meta, conv.weight.shape[0])
+        ops.audio_stream_advance(wave, self.state, self.nsamp, self.reset_flags, self.last_flags, **kw)
+        feat = ops.linear_fwd(a.view(B * Tmax, -1), lin.weight, lin.bias, B * Tmax, in_f32=False, out_f32=True)
+        return feat.view(B, Tmax, -1), out_len
+
+    # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
+    def _controls(self, n_samples, last, reset):
+        """-> (reset mask, last mask, host counts or None for a device tensor, frames per slot or None): checks a host-list push against the contract, changes nothing"""
+        B = self.B
+        rmask = [True] * B if self._first else _flag_mask(reset, B)
+        lmask = _flag_mask(last, B)
+        if torch.is_tensor(n_samples):
+            return rmask, lmask, None, None
+        if n_samples is not None and len(n_samples) != B:
+            raise ValueError("push: n_samples %r for %d slots" % (list(n_samples), B))
+        counts, frames = [], []
+        for b in range(B):
+            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
+            if n0 is None:
+                raise RuntimeError("push: slot %d was last pushed with device-tensor counts, which the host does not mirror: go on with a tensor, or reset the slot" % b)
+            c = (0 if ended else (self.first_samples if n0 == 0 else self.chunk_samples)) if n_samples is None else int(n_samples[b])
+            if c < 0 or c > self.first_samples:
+                raise ValueError("push: n_samples[%d] = %d outside 0 .. %d" % (b, c, self.first_samples))
+            if ended:
+                if c > 0:
+                    raise RuntimeError("push: slot %d has ended (last) and was not reset: it takes no samples until reset=[%d] starts the next utterance" % (b, b))
+                frames.append(0)
+            elif lmask[b]:
+                if n0 + c <= self.n_fft // 2:
+                    raise ValueError("push: slot %d ends after %d samples: an utterance of at most n_fft / 2 = %d samples cannot be reflect-padded (refused offline as well)"
+                                     % (b, n0 + c, self.n_fft // 2))
+                frames.append((n0 + c) // (2 * self.hop) + 1 - self._ready(n0))
+            else:
+                frames.append(self._ready(n0 + c) - self._ready(n0))
+            counts.append(c)
+        return rmask, lmask, counts, frames
+
+    def _upload(self, rmask, lmask, counts, n_samples):
+        B = self.B
+        if any(rmask):
+            self.reset_flags.copy_(torch.tensor(rmask, dtype=torch.uint8), non_blocking=True)        # (the push's last launch clears both flag vectors again)
+        if any(lmask):
+            self.last_flags.copy_(torch.tensor(lmask, dtype=torch.uint8), non_blocking=True)
+        if counts is None:
+            self.nsamp.copy_(n_samples.view(B), non_blocking=True)
+            self._ns_up = None
+            self._n, self._ended = [None] * B, [None] * B                 # a device tensor's contract is the caller's
+            return
+        if counts != self._ns_up:
+            self.nsamp.copy_(torch.tensor(counts, dtype=torch.int64), non_blocking=True)
+            self._ns_up = list(counts)
+        for b in range(B):
+            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
+            self._n[b], self._ended[b] = n0 + counts[b], ended or lmask[b]
+
+    def push(self, wave, n_samples=None, last=None, reset=None):
+        """wave [B, first_samples] fp32 -> (feat [B, Tc + 2, 180] fp32, out_len [B] int64 on the device): slot b takes the first n_samples[b] samples (a Python list
+        or an int64 device tensor [B]; default: the schedule's count, first_samples after a restart, chunk_samples later, 0 for an ended slot) and yields out_len[b]
+        frames; rows at or past out_len carry no information.  last: slots whose utterance ends with these samples; reset: slots to restart before them (each a list
+        of indices or a host bool mask [B]); the first push restarts every slot.  With host counts the contract is checked on the host, without a synchronisation:
+        counts within 0 .. first_samples, an utterance longer than n_fft / 2 = 256 samples at `last`, no samples to an ended slot.  With a device tensor it is the
+        caller's.  No host synchronisation after the first push; after capture() the results are static tensors that the next push overwrites."""
+        if wave.dim() != 2 or wave.shape[0] != self.B or wave.shape[1] != self.first_samples:
+            raise ValueError("push: wave %s for a session of %d slots x %d samples" % (tuple(wave.shape), self.B, self.first_samples))
+        rt.require_gpu(wave)
+        if self.enc.training:
+            raise RuntimeError("push: the encoder went back to training mode; call .eval()")
+        rmask, lmask, counts, _ = self._controls(n_samples, last, reset)
+        with torch.no_grad():
+            if self.state is None:
+                self._allocate(wave.device)
+            self._upload(rmask, lmask, counts, n_samples)
+            self._first = False
+            if self._graph is not None:
+                self._static[0].copy_(wave, non_blocking=True)
+                self._graph.replay()
+                return self._static[1]
+            return self._run(wave if (wave.dtype == torch.float32 and wave.stride(1) == 1) else wave.float().contiguous())
+
+    def capture(self, device=None):
+        """Capture one push as a graph on static wave / count / flag buffers, as ConformerStreamSession.capture(): call it on a fresh session; the device counters
+        make every replay advance; the warm-up pushes are forgotten (the next push restarts every slot)."""
+        if self._graph is not None:
+            return self
+        if not self._first:
+            raise RuntimeError("capture: call it before the first push of the session")
+        dev = torch.device(device) if device is not None else next(self.enc.parameters()).device
+        rt.require_gpu(next(self.enc.parameters()))
+        with torch.no_grad():
+            with torch.cuda.device(dev):
+                if self.state is None:
+                    self._allocate(dev)
+                x = torch.zeros(self.B, self.first_samples, dtype=torch.float32, device=dev)
+                self._upload([True] * self.B, [False] * self.B, [self.first_samples] * self.B, None)
+                cap = CapturedStep()
+                cap.warm_up(lambda: self._run(x), 2)
+                cap.capture(lambda: self._run(x))
+        self._graph, self._static = cap.graph, (x, cap.outputs)
+        self._first, self._n, self._ended = True, [0] * self.B, [False] * self.B
+        return self
+
+
+class AudioStreamSession:
+    """AudioEfficientConformerEncoder.stream(): waveform chunks -> logits.  The front session feeds back_end.stream() (a ConformerStreamSession, with its refusals) and
+    the head.  The front's schedule makes every push but an utterance's last yield exactly Tc frames, one chunk of the stack; a last push may yield Tc + 1: the stack
+    is then pushed a second time with that one frame for the slots concerned and 0 frames (no change of state) for the others, and its first output row is appended."""
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        self.enc = enc
+        self.front = AudioFrontStreamSession(enc, batch_size, chunk_frames)
+        self.back = enc.back_end.stream(batch_size, chunk_frames)
+        self.B, self.Tc, self.S = self.front.B, self.front.Tc, self.back.S
+        self.first_samples, self.chunk_samples = self.front.first_samples, self.front.chunk_samples
+        self._x2 = None
+
+    def _head(self, y):
+        return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
+
+    def push(self, wave, n_samples=None, last=None, reset=None):
+        """wave [B, first_samples] fp32 -> (logits [B, R, V] fp32, out_len [B] int64 on the device, inter: loss_prefix_i -> [logits chunk, lengths] as offline).
+        n_samples / last / reset: host lists as AudioFrontStreamSession.push; counts must follow the schedule (every push of a slot but its last yields exactly
+        chunk_frames frames; a slot may idle on 0 samples).  R = Tc / S, or Tc / S + 1 in a push where some slot's last chunk produced Tc + 1 frames."""
+        if torch.is_tensor(n_samples):
+            raise TypeError("push: the combined session takes host lists for n_samples (it decides on the host whether the stack needs a second push)")
+        B, Tc = self.B, self.Tc
+        rmask, lmask, counts, frames = self.front._controls(n_samples, last, reset)
+        for b in range(B):
+            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 1)):
+                raise ValueError("push: slot %d would yield %d frames from %d samples: off the schedule (first_samples = %d in an utterance's first push, chunk_samples = %d "
+                                 "later, fewer only with last)" % (b, frames[b], counts[b], self.first_samples, self.chunk_samples))
+        with torch.no_grad():
+            feat, _ = self.front.push(wave, counts, lmask, rmask)
+            tail = [f > Tc for f in frames]
+            y, ylen, inter = self.back.push(feat[:, :Tc], torch.tensor([min(f, Tc) for f in frames], dtype=torch.int64), rmask)
+            if not any(tail):
+                return self._head(y), ylen, inter
+            # (a captured stack's results are static: keep this push's before the second one refills them)
+            logits, ylen, inter = self._head(y).clone(), ylen.clone(), {k: [v[0].clone(), v[1].clone()] for k, v in inter.items()}
+            if self._x2 is None:
+                self._x2 = torch.zeros(B, Tc, feat.shape[2], dtype=feat.dtype, device=feat.device)
+            self._x2[:, 0].copy_(feat[:, Tc])
+            y2, ylen2, inter2 = self.back.push(self._x2, torch.tensor([1 if t else 0 for t in tail], dtype=torch.int64), None)
+            for k, v in inter.items():
+                inter[k] = [torch.cat([v[0], inter2[k][0][:, :1]], dim=1), v[1] + inter2[k][1]]
+            return torch.cat([logits, self._head(y2[:, :1].contiguous())], dim=1), ylen + ylen2, inter
+
+    def capture(self, device=None):
+        """capture both halves (AudioFrontStreamSession.capture, ConformerStreamSession.capture); call it before the first push"""
+        self.front.capture(device)
+        self.back.capture(device)
+        return self
+
 
 class VisualEfficientConformerEncoder(nn.Module):
     """nnet/networks.py:442-512"""

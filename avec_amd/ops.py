@@ -1857,18 +1857,12 @@ class AudioStemFn(torch.autograd.Function):
 def mel_spectrogram(audio, window, dft, fb, n_fft, win, hop, n_mels):
     """audio fp32 [B,L]; window [win]; dft fp32 [2*nb][win] (cos rows then -sin rows); fb [nb][n_mels] -> [B,n_mels,L//hop+1] fp32"""
     rt.require_gpu(audio)
-    from .lib import F32
     B, L = audio.shape
     audio = _f32c(audio)
     F = L // hop + 1
-    nb = n_fft // 2 + 1
     frames = empty((B * F, win), torch.float32, audio)
     lib.mel_frames(audio.data_ptr(), window.data_ptr(), frames.data_ptr(), B, L, n_fft, win, hop, rt.stream())
-    spec = empty((B * F, 2 * nb), torch.float32, audio)
-    gemm_nt(frames, dft, spec, B * F, 2 * nb, win, out_f32=True, dtype=F32)
-    out = empty((B, n_mels, F), torch.float32, audio)
-    lib.mel_power_log(spec.data_ptr(), fb.data_ptr(), out.data_ptr(), B, F, nb, n_mels, rt.stream())
-    return out
+    return mel_from_frames(frames, dft, fb, B, F, n_mels)
 
 
 def spec_augment_(mel, lens, mF, Fp, mT, pS, sid):
@@ -2271,3 +2265,81 @@ def stream_advance(pos, reset, chunk_len, full):
     _stream_ctl("stream_advance", pos, reset, chunk_len, pos.numel())
     lib.stream_advance(pos.data_ptr(), _p(reset), _p(chunk_len), int(full), pos.numel(), rt.stream())
     return pos
+
+
+# ============================================================================================
+# Streamed audio front-end (nnet.AudioFrontStreamSession): waveform chunks -> the stem's rows with the offline arithmetic (include/avec_hip.h, csrc/audio_stream.hip)
+# ============================================================================================
+def audio_stream_state(B, device):
+    """what ops.mel_frames_stream / audio_stream_advance carry between pushes: per slot the sample tail, the sample counter and the `ended` flag (one uint8 blob of
+    avec_audio_stream_state_bytes; never cleared: the first push restarts every slot)"""
+    return torch.empty(lib.raw("avec_audio_stream_state_bytes")(int(B)), dtype=torch.uint8, device=device)
+
+
+def _audio_stream_ctl(name, wave, state, n_samples, reset, last):
+    B = wave.shape[0]
+    if not (wave.dim() == 2 and wave.dtype == torch.float32 and wave.stride(1) == 1 and state.dtype == torch.uint8 and state.is_contiguous() and state.device == wave.device):
+        raise ValueError("%s: wave fp32 [B, W] with unit sample stride and a uint8 state blob on its device (got %s %s, %s)" % (name, tuple(wave.shape), wave.dtype, state.dtype))
+    if n_samples is not None and not (n_samples.dtype == torch.int64 and n_samples.device == wave.device and n_samples.is_contiguous() and n_samples.numel() == B):
+        raise ValueError("%s: n_samples must be a contiguous int64 tensor [%d] on the device" % (name, B))
+    for what, f in (("reset", reset), ("last", last)):
+        if f is not None and not (f.device == wave.device and f.is_contiguous() and f.numel() == B and f.dtype in (torch.uint8, torch.bool)):
+            raise ValueError("%s: %s must be a contiguous uint8 / bool mask [%d] on the device" % (name, what, B))
+
+
+def mel_frames_stream(wave, window, state, n_samples=None, reset=None, last=None, *, Tmax, n_fft, win, hop, out=None):
+    """The framing launch of one push: wave [B, W] fp32 (slot b takes its first n_samples[b] samples; default all W) behind the carried tail -> (frames
+    [B * (2 Tmax + 1), win] fp32: the windowed mel frames 2 E0 - 1 .. 2 E1 - 1, zeros elsewhere; out_len [B] int64 = E1 - E0 stem frames; meta [B, 2] int64 for
+    ops.audio_stem_stream).  Reads the state only: ops.audio_stream_advance ends the push.  out: (frames, out_len, meta) to write into.  No synchronisation."""
+    rt.require_gpu(wave)
+    _audio_stream_ctl("mel_frames_stream", wave, state, n_samples, reset, last)
+    B, W = wave.shape
+    if out is None:
+        out = (empty((B * (2 * Tmax + 1), win), torch.float32, wave), torch.empty(B, dtype=torch.int64, device=wave.device),
+               torch.empty(B, 2, dtype=torch.int64, device=wave.device))
+    frames, out_len, meta = out
+    if not (frames.dtype == torch.float32 and frames.is_contiguous() and frames.numel() == B * (2 * Tmax + 1) * win and out_len.dtype == meta.dtype == torch.int64
+            and out_len.is_contiguous() and meta.is_contiguous() and out_len.numel() == B and meta.numel() == 2 * B):
+        raise ValueError("mel_frames_stream: out = (frames fp32 [B (2 Tmax + 1), win], out_len int64 [B], meta int64 [B, 2]), contiguous")
+    lib.mel_frames_stream(wave.data_ptr(), wave.stride(0), window.data_ptr(), frames.data_ptr(), state.data_ptr(), state.numel(), _p(n_samples), _p(reset), _p(last),
+                          out_len.data_ptr(), meta.data_ptr(), B, W, int(Tmax), int(n_fft), int(win), int(hop), rt.stream())
+    return frames, out_len, meta
+
+
+def mel_from_frames(frames, dft, fb, B, F, n_mels):
+    """windowed frames [B * F, win] fp32 -> log-mel [B, n_mels, F] fp32: the DFT GEMM and the power / mel / log kernel of ops.mel_spectrogram, unchanged"""
+    from .lib import F32
+    M, win = frames.shape
+    nb = dft.shape[0] // 2
+    spec = empty((M, 2 * nb), torch.float32, frames)
+    gemm_nt(frames, dft, spec, M, 2 * nb, win, out_f32=True, dtype=F32)
+    out = empty((B, n_mels, F), torch.float32, frames)
+    lib.mel_power_log(spec.data_ptr(), fb.data_ptr(), out.data_ptr(), B, F, nb, n_mels, rt.stream())
+    return out
+
+
+def audio_stem_stream(mel, w, bias, ss, out_len, meta, C, out=None):
+    """mel [B, n_mels, 2 Tmax + 1] fp32 (the push's log-mel columns) -> [B, Tmax, C * n_mels / 2] act: Conv2d(1 -> C, 3x3, s2) + bias, eval-mode BatchNorm (ss: the
+    scale | shift of ops.bn_finalize), Swish, one launch; rows at or past out_len are zeros."""
+    rt.require_gpu(mel)
+    B, NM, Fmax = mel.shape
+    if not (mel.dtype == torch.float32 and mel.is_contiguous() and Fmax % 2 == 1 and ss.dtype == torch.float32 and ss.numel() >= 2 * C and w.dtype == torch.float32
+            and w.is_contiguous() and w.numel() == 9 * C):
+        raise ValueError("audio_stem_stream: mel fp32 [B, n_mels, 2 Tmax + 1] contiguous, w fp32 [C, 1, 3, 3], ss fp32 [>= 2C] (got %s %s, %s, %s)"
+                         % (tuple(mel.shape), mel.dtype, tuple(w.shape), tuple(ss.shape)))
+    Tmax = (Fmax - 1) // 2
+    if out is None:
+        out = torch.empty(B, Tmax, C * (NM // 2), dtype=rt.act_dtype(), device=mel.device)
+    elif not (out.dtype == rt.act_dtype() and out.is_contiguous() and tuple(out.shape) == (B, Tmax, C * (NM // 2))):
+        raise ValueError("audio_stem_stream: out must be contiguous [B, Tmax, C n_mels / 2] in the activation dtype")
+    lib.audio_stem_stream(rt.dt(), mel.data_ptr(), w.data_ptr(), _p(bias), ss.data_ptr(), out.data_ptr(), out_len.data_ptr(), meta.data_ptr(), B, NM, Tmax, C, rt.stream())
+    return out
+
+
+def audio_stream_advance(wave, state, n_samples=None, reset=None, last=None, *, n_fft, win, hop):
+    """end of a push: the tail becomes the samples the next frames still need, n += n_samples, ended |= last, in place; the reset and last flags are cleared (consumed)"""
+    rt.require_gpu(wave)
+    _audio_stream_ctl("audio_stream_advance", wave, state, n_samples, reset, last)
+    B, W = wave.shape
+    lib.audio_stream_advance(wave.data_ptr(), wave.stride(0), state.data_ptr(), state.numel(), _p(n_samples), _p(reset), _p(last), B, W, int(n_fft), int(win), int(hop), rt.stream())
+    return state

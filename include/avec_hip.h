@@ -333,6 +333,36 @@ int avec_relpos_attention_stream(int dtype, const void* q, const void* k, const 
                                  int B, int H, int Tq, int d, int L, float scale, hipStream_t stream);
 int avec_stream_advance(long long* pos, unsigned char* reset, const long long* chunk_len, long long full, int B, hipStream_t stream);
 
+/* ---- streamed audio front-end (nnet.AudioFrontStreamSession; avec_amd/csrc/audio_stream.hip) -------------------------------------------------------------------
+ * Waveform chunks -> the audio stem's rows, with the offline arithmetic (avec_mel_frames -> DFT GEMM -> avec_mel_power_log -> stem).  Mel frame f reads samples
+ * [hop f - win/2, hop f + win/2), reflected at both ends of the utterance; stem frame t reads mel frames 2t - 1, 2t, 2t + 1 (frame -1 and frames past the utterance's
+ * last are the convolution's zero padding).  With n samples heard, E(n) = n < hop + win/2 ? 0 : (n - hop - win/2) / (2 hop) + 1 stem frames can be computed; an
+ * utterance that ends at Ta samples has Ta / (2 hop) + 1.  state (caller-owned, avec_audio_stream_state_bytes, 16-byte aligned, never cleared): per slot the samples
+ * [max(0, 2 hop E(n) - hop - win/2), n) (fewer than 2 (hop + win/2) <= 768), n, and an `ended` flag.
+ * Controls of a push, [B] each: n_samples int64 (NULL: W) = how many samples of wave row b ([B] rows of W samples, row stride ldw) the slot takes, clamped to 0 .. W;
+ * reset bytes (NULL: none): the slot restarts (n = 0, not ended) before the samples -- whatever the state holds is older and counts as absent; last bytes (NULL:
+ * none): the utterance ends with these samples (Ta = n + n_samples must exceed n_fft / 2 as offline: the caller's contract); the slot is then ended: until a reset it
+ * takes no samples and yields 0 frames.  Samples at or past n_samples are never read into a valid output; every read is clamped into its buffer.
+ * One push = avec_mel_frames_stream -> avec_gemm_nt (fp32 DFT, B * Fmax rows) -> avec_mel_power_log(B, Fmax) -> avec_audio_stem_stream -> avec_audio_stream_advance.
+ *
+ * avec_mel_frames_stream: frames [B][Fmax = 2 Tmax + 1][win] = window * samples of mel frames 2 E0 - 1 .. 2 E1 - 1 (E0 = frames before the push, E1 after, E1 - E0
+ *   clamped to Tmax) in rows 0 .. 2 (E1 - E0); every other row, and a row whose mel frame does not exist, is written as zeros.  out_len[b] = E1 - E0;
+ *   meta [B][2] int64 = {mel frame of row 0, number of mel frames that exist (Ta / hop + 1 when last, else 2 E1)}.  Reads the state only.
+ * avec_audio_stem_stream: mel [B][n_mels][Fmax] (avec_mel_power_log on those rows) -> out [B][Tmax][C * n_mels / 2] act: Conv2d(1 -> C, 3x3, stride 2, pad 1) + bias,
+ *   then y * ss[c] + ss[C + c] (eval-mode BatchNorm, the scale | shift of avec_bn_finalize), then Swish, fp32 up to the store; local row r reads local columns
+ *   2r, 2r + 1, 2r + 2; columns whose mel frame (meta) is < 0 or does not exist count as zero; rows at or past out_len[b] are written as zeros.  n_mels even,
+ *   n_mels / 2 a multiple of 8, out 16-byte aligned.
+ * avec_audio_stream_advance: ends the push: shifts the tail (one workgroup per slot, read whole before it is written), n += n_samples, ended |= last, and clears the
+ *   reset and last flags (they are consumed).  The last reader of the controls in the push. */
+long long avec_audio_stream_state_bytes(int B);
+int avec_mel_frames_stream(const float* wave, long long ldw, const float* window, float* frames, const void* state, long long state_bytes,
+                           const long long* n_samples, const unsigned char* reset, const unsigned char* last, long long* out_len, long long* meta,
+                           int B, int W, int Tmax, int n_fft, int win, int hop, hipStream_t stream);
+int avec_audio_stem_stream(int dtype, const float* mel, const float* w, const float* bias, const float* ss, void* out, const long long* out_len,
+                           const long long* meta, int B, int n_mels, int Tmax, int C, hipStream_t stream);
+int avec_audio_stream_advance(const float* wave, long long ldw, void* state, long long state_bytes, const long long* n_samples, unsigned char* reset,
+                              unsigned char* last, int B, int W, int n_fft, int win, int hop, hipStream_t stream);
+
 /* ---- front-ends (avec_amd/csrc/frontend.hip) ------------------------------------------------ */
 /* AudioPreprocessing (nnet/preprocessing.py:57-85; torchaudio Spectrogram/MelScale restated): frames -> [DFT via avec_gemm_nt fp32] -> power/mel/log */
 int avec_mel_frames(const float* audio, const float* window, float* frames, int B, long long L, int n_fft, int win, int hop, hipStream_t stream);
