@@ -770,6 +770,16 @@ static bool s3w_geom(const S3P& G, long long clips, S3W& Q, size_t* lds) {
 extern "C" int avec_stem3p_wgrad_supported(long long clips, int T_, int H, int W) {
   S3P G; S3W Q; size_t a, b, c; return (s3p_geom(G, clips, T_, H, W, &a, &b) && s3w_geom(G, clips, Q, &c)) ? 1 : 0;
 }
+// what s3p_geom / s3w_geom decided for a clip shape (tests assert through it that a case still reaches the band layout it names):
+// out[10] = NB, pn, PH, PW, OH, OW, pitch, s3w_geom accepts (0 / 1), frames per weight-gradient unit, units per clip and band (both 0 without s3w_geom)
+extern "C" int avec_stem3p_geom(long long clips, int T_, int H, int W, int* out) {
+  S3P G; S3W Q; size_t a, b, c;
+  if (!out || !s3p_geom(G, clips, T_, H, W, &a, &b)) return 0;
+  const bool w = s3w_geom(G, clips, Q, &c);
+  const int v[10] = {G.NB, G.pn, G.PH, G.PW, G.OH, G.OW, G.pitch, w ? 1 : 0, w ? Q.CH : 0, w ? Q.NCH : 0};
+  for (int i = 0; i < 10; ++i) out[i] = v[i];
+  return 1;
+}
 
 extern "C" int avec_stem3p_wgrad(const void* video_bf16, const void* w_shadow, const float* bias, const void* dpool_masked, const unsigned char* idx, const float* ss,
                                  const float* gamma, const float* dstats, const float* count_ptr, float count, float* dw, float* dgamma, float* dbeta,

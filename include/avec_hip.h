@@ -403,6 +403,9 @@ int avec_stem3p_fwd(const void* video_bf16, const void* w_shadow, const float* b
 int avec_stem3p_reduce(void* dpool, const void* zp, const float* ss, float* dstats, long long frames, int PH, int PW, hipStream_t stream);
 /* fused: dw fp32 [64][245] += the stem's weight gradient straight from the pooled gradients (z recomputed per tile, dz formed in LDS, never written) */
 int avec_stem3p_wgrad_supported(long long clips, int T, int H, int W);
+/* the layout the two kernels' geometry rules chose (host only; 0 when avec_stem3p_supported is 0): out int[10] = bands per frame NB, pooled rows per band pn, PH, PW,
+ * OH, OW, staged row pitch in bytes, avec_stem3p_wgrad_supported, frames per weight-gradient unit, units per clip and band (both 0 where the fused kernel declines) */
+int avec_stem3p_geom(long long clips, int T, int H, int W, int* out);
 int avec_stem3p_wgrad(const void* video_bf16, const void* w_shadow, const float* bias, const void* dpool_masked, const unsigned char* idx, const float* ss,
                       const float* gamma, const float* dstats, const float* count_ptr, float count, float* dw, float* dgamma, float* dbeta,
                       long long clips, int T, int H, int W, hipStream_t stream);

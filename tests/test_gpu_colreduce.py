@@ -524,7 +524,7 @@ def test_stem_pool_bwd_reduce_pooled(dtype):
 # visual stem (avec_stem3d_fwd / _wgrad, avec_stem3p_fwd / _reduce / _wgrad): the same clip with the workspace owned by the test, two-pass against atomics
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 LOST_PARTIAL = 1.0 / (2 * 2048)              # the size of one lost partial at the largest slot count (module header)
-# worst twopass-versus-atomics rel_err (max |a - b| / max |b|) per tensor over the four paths (pooled, pooled_unfused, direct, im2col), measured on the parent
+# worst twopass-versus-atomics rel_err (max |a - b| / max |b|) per tensor over the four modes (pooled, pooled_unfused, direct, im2col), measured on the parent
 # commit, the one BEFORE the launch sites moved to ColPlan; the bound is 8 x that, the margin this module uses over a measured baseline.  A measured 0 is a bound
 # of 0: the tensor is bit-equal in the two regimes.
 STEM_REGIME_MEASURED = {
@@ -532,8 +532,11 @@ STEM_REGIME_MEASURED = {
     (1, 5, 40, 64): {"stem output": 0.0, "conv weight gradient": 3.17e-6, "bn weight gradient": 3.02e-7, "running variance (batch statistics)": 6.43e-8, "bn bias gradient": 2.75e-8},
 }
 # (1, 5, 40, 64) stands in for (1, 5, 48, 64), the W % 8 == 0 shape of tests/test_gpu_parity.py: on the parent the weight gradient at (1, 5, 48, 64) differs by
-# 1.29e-4 between the regimes in some runs (direct and pooled paths), and 8 x that is 1.0e-3, above LOST_PARTIAL; (1, 4, 56, 48) gave 2.04e-4.  (1, 5, 40, 64)
-# (T = 5, W % 8 == 0: all four paths run) and (1, 5, 56, 56) stayed at 3.2e-6 / 1.5e-6.
+# 1.29e-4 between the regimes in some runs (direct and "pooled" modes), and 8 x that is 1.0e-3, above LOST_PARTIAL; (1, 4, 56, 48) gave 2.04e-4.  (1, 5, 40, 64)
+# and (1, 5, 56, 56) stayed at 3.2e-6 / 1.5e-6.
+# At BOTH shapes below avec_stem3p_supported is 0 (s3p_geom serves W = 88 and W = 96 only), so the modes "pooled" and "pooled_unfused" fall through to stem3d.hip:
+# three distinct paths run here (direct under three names, and im2col).  The two regimes of the stem3p kernels (forward statistics, stem3p_reduce, the fused
+# weight gradient) are compared -- for equality -- in tests/test_gpu_stem_exact.py.
 STEM_REGIME_SHAPES = [(1, 3, 72, 40), (1, 5, 40, 64)]
 
 
@@ -541,7 +544,8 @@ STEM_REGIME_SHAPES = [(1, 3, 72, 40), (1, 5, 40, 64)]
 def test_visual_stem_twopass_matches_atomics(shape):
     """tests/test_gpu_parity.py's visual-stem comparison (its smallest shape and a T = 5, W % 8 == 0 shape) run twice, with the reduction workspace owned by Ws("twopass")
     and by Ws("atomics"): the path-against-path assertions of that test hold in each, the poisoned workspace shows that the two-pass branch ran, and every tensor
-    of every path agrees between the regimes within 8 x STEM_REGIME_MEASURED[shape]:
+    of every path agrees between the regimes within 8 x STEM_REGIME_MEASURED[shape].  The paths are stem3d.hip (under the mode names "pooled", "pooled_unfused"
+    and "direct": the pooled kernels decline both widths) and im2col; stem3p.hip's regimes are covered by tests/test_gpu_stem_exact.py.
 
                                                 (1, 3, 72, 40)                   (1, 5, 40, 64)
                                                 parent       bound (x 8)        parent       bound (x 8)

@@ -12,7 +12,7 @@ Geometry: every family here accepts non-square images (none rejects them), so ea
 OW = 2 (the limits of the stride-2 kernel; OW = 16 falls to the parity-class order of the LDS-DMA kernel), the shifted-window kernel W = 31 (W = 32 falls through);
 image counts leave the last tile ragged, 128-row tiles straddle image boundaries (8x8 images), and every family runs one image alone.
 
-Not here (see the issue this file answers): the stems, the fp8 products, the env-forced variants (AVEC_NO_*, AVEC_SHIFT_BM, AVEC_NT_RB: read once per process).
+Not here (see the issue this file answers): the stems (tests/test_gpu_stem_exact.py has them), the fp8 products, the env-forced variants (AVEC_NO_*, AVEC_SHIFT_BM, AVEC_NT_RB: read once per process).
 The BatchNorm-backward fusion has no register-direct form: epi_tr_ok() and the stride-2 kernel decline a launch that carries bnb_y, so it is tested in the staged
 epilogue from every kernel that reaches it.
 """
