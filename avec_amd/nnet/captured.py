@@ -1,5 +1,5 @@
 """Captured steps: the capture procedure (CapturedStep) and the shape-keyed cache of captured training steps (StepCache).  Host sequencing only: what a captured
-body launches is its caller's business (nnet/model.py: the whole training step and the micro-step; nnet/networks.py: one push of a streaming session)."""
+body launches is its caller's business (nnet/model.py: the whole training step and the micro-step; nnet/streaming.py: one push of a streaming session)."""
 import gc
 import time
 import warnings

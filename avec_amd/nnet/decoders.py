@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .streaming import CTCBeamStreamSession
 
 
 def ctc_collapse(tokens, length, blank=0):
@@ -292,86 +293,6 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
             tokens, lens = outputs
             ids = [t[:int(n)].tolist() for t, n in zip(tokens.cpu(), lens.cpu())]
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
-
-
-class CTCBeamStreamSession:
-    """CTCBeamSearchDecoder.stream(): the beam search of avec_amd/csrc/ctc_beam.hip carried across logit chunks (one launch per push, the beam state stays on the
-    device).  The search is the offline one bit for bit: after any sequence of pushes the beams are those of beam_search on the frames pushed so far."""
-
-    def __init__(self, decoder, batch_size, max_frames):
-        self.dec, self.B, self.max_frames = decoder, int(batch_size), int(max_frames)
-        if self.B < 1 or self.max_frames < 1:
-            raise ValueError("stream: batch_size %d, max_frames %d" % (self.B, self.max_frames))
-        self.state = None                                # ops.CTCBeamStreamState, allocated by the first push (it knows the device)
-        self._frames = [0] * self.B                      # per slot, an upper bound of the frames it holds (Tc per push): the capacity check needs no sync
-        self._emitted = False                            # the state's outputs describe every frame pushed so far
-
-    def _launch(self, chunk, chunk_len, reset, emit):
-        d = self.dec
-        out = ops.ctc_beam_stream(self.state, chunk, chunk_len, reset, d.ngram_tmp, d.lm(chunk.shape[-1]), d.ngram_alpha, d.ngram_beta, emit=emit)
-        self._emitted = emit
-        return out
-
-    def push(self, logits_chunk, chunk_len=None, reset=None, fetch=True):
-        """Consume logits_chunk [B, Tc, V]; slot b takes chunk_len[b] frames of it (int64 tensor; default: all Tc).  reset: slots to restart from the empty
-        transcript before this chunk, as a list of indices or a host bool mask [B] (a device mask costs a synchronisation); the first push resets every slot.
-        A push after which a slot could hold more than max_frames frames raises RuntimeError before anything is launched (each push counts as Tc frames for every
-        slot, whatever chunk_len says).
-        fetch=True returns one record per slot: {"partial_ids": the best hypothesis so far (the n-gram beam's; neural rescoring happens in finish()),
-        "stable_ids": its leading tokens that every live beam shares and no later frame can change}, and with a tokenizer "partial" and "stable", their text.
-        "stable" is decode(stable_ids): it is final token by token, not character by character (a later piece can still complete its last word).
-        fetch=False skips the traceback and copies nothing to the host."""
-        B, Tc, self._V = logits_chunk.shape
-        if B != self.B:
-            raise ValueError("push: chunk of %d utterances for a session of %d" % (B, self.B))
-        first = self.state is None
-        if first:
-            mask = [True] * B
-        elif reset is None:
-            mask = None
-        else:
-            r = reset.cpu().tolist() if torch.is_tensor(reset) else list(reset)
-            if len(r) == B and all(isinstance(x, bool) for x in r):
-                mask = r
-            else:
-                mask = [False] * B
-                for i in r:
-                    mask[int(i)] = True
-        frames = [(0 if mask is not None and mask[b] else n) + Tc for b, n in enumerate(self._frames)]
-        if max(frames) > self.max_frames:
-            raise RuntimeError("push: %d frames in a slot of a session with max_frames = %d" % (max(frames), self.max_frames))
-        if first:
-            self.state = ops.CTCBeamStreamState(B, self.dec.beam_size, self.max_frames, logits_chunk.device)
-        flags = None
-        if mask is not None and any(mask):
-            flags = self.state.reset_flags
-            flags.copy_(torch.tensor(mask, dtype=torch.uint8), non_blocking=True)
-        self._frames = frames
-        out = self._launch(logits_chunk, chunk_len, flags, fetch)
-        if not fetch:
-            return None
-        tokens, out_len, _, _, stable_len = out
-        tok0, len0, st = tokens[:, 0].cpu(), out_len[:, 0].cpu().tolist(), stable_len.cpu().tolist()
-        tk = self.dec.tokenizer
-        recs = []
-        for b in range(B):
-            rec = {"partial_ids": tok0[b, :len0[b]].tolist(), "stable_ids": tok0[b, :st[b]].tolist()}
-            if tk is not None:
-                rec["partial"], rec["stable"] = tk.decode(rec["partial_ids"]), tk.decode(rec["stable_ids"])
-            recs.append(rec)
-        return recs
-
-    def finish(self):
-        """What decoder.beam_search returns for the frames pushed: per slot the winning token list (rescored by the neural LM when one is loaded)."""
-        if self.state is None:
-            raise RuntimeError("finish: nothing was pushed")
-        st = self.state
-        if not self._emitted:                            # one launch that consumes no frame and emits
-            self._launch(torch.zeros(self.B, 1, self._V, device=st.state.device), torch.zeros(self.B, dtype=torch.int64, device=st.state.device), None, True)
-        if self.dec.neural_rescorer is not None:
-            return self.dec._rescore(st.tokens, st.out_len, st.score, self.B, 1)
-        tok0, len0 = st.tokens[:, 0].cpu(), st.out_len[:, 0].cpu().tolist()
-        return [tok0[b, :len0[b]].tolist() for b in range(self.B)]
 
 
 decoder_dict = {"CTCGreedySearchDecoder": CTCGreedySearchDecoder, "CTCBeamSearchDecoder": CTCBeamSearchDecoder, "CTCBeamSearch": CTCBeamSearchDecoder}

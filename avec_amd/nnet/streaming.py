@@ -1,0 +1,552 @@
+"""Streaming sessions: a causal Conformer stack, the audio front-end and the CTC beam search run chunk by chunk over a fixed number of utterance slots.  None of
+them has a counterpart in the reference; the factories (ConformerInterCTC.stream, AudioEfficientConformerEncoder.stream_front / .stream, CTCBeamSearchDecoder.stream)
+stay with the classes they wrap.  A session owns its device state; nothing is added to a module tree or a state_dict."""
+import torch
+import torch.nn as nn
+
+from .. import ops
+from .. import runtime as rt
+from . import attentions, normalizations
+from .captured import CapturedStep
+
+__all__ = ["slot_mask", "ConformerStreamSession", "AudioFrontStreamSession", "AudioStreamSession", "CTCBeamStreamSession"]
+
+
+def slot_mask(flags, B):
+    """reset / last as passed to a push (None, a list of slot indices, a host bool mask [B], or a tensor of either) -> a bool list [B]"""
+    if flags is None:
+        return [False] * B
+    r = flags.cpu().tolist() if torch.is_tensor(flags) else list(flags)
+    if len(r) == B and all(isinstance(v, bool) for v in r):
+        return r
+    mask = [False] * B
+    for k in r:
+        mask[int(k)] = True
+    return mask
+
+
+class _StreamSession:
+    """What every session keeps: B slots, `_first` (the first push restarts every slot), device state allocated by the first push (it knows the device; the
+    subclass's _allocate(dev)) and uint8 flag vectors that a push uploads only when some flag is set."""
+
+    def __init__(self, batch_size):
+        self.B = int(batch_size)
+        self.state = None
+        self._first = True
+
+    def _reset_mask(self, reset):
+        """the first push restarts every slot; later, None stays None (nothing to upload, nothing to check)"""
+        if self._first:
+            return [True] * self.B
+        return None if reset is None else slot_mask(reset, self.B)
+
+    def _flags(self, dev):
+        return torch.zeros(self.B, dtype=torch.uint8, device=dev)
+
+    @staticmethod
+    def _raise_flags(buf, mask):
+        """upload a flag vector only when some flag is set (the push's last launch clears it again: no memset afterwards) -> buf, or None when none is"""
+        if mask is None or not any(mask):
+            return None
+        return buf.copy_(torch.tensor(mask, dtype=torch.uint8), non_blocking=True)
+
+    def _ensure_state(self, dev):
+        if self.state is None:
+            self._allocate(dev)
+
+
+class _CapturableSession(_StreamSession):
+    """A session over an eval-mode `module` whose push is a fixed sequence of launches: the tail of push and capture() for the subclass's _upload(*controls) (flag
+    and count vectors to the device), _run(x) (the eager launches), _static_input(dev) (a zero input and a first push's controls) and _forget() (reset whatever
+    the host mirrors of the warm-up pushes)."""
+
+    def __init__(self, module, batch_size):
+        super().__init__(batch_size)
+        self.module = module
+        self._capture = None               # the CapturedStep of one push, after capture()
+
+    def _push(self, x, *controls):
+        """the device side of a push: flag and count uploads, then the input copy and the replay, or the eager launches"""
+        with torch.no_grad():
+            self._ensure_state(x.device)
+            self._upload(*controls)
+            self._first = False
+            if self._capture is not None:
+                self._capture.load((x,), ())
+                return self._capture.replay()
+            return self._run(x)
+
+    def capture(self, device=None):
+        """Capture one push as a graph on static input / count / flag buffers; push then copies into them and replays (the device counters make every replay
+        advance).  Call it on a fresh session, before the first push; the warm-up pushes it runs are forgotten (the next push restarts every slot).  After it the
+        results of a push are static tensors that the next push overwrites."""
+        if self._capture is not None:
+            return self
+        if not self._first:
+            raise RuntimeError("capture: call it before the first push of the session")
+        p = next(self.module.parameters())
+        dev = torch.device(device) if device is not None else p.device
+        rt.require_gpu(p)
+        with torch.no_grad(), torch.cuda.device(dev):
+            self._ensure_state(dev)
+            x, controls = self._static_input(dev)
+            cap = CapturedStep((x,))
+            x = cap.inputs[0]
+            self._upload(*controls)
+            cap.warm_up(lambda: self._run(x), 2)        # weight shadows, lazy kernel attributes, allocator
+            cap.capture(lambda: self._run(x))
+        self._capture = cap
+        self._forget()
+        return self
+
+
+class ConformerStreamSession(_CapturableSession):
+    """ConformerInterCTC.stream(): a causal stack run chunk by chunk.  After any sequence of push calls the rows a slot has produced equal the rows that
+    stack(x, lengths) produces offline (eval mode, the same Mask) on the frames pushed so far for that slot, up to floating-point summation order, for every split
+    into chunks.  Everything row-wise (LayerNorm, the feed-forward and pointwise products, the InterCTC modules, the strided k=1 residual) runs through the offline
+    eval-path launchers; the depthwise convolution's left context and the attention's keys / values are carried by ops.glu_dwconv_stream / relpos_attention_stream in
+    buffers this object owns.  Per slot a frame counter lives on the device; a restart only sets a flag that the kernels read: whatever the buffers hold from
+    before the restart is older than the counter and counts as absent."""
+
+    def __init__(self, stack, batch_size, chunk_frames):
+        super().__init__(stack, batch_size)
+        self.stack, self.Tc = stack, int(chunk_frames)
+        self.plan = self._check(stack)
+        self.S = 1
+        for p in self.plan:
+            self.S *= p["stride"]
+        if self.B < 1:
+            raise ValueError("stream: batch_size %d" % self.B)
+        if self.Tc < 1 or self.Tc % self.S:
+            raise ValueError("stream: chunk_frames = %d must be a positive multiple of the stack's total stride %d (every push then yields whole output frames at every stage)"
+                             % (self.Tc, self.S))
+        for p in self.plan:
+            if p["K"] - 1 + self.Tc // p["div"] > 96:
+                raise ValueError("stream: chunk_frames = %d is %d frames at a stage with a %d-tap convolution: at most %d (the kernel holds context + chunk in LDS)"
+                                 % (self.Tc, self.Tc // p["div"], p["K"], 97 - p["K"]))
+        self._short = [False] * self.B     # host mirror of "this slot's last chunk was short" (the contract check of host-list chunk lengths: no sync)
+
+    @staticmethod
+    def _check(stack):
+        """-> per block {div, stride, L, K}; raises before anything is launched"""
+        if stack.training:
+            raise RuntimeError("stream: the stack is in training mode (BatchNorm batch statistics and dropout are not functions of the past): call .eval() first")
+        m = stack.mask
+        if not isinstance(m, attentions.Mask):
+            raise NotImplementedError("stream: the stack needs a streaming Mask(left_context=L, right_context=0), got mask=%r" % (m,))
+        if m.left_context is None:
+            raise NotImplementedError("stream: left_context=None would need an unbounded key/value cache; give the Mask an integer left_context")
+        if not isinstance(m.left_context, int) or m.left_context < 0:
+            raise NotImplementedError("stream: left_context=%r must be an integer >= 0" % (m.left_context,))
+        if m.right_context != 0:
+            raise NotImplementedError("stream: right_context=%r needs look-ahead buffering (only right_context=0 is streamed)" % (m.right_context,))
+        if (m.mask_start or 0) > 1:
+            raise NotImplementedError("stream: mask_start=%r opens a block of future keys at the start of the utterance (only mask_start <= 1 is causal)" % (m.mask_start,))
+        plan, div = [], 1
+        for i, blk in enumerate(stack.conformer_blocks):
+            att = blk.self_att_module.attention
+            if isinstance(att, attentions.RelPosPatch1dMultiHeadAttention):
+                raise NotImplementedError("stream: block %d uses RelPosPatch1dMultiHeadAttention (patch attention): under a causal mask the min-pooled patch mask hides a patch "
+                                          "from itself, its first patch row keeps no key and the offline kernels then average over ALL keys of the utterance, future ones "
+                                          "included -- not a function of the past, so no chunked form can equal it" % i)
+            if isinstance(att, attentions.RelPosMultiHeadSelfAttention):
+                raise NotImplementedError("stream: block %d uses grouped / Transformer-XL attention (%s): its `hidden` cache grows without bound and is not streamed here"
+                                          % (i, type(att).__name__))
+            if type(att) is not attentions.RelPos1dMultiHeadAttention:
+                raise NotImplementedError("stream: block %d attention %s is not RelPos1dMultiHeadAttention" % (i, type(att).__name__))
+            dw, bn = blk.conv_module.layers[3], blk.conv_module.layers[4]
+            if getattr(dw, "padding_type", "same") != "causal":
+                raise NotImplementedError("stream: block %d depthwise conv has padding=%r: only padding='causal' depends on the past alone" % (i, getattr(dw, "padding_type", "same")))
+            if not (bn.track_running_stats and bn.running_mean is not None):
+                raise NotImplementedError("stream: block %d BatchNorm keeps no running statistics" % i)
+            plan.append({"div": div, "stride": blk.stride, "L": m.left_context // div, "K": dw.kernel_size[0]})
+            div *= blk.stride
+        return plan
+
+    # ---- device state ----------------------------------------------------------------------------------------------------------------------------------------------
+    def _allocate(self, dev):
+        B = self.B
+        self.pos = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.reset_flags = self._flags(dev)
+        self.clen = torch.full((B,), self.Tc, dtype=torch.int64, device=dev)
+        self._clen_full = True
+        self.state = []                    # per block: E table, key / value rings, conv context, BatchNorm scale | shift
+        for p, blk in zip(self.plan, self.stack.conformer_blocks):
+            att, dw, bn = blk.self_att_module.attention, blk.conv_module.layers[3], blk.conv_module.layers[4]
+            D, H, L, Tq = att.dim_model, att.num_heads, p["L"], self.Tc // p["div"]
+            C = dw.weight.shape[0]
+            # E[delta] = pos_layer(PE(delta)), delta = 0 .. L: the first L + 1 rows of the offline table are the positions L .. 0, the same for every T
+            pe = ops.rel_pos_table(L + 1, D, dev)[:L + 1].flip(0)
+            e = ops.linear_fwd(pe, att.pos_layer.weight, att.pos_layer.bias, L + 1, in_f32=False, out_f32=False)
+            kc, vc = ops.relpos_attention_stream_state(B, H, D // H, L, Tq, dev)
+            st = ops.BNState(C, pe)
+            ops.bn_finalize(bn, st, 1, False)              # eval mode: scale | shift from the running statistics
+            self.state.append({"e": e, "kc": kc, "vc": vc, "ss": st.ss, "ctx": ops.glu_dwconv_stream_state(B, C, p["K"], dev)})
+
+    # ---- one push, eager: a fixed sequence of launches on the current stream ------------------------------------------------------------------------------------
+    def _attention(self, p, st, blk, x):
+        mod = blk.self_att_module
+        att, ln = mod.attention, mod.norm
+        B, Tq, D = x.shape
+        M = B * Tq
+        x2 = ops._f32c(x.reshape(M, D))
+        h, _, _ = ops.layernorm_fwd(x2, ln.weight, ln.bias, M, D, False, ln.eps)
+        q, k, v = att.query_layer, att.key_layer, att.value_layer
+        qkv = ops.qkv_project(h, ((q.weight, k.weight, v.weight), (q.bias, k.bias, v.bias)), M, D)
+        o = ops.relpos_attention_stream(qkv, st["e"], st["kc"], st["vc"], self.pos, self.reset_flags, self.clen, p["div"], B=B, H=att.num_heads, L=p["L"])
+        return ops.linear_fwd(o, att.output_layer.weight, att.output_layer.bias, M, in_f32=False, out_f32=True, res=x2, alpha=1.0).view(B, Tq, D)
+
+    def _conv(self, p, st, blk, x):
+        mod = blk.conv_module
+        ln, pw1, dw, pw2 = mod.layers[0], mod.layers[1], mod.layers[3], mod.layers[6]
+        res_conv = None if isinstance(blk.conv_res, nn.Identity) else blk.conv_res
+        B, Tq, D = x.shape
+        Dp, s = dw.weight.shape[0], p["stride"]
+        To = Tq // s
+        M, Mo, adt = B * Tq, B * To, rt.act_dtype()
+        x2 = ops._f32c(x.reshape(M, D))
+        h, _, _ = ops.layernorm_fwd(x2, ln.weight, ln.bias, M, D, False, ln.eps)
+        u = ops.linear_fwd(h, pw1.weight, pw1.bias, M, in_f32=False, out_f32=False)
+        a = ops.glu_dwconv_stream(u.view(B, Tq, 2 * Dp), dw.weight, dw.bias, st["ss"], st["ctx"], self.pos, self.reset_flags, self.clen, p["div"], s)
+        if res_conv is not None:
+            rs = res_conv.stride[0]
+            R = ops.linear_fwd(x2, res_conv.weight, res_conv.bias, Mo, in_f32=(adt != torch.float32), out_f32=True, rows=ops.rows_plain(D, To, Tq, rs) if rs > 1 else None)
+        else:
+            R = x2
+        return ops.linear_fwd(a.view(Mo, Dp), pw2.weight, pw2.bias, Mo, in_f32=False, out_f32=True, res=R, alpha=1.0).view(B, To, Dp)
+
+    def _run(self, x):
+        stack = self.stack
+        lengths, inter, j = self.clen, {}, 0
+        for i, (p, st, blk) in enumerate(zip(self.plan, self.state, stack.conformer_blocks)):
+            x = blk.ff_module1.residual_forward(x, 0.5)
+            x = self._attention(p, st, blk, x)
+            x = self._conv(p, st, blk, x)
+            x = blk.ff_module2.residual_forward(x, 0.5)
+            if isinstance(blk.norm, nn.LayerNorm):
+                x = normalizations.torch_layer_norm_forward(blk.norm, x, getattr(blk, "_next_ln", None))
+            logits = None
+            if i + 1 in stack.interctc_blocks:
+                x, logits = stack.interctc_modules[j](x)
+                j += 1
+            if p["stride"] > 1:
+                lengths = ops.len_affine(lengths, 1, p["stride"], 1)
+            if logits is not None:
+                inter[stack.loss_prefix + "_" + str(i)] = [logits, lengths]
+        if lengths is self.clen:
+            lengths = lengths.clone()
+        ops.stream_advance(self.pos, self.reset_flags, self.clen, self.Tc)
+        return x, lengths, inter
+
+    # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
+    def _controls(self, chunk_len, reset):
+        B = self.B
+        mask = self._reset_mask(reset)
+        host_len = None
+        if chunk_len is not None and not torch.is_tensor(chunk_len):
+            host_len = [int(v) for v in chunk_len]
+            if len(host_len) != B or any(v < 0 or v > self.Tc for v in host_len):
+                raise ValueError("push: chunk_len %r for %d slots of at most %d frames" % (host_len, B, self.Tc))
+        if not torch.is_tensor(chunk_len):
+            for b in range(B):                # (a slot that has ended may idle: further chunks of 0 frames change nothing)
+                if self._short[b] and not (mask is not None and mask[b]) and (self.Tc if host_len is None else host_len[b]) > 0:
+                    raise RuntimeError("push: slot %d ended with a short chunk and was not reset: a chunk shorter than chunk_frames is legal only as the last one "
+                                       "of an utterance (pass reset=[%d] with the next utterance's first chunk)" % (b, b))
+        return mask, host_len
+
+    def _upload(self, mask, host_len, chunk_len):
+        self._raise_flags(self.reset_flags, mask)
+        if torch.is_tensor(chunk_len):
+            self.clen.copy_(chunk_len.view(self.B), non_blocking=True)
+            self._clen_full = False
+            self._short = [False] * self.B           # a device tensor's contract is the caller's
+        elif host_len is not None:
+            full = all(v == self.Tc for v in host_len)
+            if not (full and self._clen_full):
+                self.clen.copy_(torch.tensor(host_len, dtype=torch.int64), non_blocking=True)
+            self._clen_full = full
+            self._short = [v < self.Tc for v in host_len]
+        else:
+            if not self._clen_full:
+                self.clen.fill_(self.Tc)
+                self._clen_full = True
+            self._short = [False] * self.B
+
+    def _static_input(self, dev):
+        D0 = self.stack.conformer_blocks[0].ff_module1.layers[0].normalized_shape[0]
+        return torch.zeros(self.B, self.Tc, D0, dtype=torch.float32, device=dev), ([True] * self.B, None, None)
+
+    def _forget(self):
+        self._short = [False] * self.B
+
+    def push(self, x_chunk, chunk_len=None, reset=None):
+        """x_chunk [B, Tc, D] (the stack's input features) -> (y [B, Tc / S, D_out] fp32, out_len [B] int64 on the device, inter: the offline forward's dict
+        loss_prefix_i -> [logits chunk, lengths]).  Slot b takes the first chunk_len[b] frames (a Python list or an int64 device tensor [B]; default all Tc); fewer
+        than Tc is legal only as the slot's last chunk before a reset -- until then the slot may only idle on chunks of 0 frames (checked on the host for a list; the
+        caller's contract for a device tensor).  Rows at or past
+        chunk_len are computed from whatever was passed and never reach the carried state.  reset: slots to restart before this chunk, a list of indices or a host
+        bool mask [B]; the first push restarts every slot.  No host synchronisation after the first push; after capture() the results are static tensors that the
+        next push overwrites."""
+        if x_chunk.dim() != 3 or x_chunk.shape[0] != self.B or x_chunk.shape[1] != self.Tc:
+            raise ValueError("push: chunk %s for a session of %d slots x %d frames" % (tuple(x_chunk.shape), self.B, self.Tc))
+        rt.require_gpu(x_chunk)
+        if self.stack.training:
+            raise RuntimeError("push: the stack went back to training mode; call .eval()")
+        mask, host_len = self._controls(chunk_len, reset)
+        return self._push(x_chunk, mask, host_len, chunk_len)
+
+
+class AudioFrontStreamSession(_CapturableSession):
+    """AudioEfficientConformerEncoder.stream_front(): the audio front-end (log-mel -> Conv2d + BatchNorm2d + Swish stem -> Linear) run on waveform chunks.  The frames a
+    slot has produced after any sequence of pushes equal the offline front-end's frames on the samples pushed so far (and, once the utterance has ended, on the whole
+    utterance: both STFT reflections and both zero paddings of the stem included), up to the DFT GEMM's tile choice.  Mel frame f reads samples [160 f - 200, 160 f + 200),
+    stem frame t reads mel frames 2t - 1, 2t, 2t + 1: with n samples heard E(n) = 0 if n < 360 else (n - 40) // 320 frames exist, Ta // 320 + 1 at the end.  Schedule:
+    first_samples = 320 Tc + 40 in an utterance's first push, chunk_samples = 320 Tc in every later one; every push but the last then yields exactly Tc frames, the last at
+    most Tc + 1.  The carried state is a sample tail of fewer than 720 samples per slot, a counter and an `ended` flag, on the device (ops.audio_stream_state)."""
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        super().__init__(enc, batch_size)
+        self.enc, self.Tc = enc, int(chunk_frames)
+        self._check(enc)
+        if self.B < 1:
+            raise ValueError("stream_front: batch_size %d" % self.B)
+        if self.Tc < 2:
+            raise ValueError("stream_front: chunk_frames = %d: a push of %d samples would be shorter than one %d-sample analysis window; at least 2 frames (80 ms) per push"
+                             % (self.Tc, 2 * self.hop * self.Tc, self.win))
+        self.first_samples, self.chunk_samples = 2 * self.hop * self.Tc + (self.win // 2 - self.hop), 2 * self.hop * self.Tc
+        self.Tmax = self.Tc + 2                    # any count up to first_samples, at the end of an utterance too, gives at most Tc + 2 frames
+        self._n = [0] * self.B                     # host mirror of the device counters (None: unknown after a push with device-tensor counts)
+        self._ended = [False] * self.B
+        self._ns_up = None                         # what self.nsamp holds
+
+    def _check(self, enc):
+        if enc.training:
+            raise RuntimeError("stream_front: the encoder is in training mode (SpecAugment and BatchNorm batch statistics are not functions of the past): call .eval() first")
+        pre = enc.audio_preprocessing
+        if pre.normalize:
+            raise NotImplementedError("stream_front: AudioPreprocessing(normalize=True) is not streamed: the stem's zero padding would have to become (0 - mean) / std columns")
+        conv, bn = enc.subsampling_module.layers[0][0], enc.subsampling_module.layers[0][1]
+        if not (bn.track_running_stats and bn.running_mean is not None):
+            raise NotImplementedError("stream_front: the stem's BatchNorm keeps no running statistics")
+        self.n_fft, self.win, self.hop, self.n_mels = pre.n_fft, pre.win_length, pre.hop_length, pre.n_mels
+        if self.win // 2 < self.hop or self.win % 2:
+            raise NotImplementedError("stream_front: window %d / hop %d: the schedule needs an even window of at least two hops" % (self.win, self.hop))
+        if tuple(conv.weight.shape[1:]) != (1, 3, 3):
+            raise NotImplementedError("stream_front: the stem is not a 3x3 convolution of one input channel")
+
+    def _ready(self, n):
+        a = self.hop + self.win // 2
+        return 0 if n < a else (n - a) // (2 * self.hop) + 1
+
+    def _allocate(self, dev):
+        bn = self.enc.subsampling_module.layers[0][1]
+        self.state = ops.audio_stream_state(self.B, dev)
+        self.nsamp = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        self.reset_flags, self.last_flags = self._flags(dev), self._flags(dev)
+        st = ops.BNState(bn.num_features, self.state)
+        ops.bn_finalize(bn, st, 1, False)              # eval mode: scale | shift from the running statistics
+        self.ss = st.ss
+
+    def _run(self, wave):
+        if not (wave.dtype == torch.float32 and wave.stride(1) == 1):
+            wave = wave.float().contiguous()
+        enc, pre = self.enc, self.enc.audio_preprocessing
+        conv, lin = enc.subsampling_module.layers[0][0], enc.linear
+        B, Tmax = self.B, self.Tmax
+        kw = dict(n_fft=self.n_fft, win=self.win, hop=self.hop)
+        frames, out_len, meta = ops.mel_frames_stream(wave, pre.Spectrogram.window, self.state, self.nsamp, self.reset_flags, self.last_flags, Tmax=Tmax, **kw)
+        mel = ops.mel_from_frames(frames, pre._dft_matrix(wave.device), pre.MelScale.fb, B, 2 * Tmax + 1, self.n_mels)
+        a = ops.audio_stem_stream(mel, conv.weight, conv.bias, self.ss, out_len, meta, conv.weight.shape[0])
+        ops.audio_stream_advance(wave, self.state, self.nsamp, self.reset_flags, self.last_flags, **kw)
+        feat = ops.linear_fwd(a.view(B * Tmax, -1), lin.weight, lin.bias, B * Tmax, in_f32=False, out_f32=True)
+        return feat.view(B, Tmax, -1), out_len
+
+    # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
+    def _controls(self, n_samples, last, reset):
+        """-> (reset mask, last mask, host counts or None for a device tensor, frames per slot or None): checks a host-list push against the contract, changes nothing"""
+        B = self.B
+        rmask = self._reset_mask(reset) or [False] * B
+        lmask = slot_mask(last, B)
+        if torch.is_tensor(n_samples):
+            return rmask, lmask, None, None
+        if n_samples is not None and len(n_samples) != B:
+            raise ValueError("push: n_samples %r for %d slots" % (list(n_samples), B))
+        counts, frames = [], []
+        for b in range(B):
+            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
+            if n0 is None:
+                raise RuntimeError("push: slot %d was last pushed with device-tensor counts, which the host does not mirror: go on with a tensor, or reset the slot" % b)
+            c = (0 if ended else (self.first_samples if n0 == 0 else self.chunk_samples)) if n_samples is None else int(n_samples[b])
+            if c < 0 or c > self.first_samples:
+                raise ValueError("push: n_samples[%d] = %d outside 0 .. %d" % (b, c, self.first_samples))
+            if ended:
+                if c > 0:
+                    raise RuntimeError("push: slot %d has ended (last) and was not reset: it takes no samples until reset=[%d] starts the next utterance" % (b, b))
+                frames.append(0)
+            elif lmask[b]:
+                if n0 + c <= self.n_fft // 2:
+                    raise ValueError("push: slot %d ends after %d samples: an utterance of at most n_fft / 2 = %d samples cannot be reflect-padded (refused offline as well)"
+                                     % (b, n0 + c, self.n_fft // 2))
+                frames.append((n0 + c) // (2 * self.hop) + 1 - self._ready(n0))
+            else:
+                frames.append(self._ready(n0 + c) - self._ready(n0))
+            counts.append(c)
+        return rmask, lmask, counts, frames
+
+    def _upload(self, rmask, lmask, counts, n_samples):
+        B = self.B
+        self._raise_flags(self.reset_flags, rmask)
+        self._raise_flags(self.last_flags, lmask)
+        if counts is None:
+            self.nsamp.copy_(n_samples.view(B), non_blocking=True)
+            self._ns_up = None
+            self._n, self._ended = [None] * B, [None] * B                 # a device tensor's contract is the caller's
+            return
+        if counts != self._ns_up:
+            self.nsamp.copy_(torch.tensor(counts, dtype=torch.int64), non_blocking=True)
+            self._ns_up = list(counts)
+        for b in range(B):
+            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
+            self._n[b], self._ended[b] = n0 + counts[b], ended or lmask[b]
+
+    def _static_input(self, dev):
+        B = self.B
+        return torch.zeros(B, self.first_samples, dtype=torch.float32, device=dev), ([True] * B, [False] * B, [self.first_samples] * B, None)
+
+    def _forget(self):
+        self._n, self._ended = [0] * self.B, [False] * self.B
+
+    def push(self, wave, n_samples=None, last=None, reset=None):
+        """wave [B, first_samples] fp32 -> (feat [B, Tc + 2, 180] fp32, out_len [B] int64 on the device): slot b takes the first n_samples[b] samples (a Python list
+        or an int64 device tensor [B]; default: the schedule's count, first_samples after a restart, chunk_samples later, 0 for an ended slot) and yields out_len[b]
+        frames; rows at or past out_len carry no information.  last: slots whose utterance ends with these samples; reset: slots to restart before them (each a list
+        of indices or a host bool mask [B]); the first push restarts every slot.  With host counts the contract is checked on the host, without a synchronisation:
+        counts within 0 .. first_samples, an utterance longer than n_fft / 2 = 256 samples at `last`, no samples to an ended slot.  With a device tensor it is the
+        caller's.  No host synchronisation after the first push; after capture() the results are static tensors that the next push overwrites."""
+        if wave.dim() != 2 or wave.shape[0] != self.B or wave.shape[1] != self.first_samples:
+            raise ValueError("push: wave %s for a session of %d slots x %d samples" % (tuple(wave.shape), self.B, self.first_samples))
+        rt.require_gpu(wave)
+        if self.enc.training:
+            raise RuntimeError("push: the encoder went back to training mode; call .eval()")
+        rmask, lmask, counts, _ = self._controls(n_samples, last, reset)
+        return self._push(wave, rmask, lmask, counts, n_samples)
+
+
+class AudioStreamSession:
+    """AudioEfficientConformerEncoder.stream(): waveform chunks -> logits.  The front session feeds back_end.stream() (a ConformerStreamSession, with its refusals) and
+    the head.  The front's schedule makes every push but an utterance's last yield exactly Tc frames, one chunk of the stack; a last push may yield Tc + 1: the stack
+    is then pushed a second time with that one frame for the slots concerned and 0 frames (no change of state) for the others, and its first output row is appended."""
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        self.enc = enc
+        self.front = AudioFrontStreamSession(enc, batch_size, chunk_frames)
+        self.back = enc.back_end.stream(batch_size, chunk_frames)
+        self.B, self.Tc, self.S = self.front.B, self.front.Tc, self.back.S
+        self.first_samples, self.chunk_samples = self.front.first_samples, self.front.chunk_samples
+        self._x2 = None
+
+    def _head(self, y):
+        return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
+
+    def push(self, wave, n_samples=None, last=None, reset=None):
+        """wave [B, first_samples] fp32 -> (logits [B, R, V] fp32, out_len [B] int64 on the device, inter: loss_prefix_i -> [logits chunk, lengths] as offline).
+        n_samples / last / reset: host lists as AudioFrontStreamSession.push; counts must follow the schedule (every push of a slot but its last yields exactly
+        chunk_frames frames; a slot may idle on 0 samples).  R = Tc / S, or Tc / S + 1 in a push where some slot's last chunk produced Tc + 1 frames."""
+        if torch.is_tensor(n_samples):
+            raise TypeError("push: the combined session takes host lists for n_samples (it decides on the host whether the stack needs a second push)")
+        B, Tc = self.B, self.Tc
+        rmask, lmask, counts, frames = self.front._controls(n_samples, last, reset)
+        for b in range(B):
+            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 1)):
+                raise ValueError("push: slot %d would yield %d frames from %d samples: off the schedule (first_samples = %d in an utterance's first push, chunk_samples = %d "
+                                 "later, fewer only with last)" % (b, frames[b], counts[b], self.first_samples, self.chunk_samples))
+        with torch.no_grad():
+            feat, _ = self.front.push(wave, counts, lmask, rmask)
+            tail = [f > Tc for f in frames]
+            y, ylen, inter = self.back.push(feat[:, :Tc], torch.tensor([min(f, Tc) for f in frames], dtype=torch.int64), rmask)
+            if not any(tail):
+                return self._head(y), ylen, inter
+            # (a captured stack's results are static: keep this push's before the second one refills them)
+            logits, ylen, inter = self._head(y).clone(), ylen.clone(), {k: [v[0].clone(), v[1].clone()] for k, v in inter.items()}
+            if self._x2 is None:
+                self._x2 = torch.zeros(B, Tc, feat.shape[2], dtype=feat.dtype, device=feat.device)
+            self._x2[:, 0].copy_(feat[:, Tc])
+            y2, ylen2, inter2 = self.back.push(self._x2, torch.tensor([1 if t else 0 for t in tail], dtype=torch.int64), None)
+            for k, v in inter.items():
+                inter[k] = [torch.cat([v[0], inter2[k][0][:, :1]], dim=1), v[1] + inter2[k][1]]
+            return torch.cat([logits, self._head(y2[:, :1].contiguous())], dim=1), ylen + ylen2, inter
+
+    def capture(self, device=None):
+        """capture both halves (AudioFrontStreamSession.capture, ConformerStreamSession.capture); call it before the first push"""
+        self.front.capture(device)
+        self.back.capture(device)
+        return self
+
+
+class CTCBeamStreamSession(_StreamSession):
+    """CTCBeamSearchDecoder.stream(): the beam search of avec_amd/csrc/ctc_beam.hip carried across logit chunks (one launch per push, the beam state stays on the
+    device).  The search is the offline one bit for bit: after any sequence of pushes the beams are those of beam_search on the frames pushed so far.  One launch
+    per push and nothing to replay: it is not capturable."""
+
+    def __init__(self, decoder, batch_size, max_frames):
+        super().__init__(batch_size)
+        self.dec, self.max_frames = decoder, int(max_frames)
+        if self.B < 1 or self.max_frames < 1:
+            raise ValueError("stream: batch_size %d, max_frames %d" % (self.B, self.max_frames))
+        self._frames = [0] * self.B                      # per slot, an upper bound of the frames it holds (Tc per push): the capacity check needs no sync
+        self._emitted = False                            # the state's outputs describe every frame pushed so far
+
+    def _allocate(self, dev):
+        self.state = ops.CTCBeamStreamState(self.B, self.dec.beam_size, self.max_frames, dev)
+        self.reset_flags = self.state.reset_flags
+
+    def _launch(self, chunk, chunk_len, reset, emit):
+        d = self.dec
+        out = ops.ctc_beam_stream(self.state, chunk, chunk_len, reset, d.ngram_tmp, d.lm(chunk.shape[-1]), d.ngram_alpha, d.ngram_beta, emit=emit)
+        self._emitted = emit
+        return out
+
+    def push(self, logits_chunk, chunk_len=None, reset=None, fetch=True):
+        """Consume logits_chunk [B, Tc, V]; slot b takes chunk_len[b] frames of it (int64 tensor; default: all Tc).  reset: slots to restart from the empty
+        transcript before this chunk, as a list of indices or a host bool mask [B] (a device mask costs a synchronisation); the first push resets every slot.
+        A push after which a slot could hold more than max_frames frames raises RuntimeError before anything is launched (each push counts as Tc frames for every
+        slot, whatever chunk_len says).
+        fetch=True returns one record per slot: {"partial_ids": the best hypothesis so far (the n-gram beam's; neural rescoring happens in finish()),
+        "stable_ids": its leading tokens that every live beam shares and no later frame can change}, and with a tokenizer "partial" and "stable", their text.
+        "stable" is decode(stable_ids): it is final token by token, not character by character (a later piece can still complete its last word).
+        fetch=False skips the traceback and copies nothing to the host."""
+        B, Tc, self._V = logits_chunk.shape
+        if B != self.B:
+            raise ValueError("push: chunk of %d utterances for a session of %d" % (B, self.B))
+        mask = self._reset_mask(reset)
+        frames = [(0 if mask is not None and mask[b] else n) + Tc for b, n in enumerate(self._frames)]
+        if max(frames) > self.max_frames:
+            raise RuntimeError("push: %d frames in a slot of a session with max_frames = %d" % (max(frames), self.max_frames))
+        self._ensure_state(logits_chunk.device)
+        self._first = False
+        self._frames = frames
+        out = self._launch(logits_chunk, chunk_len, self._raise_flags(self.reset_flags, mask), fetch)
+        if not fetch:
+            return None
+        tokens, out_len, _, _, stable_len = out
+        tok0, len0, st = tokens[:, 0].cpu(), out_len[:, 0].cpu().tolist(), stable_len.cpu().tolist()
+        tk = self.dec.tokenizer
+        recs = []
+        for b in range(B):
+            rec = {"partial_ids": tok0[b, :len0[b]].tolist(), "stable_ids": tok0[b, :st[b]].tolist()}
+            if tk is not None:
+                rec["partial"], rec["stable"] = tk.decode(rec["partial_ids"]), tk.decode(rec["stable_ids"])
+            recs.append(rec)
+        return recs
+
+    def finish(self):
+        """What decoder.beam_search returns for the frames pushed: per slot the winning token list (rescored by the neural LM when one is loaded)."""
+        if self.state is None:
+            raise RuntimeError("finish: nothing was pushed")
+        st = self.state
+        if not self._emitted:                            # one launch that consumes no frame and emits
+            self._launch(torch.zeros(self.B, 1, self._V, device=st.state.device), torch.zeros(self.B, dtype=torch.int64, device=st.state.device), None, True)
+        if self.dec.neural_rescorer is not None:
+            return self.dec._rescore(st.tokens, st.out_len, st.score, self.B, 1)
+        tok0, len0 = st.tokens[:, 0].cpu(), st.out_len[:, 0].cpu().tolist()
+        return [tok0[b, :len0[b]].tolist() for b in range(self.B)]

@@ -807,14 +807,30 @@ def _pos_group_backward(entry, wp):
     gemm_tn(dea, entry.pe, grp.wgrad, R, W, entry.D, p_colsum=grp.bgrad, side=True)
 
 
+def qkv_project(h, wb, M, D, fp8_ok=False):
+    """h [M, D] act -> Q | K | V [M, 3D] act.  wb = ((wq, wk, wv), (bq, bk, bv)).  One GEMM when the arena laid the three weights back to back, else three GEMMs
+    into column slices of the one buffer.  fp8_ok (the training forward only): the grouped product may take the weights' fp8 entry."""
+    (wq, wk, wv), bs = wb
+    qkv = empty((M, 3 * D), rt.act_dtype(), h)
+    grp = rt.fused_group(wq)          # (no test of the biases: ParamArena forms a group only when every bias exists)
+    if grp is not None and grp.weights[1] is wk and grp.weights[2] is wv:
+        ent = fp8.entry(wq, D) if fp8_ok else None
+        if ent is not None and ent.N == 3 * D:
+            gemm_nt_fp8(h, ent, qkv, M, 3 * D, D, bias=grp.bias)
+        else:
+            gemm_nt(h, grp.fwd, qkv, M, 3 * D, D, bias=grp.bias)
+    else:
+        for i, (w, b) in enumerate(zip((wq, wk, wv), bs)):
+            gemm_nt(h, rt.shadow(w).fwd, qkv[:, i * D:], M, D, D, bias=b, ldo=3 * D)
+    return qkv
+
+
 class AttentionModuleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, lens, mask, ln_w, ln_b, wq, bq, wk, bk, wv, bv, wo, bo, wp, bp, H, patch, eps, drop_p, sid, residual):
         rt.require_gpu(x)
         B, T, D = x.shape
         M, d, adt = B * T, D // H, rt.act_dtype()
-        grp = rt.fused_group(wq)
-        grp_ok = grp is not None and grp.weights[1] is wk and grp.weights[2] is wv and bq is not None
         x2 = _f32c(x.reshape(-1, D))
         if ln_w is not None:
             h, mean, rstd = layernorm_fwd(x2, ln_w, ln_b, M, D, False, eps)
@@ -832,18 +848,7 @@ class AttentionModuleFn(torch.autograd.Function):
         if mask is not None:      # dense (B or 1,1,T,T) float mask as the reference API; patch variant min-pools it on the host side
             mask = mask.reshape(mask.shape[0], T, T) if patch == 1 else _pool_mask(mask, T, patch)
             mask = mask.float().contiguous()
-        if grp_ok:
-            qkv = empty((Mp, 3 * D), adt, x2)
-            ent = fp8.entry(wq, D)
-            if ent is not None and ent.N == 3 * D:
-                gemm_nt_fp8(hp, ent, qkv, Mp, 3 * D, D, bias=grp.bias)
-            else:
-                gemm_nt(hp, grp.fwd, qkv, Mp, 3 * D, D, bias=grp.bias)               # Q|K|V in one launch
-        else:
-            qkv = empty((Mp, 3 * D), adt, x2)
-            for i, (w, b) in enumerate(((wq, bq), (wk, bk), (wv, bv))):
-                sh = rt.shadow(w)
-                gemm_nt(hp, sh.fwd, qkv[:, i * D:], Mp, D, D, bias=b, ldo=3 * D)
+        qkv = qkv_project(hp, ((wq, wk, wv), (bq, bk, bv)), Mp, D, fp8_ok=True)
         pg, pgi = _pos_group_entry(wp, Tp, D, x.device)
         if pg is not None:
             pe, e = pg.pe, pg.e_all[:, pgi * D:(pgi + 1) * D]          # this block's slice of the stack's position projections (one launch per stage and pass)
@@ -1942,6 +1947,16 @@ def ctc_beam_search(logits, lengths, beam, tmp=1.0, lm=None, alpha=0.6, beta=1.0
     return tokens, out_len, score, ctc_logp
 
 
+def _slot_vec(op, name, t, B, dev, mask=False, convert=False):
+    """A per-slot control vector of a streaming op: None, or a contiguous tensor [B] on the GPU `dev`, int64 counts or (mask) a uint8 / bool mask.  Returns it;
+    anything else raises, unless `convert` (ctc_beam_stream's chunk_len) asks for the counts to be brought into that form."""
+    if t is None or (t.is_cuda and t.device == dev and t.is_contiguous() and t.numel() == B and (t.dtype in (torch.uint8, torch.bool) if mask else t.dtype == torch.int64)):
+        return t
+    if convert:
+        return t.to(device=dev, dtype=torch.int64).contiguous().view(B)
+    raise ValueError("%s: %s must be a contiguous %s [%d] on the device" % (op, name, "uint8 / bool mask" if mask else "int64 tensor", B))
+
+
 class CTCBeamStreamState:
     """Everything a streaming beam search keeps between pushes (ops.ctc_beam_stream), allocated once: the beam state and backpointer rows of avec_ctc_beam_stream,
     the outputs it writes when it emits, and a reset flag buffer.  batch utterance slots, `beam` beams, at most max_frames frames per utterance.  A zero-filled
@@ -1976,10 +1991,8 @@ def ctc_beam_stream(st, logits, chunk_len=None, reset=None, tmp=1.0, lm=None, al
     dev = st.state.device
     if lg.device != dev:
         raise ValueError("ctc_beam_stream: chunk on %s, state on %s" % (lg.device, dev))
-    if chunk_len is not None and not (chunk_len.dtype == torch.int64 and chunk_len.device == dev and chunk_len.is_contiguous() and chunk_len.numel() == B):
-        chunk_len = chunk_len.to(device=dev, dtype=torch.int64).contiguous().view(B)
-    if reset is not None and not (reset.device == dev and reset.is_contiguous() and reset.numel() == B and reset.dtype in (torch.uint8, torch.bool)):
-        raise ValueError("ctc_beam_stream: reset must be a contiguous uint8 / bool mask [B] on the state's device")
+    chunk_len = _slot_vec("ctc_beam_stream", "chunk_len", chunk_len, B, dev, convert=True)
+    _slot_vec("ctc_beam_stream", "reset", reset, B, dev, mask=True)
     use_lm = lm is not None and lm.usable
     lm_arg = _byref(lm.device_struct(dev)) if use_lm else None
     oov = lm.oov_logprob if use_lm else 0.0
@@ -2159,15 +2172,8 @@ def lm_attention_module(x2, N, L, ln, att, lens=None):
     projection with the residual in its epilogue"""
     M, D = x2.shape
     h, _, _ = layernorm_fwd(x2, ln.weight, ln.bias, M, D, False, ln.eps)
-    qkv = empty((M, 3 * D), rt.act_dtype(), x2)
-    ws = (att.query_layer.weight, att.key_layer.weight, att.value_layer.weight)
-    bs = (att.query_layer.bias, att.key_layer.bias, att.value_layer.bias)
-    grp = rt.fused_group(ws[0])
-    if grp is not None and grp.weights[1] is ws[1] and grp.weights[2] is ws[2]:
-        gemm_nt(h, grp.fwd, qkv, M, 3 * D, D, bias=grp.bias)
-    else:
-        for i in range(3):
-            gemm_nt(h, rt.shadow(ws[i]).fwd, qkv[:, i * D:], M, D, D, bias=bs[i], ldo=3 * D)
+    q, k, v = att.query_layer, att.key_layer, att.value_layer
+    qkv = qkv_project(h, ((q.weight, k.weight, v.weight), (q.bias, k.bias, v.bias)), M, D)
     o = causal_attention(qkv, N, att.num_heads, L, lens)
     return linear_fwd(o, att.output_layer.weight, att.output_layer.bias, M, in_f32=False, out_f32=True, res=x2, alpha=1.0)
 
@@ -2204,12 +2210,9 @@ def lm_rescore(model, ids, lens, beam_score, alpha, beta, B):
 # Streaming encoder (nnet.ConformerStreamSession): the two stateful kernels of a causal Conformer stack run chunk by chunk (include/avec_hip.h)
 # ============================================================================================
 def _stream_ctl(name, pos, reset, chunk_len, B):
-    if not (pos.dtype == torch.int64 and pos.is_cuda and pos.is_contiguous() and pos.numel() == B):
-        raise ValueError("%s: pos must be a contiguous int64 tensor [%d] on the device" % (name, B))
-    if reset is not None and not (reset.device == pos.device and reset.is_contiguous() and reset.numel() == B and reset.dtype in (torch.uint8, torch.bool)):
-        raise ValueError("%s: reset must be a contiguous uint8 / bool mask [%d] on the device" % (name, B))
-    if chunk_len is not None and not (chunk_len.dtype == torch.int64 and chunk_len.device == pos.device and chunk_len.is_contiguous() and chunk_len.numel() == B):
-        raise ValueError("%s: chunk_len must be a contiguous int64 tensor [%d] on the device" % (name, B))
+    _slot_vec(name, "pos", pos, B, pos.device)
+    _slot_vec(name, "reset", reset, B, pos.device, mask=True)
+    _slot_vec(name, "chunk_len", chunk_len, B, pos.device)
 
 
 def glu_dwconv_stream_state(B, C, K, device):
@@ -2280,11 +2283,9 @@ def _audio_stream_ctl(name, wave, state, n_samples, reset, last):
     B = wave.shape[0]
     if not (wave.dim() == 2 and wave.dtype == torch.float32 and wave.stride(1) == 1 and state.dtype == torch.uint8 and state.is_contiguous() and state.device == wave.device):
         raise ValueError("%s: wave fp32 [B, W] with unit sample stride and a uint8 state blob on its device (got %s %s, %s)" % (name, tuple(wave.shape), wave.dtype, state.dtype))
-    if n_samples is not None and not (n_samples.dtype == torch.int64 and n_samples.device == wave.device and n_samples.is_contiguous() and n_samples.numel() == B):
-        raise ValueError("%s: n_samples must be a contiguous int64 tensor [%d] on the device" % (name, B))
-    for what, f in (("reset", reset), ("last", last)):
-        if f is not None and not (f.device == wave.device and f.is_contiguous() and f.numel() == B and f.dtype in (torch.uint8, torch.bool)):
-            raise ValueError("%s: %s must be a contiguous uint8 / bool mask [%d] on the device" % (name, what, B))
+    _slot_vec(name, "n_samples", n_samples, B, wave.device)
+    _slot_vec(name, "reset", reset, B, wave.device, mask=True)
+    _slot_vec(name, "last", last, B, wave.device, mask=True)
 
 
 def mel_frames_stream(wave, window, state, n_samples=None, reset=None, last=None, *, Tmax, n_fft, win, hop, out=None):

@@ -146,3 +146,29 @@ def test_session_refusals_name_their_cause():
         ses._controls(None, [0])
     assert ses._controls([4, 2, 4], [1]) == ([False, True, False], [4, 2, 4])
     assert ses._controls([4, 0, 4], None) == (None, [4, 0, 4])         # a slot that has ended may idle on chunks of 0 frames
+
+
+def test_slot_mask():
+    """reset / last in every accepted form -> the one bool list [B]"""
+    from avec_amd.nnet.streaming import slot_mask
+    assert slot_mask(None, 3) == [False, False, False]
+    assert slot_mask([1], 3) == slot_mask([False, True, False], 3) == [False, True, False]
+    t = torch.tensor([True, False, True])
+    assert slot_mask(t, 3) == t.tolist() == [True, False, True]
+    assert slot_mask(torch.tensor([2]), 3) == [False, False, True]
+    assert slot_mask([0, 1, 2], 3) == [True, True, True]               # B ints are indices, not a mask
+    assert slot_mask([], 3) == [False, False, False]
+
+
+def test_stream_sinusoid_table_is_the_offline_tables_rows():
+    """the session's E input, delta = 0 .. L: the first L + 1 rows of ops.rel_pos_table(L + 1, D) flipped equal the table written out position by position"""
+    from avec_amd import ops
+    from avec_amd import runtime as rt
+    L, D = 6, 32
+    pos = torch.arange(0, L + 1, dtype=torch.float32).unsqueeze(1)
+    inv = 10000 ** (2 * torch.arange(0, D // 2, dtype=torch.float32).unsqueeze(0) / D)
+    pe = torch.zeros(L + 1, D)
+    pe[:, 0::2], pe[:, 1::2] = (pos / inv).sin(), (pos / inv).cos()
+    pe = pe.to(rt.act_dtype())
+    got = ops.rel_pos_table(L + 1, D, "cpu")[:L + 1].flip(0)
+    assert got.dtype == pe.dtype and torch.equal(got, pe)
