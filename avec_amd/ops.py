@@ -32,12 +32,17 @@ class KernelTimer:
         self.enabled, self.records = enabled, []
 
     def start(self):
+        """the event in front of a launch; None while disabled, which stop() ignores: launch sites bracket unconditionally"""
+        if not self.enabled:
+            return None
         e = torch.cuda.Event(enable_timing=True)
         e.record()
         return e
 
     def stop(self, e0, key, flops, abytes=0.0):
         """abytes: ALGORITHMIC bytes of the launch (operands once + results once), next to the PMC traffic in the roofline rows"""
+        if e0 is None:
+            return
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()
         name = lib.raw("avec_last_kernel")()                  # the kernel instance the entry point chose (api.hip)
@@ -96,6 +101,11 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _rng(device, drop_p=1.0):
+    """the RNG state pointer for a launch that drops with probability drop_p; None when it draws nothing (launches that always draw leave drop_p out)"""
+    return rt.rng_state(device).data_ptr() if drop_p > 0 else None
+
+
 # ---- step stamps (measurement aid, AVEC_STAMPS=1): wall-clock marks written by one-wave kernels at named points of the forward and backward passes, on whatever stream the
 # point runs on -- they replay with the captured graph, so tools/step_stamps.py sees the real overlap of the two branch streams without a profiler ----
 STAMPS = {"on": os.environ.get("AVEC_STAMPS", "0") == "1", "buf": None, "names": []}
@@ -146,10 +156,6 @@ def empty(shape, dtype, ref):
     return torch.empty(shape, dtype=dtype, device=ref.device)
 
 
-TN_MULTI = True                     # attention backward: dK, dV and dE as one launch (0: three)
-ATTN_ODD_VALU = False             # A/B: odd head widths take the VALU column pass of the attention backward (round 2)
-
-
 def _chunk_readable(t, ld, width, rows):
     """rows of `width` 16-bit elements at stride `ld`: may the kernels read whole 8-element chunks behind the last row?"""
     if width % 8 == 0 and ld % 8 == 0 and t.data_ptr() % 16 == 0:
@@ -184,13 +190,12 @@ def gemm_nt_fp8(A, ent, out, M, N, K, *, bias=None, act=ACT_NONE, out_pre=None, 
         ep.out_pre, ep.ldpre = out_pre.data_ptr(), N
     ep.bias, ep.act, ep.alpha = _p(bias), act, alpha
     if drop_p > 0.0:
-        ep.drop_p, ep.rng, ep.rng_stream = drop_p, rt.rng_state(out.device).data_ptr(), sid
+        ep.drop_p, ep.rng, ep.rng_stream = drop_p, _rng(out.device, drop_p), sid
     if res is not None:
         ep.res, ep.ldres, ep.res_act = res.data_ptr(), N, 0
-    ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
+    ev = KERNEL_TIMER.start()
     lib.gemm_nt_fp8(q.data_ptr(), Kp, ent.wq, Kp, M, N, Kp, ent.a_amax, ent.w_amax, _byref(ep), rt.stream())
-    if ev is not None:
-        KERNEL_TIMER.stop(ev, (0, 0), 2.0 * M * N * K)
+    KERNEL_TIMER.stop(ev, (0, 0), 2.0 * M * N * K)
     return out
 
 
@@ -204,7 +209,7 @@ def gemm_nt(A, W, out, M, N, K, *, rows=None, mode=ROWS_PLAIN, a_f32=False, ldw=
     ep.bias = _p(bias)
     ep.act = act
     if drop_p > 0.0:
-        ep.drop_p, ep.rng, ep.rng_stream = drop_p, rt.rng_state(out.device).data_ptr(), sid
+        ep.drop_p, ep.rng, ep.rng_stream = drop_p, _rng(out.device, drop_p), sid
     if res is not None:
         ep.res, ep.ldres, ep.res_act, ep.res_cls0 = res.data_ptr(), (N if ldres is None else ldres), int(res_act), int(res_cls0)
         if res_mask is not None:
@@ -221,18 +226,19 @@ def gemm_nt(A, W, out, M, N, K, *, rows=None, mode=ROWS_PLAIN, a_f32=False, ldw=
             ep.bnb_ss, ep.bnb_mask = bnb.ss.data_ptr(), 1
     if rows is None:
         rows = rows_plain(K)
-    ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
+    ev = KERNEL_TIMER.start()
     lib.gemm_nt(rt.dt() if dtype is None else dtype, A.data_ptr(), _byref(rows), mode, int(a_f32), W.data_ptr(),
                 K if ldw is None else ldw, M, N, K, _byref(ep), rt.stream())
-    if ev is not None:
-        esz = A.element_size()
-        KERNEL_TIMER.stop(ev, (0, mode), 2.0 * M * N * K if flops is None else flops,
-                          ((M * K + N * K) * esz + M * N * (4 if out_f32 else esz)) if abytes is None else abytes)
+    esz = A.element_size()
+    KERNEL_TIMER.stop(ev, (0, mode), 2.0 * M * N * K if flops is None else flops,
+                      ((M * K + N * K) * esz + M * N * (4 if out_f32 else esz)) if abytes is None else abytes)
     return out
 
 
-# (The module-level switches of this file -- TN_MULTI, LN_PAIR, RELU_BITMASK, CONVMOD_BN_FUSE, STEM3P, ... -- are plain constants: the alternatives they select
-# are kept for the parity tests that flip them in-process (tests/test_gpu_round3.py, test_gpu_round4.py, test_gpu_parity.py), not as environment switches.)
+# (The module-level switches of this file are plain constants, not environment switches (DEFER_WGRAD alone also reads AVEC_DEFER_WGRAD); each alternative is kept for
+# the test or tool that flips it in-process: DEFER_WGRAD tests/test_gpu_backward_state.py; LN_PAIR tests/test_gpu_round4.py; RELU_BITMASK, SHORTCUT_SUBGRID,
+# GROUP_WGRAD128, BNB_FUSE tests/test_gpu_round3.py; CONVMOD_BN_FUSE tests/test_gpu_convmod_bn.py; STEM3D_DIRECT, STEM3P, STEM3P_FUSED_WGRAD tests/test_gpu_parity.py
+# and tools/bench_stem.py.)
 # ---- deferred parameter gradients ------------------------------------------------------------------------------------------------------------
 # Weight gradients (dW = dY^T X), bias gradients and LayerNorm gamma/beta gradients only feed the optimizer: nothing in the backward chain waits for
 # them.  Launched one by one they are ~45 % of a conformer block's backward launches, each latency-bound (a few hundred workgroups, 12-21 us).  Inside a
@@ -289,11 +295,11 @@ class _PendingGrads:
             k, items = _QUEUE_KINDS[kind], self.items[kind]
             if not items:
                 continue
-            ev = KERNEL_TIMER.start() if (k.timer_key is not None and KERNEL_TIMER.enabled) else None
+            ev = KERNEL_TIMER.start() if k.timer_key is not None else None
             for i in range(0, len(items), k.group_max):
                 chunk = items[i:i + k.group_max]
                 getattr(lib, k.launcher)(*(() if k.dtype is None else (k.dtype(),)), (k.item * len(chunk))(*chunk), len(chunk), rt.stream())
-            if ev is not None:
+            if ev is not None:          # (the byte count walks the items: only while timing)
                 KERNEL_TIMER.stop(ev, k.timer_key, self.flops[kind], sum(k.abytes(it) for it in items))
             self.items[kind], self.flops[kind] = [], 0.0
         if not any(self.items.values()):
@@ -387,15 +393,14 @@ def gemm_tn(P, Q, O, M, I, J, *, ldp=None, q_rows=None, q_mode=ROWS_PLAIN, q_f32
         if lib.raw("avec_gemm_tn_grouped_ok")(BF16, _byref(it)) and _chunk_readable(P, it.ldp, I, M) and _chunk_readable(Q, it.ldq, J, M):
             _pass().pending().push("tn", it, [P, Q], 2.0 * M * I * J)
             return
-    ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
+    ev = KERNEL_TIMER.start()
     st = rt.stream()
     if side and not KERNEL_TIMER.enabled:
         sd = rt.wgrad_fork(P, Q)
         st = st if sd is None else sd.cuda_stream
     lib.gemm_tn_bias(rt.dt() if dtype is None else dtype, P.data_ptr(), I if ldp is None else ldp, Q.data_ptr(), _byref(q_rows), q_mode,
                      int(q_f32), O.data_ptr(), J if ldo is None else ldo, _p(p_colsum), M, I, J, st)
-    if ev is not None:
-        KERNEL_TIMER.stop(ev, (1, q_mode), 2.0 * M * I * J, (M * I + M * J) * 2.0 + I * J * 4.0)
+    KERNEL_TIMER.stop(ev, (1, q_mode), 2.0 * M * I * J, (M * I + M * J) * 2.0 + I * J * 4.0)
 
 
 def layernorm_fwd(x, w, b, M, D, out_f32, eps):
@@ -438,9 +443,8 @@ def layernorm_bwd(dy, dy_f32, x, mean, rstd, w, b, M, D, dres=None, prep=None):
         if prep is not None:
             pt = empty((M, D), rt.act_dtype(), x)
             alpha, drop_p, sid = prep
-            rng = rt.rng_state(x.device).data_ptr() if drop_p > 0 else None
             lib.layernorm_bwd_prep(rt.dt(), dy.data_ptr(), int(dy_f32), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), dx.data_ptr(), _p(dres),
-                                   pt.data_ptr(), alpha, drop_p, rng, sid, M, D, rt.stream())
+                                   pt.data_ptr(), alpha, drop_p, _rng(x.device, drop_p), sid, M, D, rt.stream())
             _pass().prep[dx.data_ptr()] = (pt, M, D, alpha, drop_p, sid)
         else:
             lib.layernorm_bwd(rt.dt(), dy.data_ptr(), int(dy_f32), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), dx.data_ptr(), _p(dres),
@@ -461,9 +465,9 @@ def layernorm_bwd_pair(dy2, x2, mean2, rstd2, w2, b2, dres2, x1, mean1, rstd1, w
         pt = empty((M, D), rt.act_dtype(), x2)
         alpha, drop_p, sid = req1
         _pass().prep[dx1.data_ptr()] = (pt, M, D, alpha, drop_p, sid)
-    rng = rt.rng_state(x2.device).data_ptr() if (pt is not None and drop_p > 0) else None
     lib.layernorm_bwd2(rt.dt(), dy2.data_ptr(), x2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr(), w2.data_ptr(), dres2.data_ptr(), dx2.data_ptr(),
-                       x1.data_ptr(), mean1.data_ptr(), rstd1.data_ptr(), w1.data_ptr(), dx1.data_ptr(), _p(pt), alpha, drop_p, rng, sid, M, D, rt.stream())
+                       x1.data_ptr(), mean1.data_ptr(), rstd1.data_ptr(), w1.data_ptr(), dx1.data_ptr(), _p(pt), alpha, drop_p, _rng(x2.device, drop_p), sid, M, D,
+                       rt.stream())         # (drop_p is 0 without a request)
     _pass().ln2[dx2.data_ptr()] = (dx1, ctx1, dx2, dx2._version)
     defer_ln_param_grads(dy2, False, x2, mean2, rstd2, w2, b2, M, D)
     return dx2
@@ -471,8 +475,7 @@ def layernorm_bwd_pair(dy2, x2, mean2, rstd2, w2, b2, dres2, x1, mean1, rstd1, w
 
 def grad_prep(dout, M, N, alpha=1.0, drop_p=0.0, sid=0, dbias=None):
     dacc = empty((M, N), rt.act_dtype(), dout)
-    rng = rt.rng_state(dout.device).data_ptr() if drop_p > 0 else None
-    lib.grad_prep(rt.dt(), dout.data_ptr(), N, dacc.data_ptr(), alpha, drop_p, rng, sid, _p(dbias), M, N, rt.stream())
+    lib.grad_prep(rt.dt(), dout.data_ptr(), N, dacc.data_ptr(), alpha, drop_p, _rng(dout.device, drop_p), sid, _p(dbias), M, N, rt.stream())
     return dacc
 
 
@@ -634,7 +637,7 @@ class DropoutFn(torch.autograd.Function):
     def forward(ctx, x, p, sid):
         x = _f32c(x)
         y = torch.empty_like(x)
-        lib.dropout_f32(x.data_ptr(), y.data_ptr(), p, rt.rng_state(x.device).data_ptr(), sid, x.numel(), rt.stream())
+        lib.dropout_f32(x.data_ptr(), y.data_ptr(), p, _rng(x.device), sid, x.numel(), rt.stream())
         ctx.saved = (p, sid)
         return y
 
@@ -643,7 +646,7 @@ class DropoutFn(torch.autograd.Function):
         p, sid = ctx.saved
         dy = _f32c(dy)
         dx = torch.empty_like(dy)
-        lib.dropout_f32(dy.data_ptr(), dx.data_ptr(), p, rt.rng_state(dy.device).data_ptr(), sid, dy.numel(), rt.stream())
+        lib.dropout_f32(dy.data_ptr(), dx.data_ptr(), p, _rng(dy.device), sid, dy.numel(), rt.stream())
         return dx, None, None
 
 
@@ -727,18 +730,69 @@ def rel_pos_table(T, D, device):
     return _PE_CACHE[key]
 
 
-def _attn_args(qkv, e, lens, len_div, mask, o, lse, B, H, T, d, D, q_full=0):
+def _attn_args(qkv, e, lens, len_div, mask, o, lse, B, H, T, d, D, q_full=0, *, kv=None, Tk=0, scale=None):
+    """the forward fields of an Attn.  qkv: packed [B*T][3D] = q | k | v; or, with kv = (k, v, row stride) -- the key/value-cache form, Tk keys per sequence --, q
+    alone at the same row stride.  scale: 1 / sqrt(d) unless given."""
     a = Attn()
     a.q_full = q_full
-    esz = qkv.element_size()
-    a.q, a.k, a.v, a.ld = qkv.data_ptr(), qkv.data_ptr() + D * esz, qkv.data_ptr() + 2 * D * esz, 3 * D
+    if kv is None:
+        esz = qkv.element_size()
+        a.q, a.k, a.v, a.ld = qkv.data_ptr(), qkv.data_ptr() + D * esz, qkv.data_ptr() + 2 * D * esz, 3 * D
+    else:
+        a.q, a.k, a.v, a.ld = qkv.data_ptr(), kv[0].data_ptr(), kv[1].data_ptr(), kv[2]
     a.e, a.lde = e.data_ptr(), (e.stride(0) if e.dim() == 2 else D)      # (a column slice of a stack's fused position projections: row stride L * D)
     a.lens, a.len_div = _p(lens), len_div
     if mask is not None:
-        a.mask, a.mask_bstride = mask.data_ptr(), (T * T if mask.shape[0] > 1 else 0)
+        a.mask, a.mask_bstride = mask.data_ptr(), (T * (Tk or T) if mask.shape[0] > 1 else 0)
     a.o, a.ldo, a.lse = o.data_ptr(), D, lse.data_ptr()
-    a.B, a.H, a.T, a.d, a.scale = B, H, T, d, 1.0 / d ** 0.5
+    a.B, a.H, a.T, a.d, a.scale, a.Tk = B, H, T, d, (1.0 / d ** 0.5 if scale is None else scale), Tk
     return a
+
+
+def _pad8(n):
+    return (n + 7) // 8 * 8
+
+
+def _attn_backward(a, do, dq, dsrel, de=None, products=False, one_launch=False):
+    """avec_relpos_attention_bwd on the forward Attn `a` (of _attn_args), then -- products -- dK = dS^T Q and dV = P^T dO per (batch, head) and dE_h = sum_b skew(dS)^T Q
+    as batched TN MFMA GEMMs with fp32 accumulation: one_launch puts the three into one (avec_gemm_tn_batched_multi), else two stores and one accumulation.
+    The buffers are the caller's: do [B*T][D] act; dq the dQ rows (with products: the first third of a packed [B*T][3D] dQ | dK | dV, row stride dq.stride(0)); de fp32
+    [2T-1][D] rows, zeroed or holding a sum to add to; dsrel [H][B*T][_pad8(T + Tk - 1)] act, zeroed.  Returns the (P, dS) scratch [2][B*H][T][_pad8(Tk)].
+    `do` NEEDS 16 READABLE BYTES BEHIND ITS LAST ROW when d is no multiple of 8 (d = 45, 90): dV reads dO per head in whole 16-byte chunks (gemm_tn_batched: J = d
+    rounded up to the vector width), so the last head's last chunk ends up to 12 bytes behind the row -- in the last row, behind the tensor."""
+    B, H, T, d = a.B, a.H, a.T, a.d
+    D, esz = H * d, do.element_size()
+    a.dout = do.data_ptr()
+    a.dq, a.lddq = dq.data_ptr(), dq.stride(0)
+    if products:
+        a.dk, a.dv, a.ldd = a.dq + D * esz, a.dq + 2 * D * esz, a.lddq
+        a.de, a.ldde = de.data_ptr(), de.stride(0)
+    Tld = _pad8(a.Tk or T)
+    scratch = empty((2, B * H, T, Tld), do.dtype, do)                # P and dS of every (batch, head), row stride padded to 8
+    a.pbuf, a.dsbuf, a.ldt = scratch.data_ptr(), scratch.data_ptr() + scratch[0].numel() * esz, Tld
+    a.dsrel, a.ldr = dsrel.data_ptr(), dsrel.shape[2]
+    lib.relpos_attention_bwd(rt.dt(), _byref(a), rt.stream())
+    if not products:
+        return scratch
+    # dK and dV: one workgroup per (batch, head, tile) reduces over all T rows and stores straight into the K / V thirds of the packed gradient (no zero-filled
+    # fp32 staging, no atomics, no cast pass); dE sums over the batch, so it keeps the accumulate form
+    L6 = ctypes.c_longlong * 6
+    sK, sV, sE = L6(H * T * Tld, T * Tld, T * a.ld, d, T * a.ldd, d), L6(H * T * Tld, T * Tld, T * D, d, T * a.ldd, d), L6(0, B * T * a.ldr, 0, d, 0, d)
+    # (P, ldp, Q, ldq, O, ldo, M, I, J, outer batch, inner batch, strides)
+    pK = (a.dsbuf, Tld, a.q, a.ld, a.dk, a.ldd, T, T, d, B, H, sK)
+    pV = (a.pbuf, Tld, a.dout, D, a.dv, a.ldd, T, T, d, B, H, sV)
+    pE = (a.dsrel, a.ldr, a.q, a.ld, a.de, a.ldde, B * T, 2 * T - 1, d, 1, H, sE)
+    if one_launch:
+        it = (TnBatched * 3)()
+        for t, p, out in zip(it, (pK, pV, pE), ("O_act", "O_act", "O")):
+            t.P, t.ldp, t.Q, t.ldq, _, t.ldo, t.M, t.I, t.J, t.nb_outer, t.nb_inner, t.strides6 = p
+            setattr(t, out, p[4])
+        lib.gemm_tn_batched_multi(rt.dt(), it, 3, rt.stream())
+    else:
+        lib.gemm_tn_batched_store(rt.dt(), *pK, rt.stream())
+        lib.gemm_tn_batched_store(rt.dt(), *pV, rt.stream())
+        lib.gemm_tn_batched(rt.dt(), *pE, rt.stream())
+    return scratch
 
 
 # ---- position projections of a whole stack in one launch ---------------------------------------------------------------------------------------------------
@@ -865,8 +919,7 @@ class AttentionModuleFn(torch.autograd.Function):
             oo = linear_fwd(o, wo, bo, Mp, in_f32=False, out_f32=False)
             base = x2 if residual else torch.zeros_like(x2)
             y = empty((M, D), torch.float32, x2)
-            rng = rt.rng_state(x.device).data_ptr() if drop_p > 0 else None
-            lib.patch_unpool_add(rt.dt(), oo.data_ptr(), base.data_ptr(), y.data_ptr(), drop_p, rng, sid, B, T, D, patch, rt.stream())
+            lib.patch_unpool_add(rt.dt(), oo.data_ptr(), base.data_ptr(), y.data_ptr(), drop_p, _rng(x.device, drop_p), sid, B, T, D, patch, rt.stream())
         else:
             y = linear_fwd(o, wo, bo, M, in_f32=False, out_f32=True, drop_p=drop_p, sid=sid, res=res, alpha=1.0)
         ctx.saved = (x2, mean, rstd, h, hp, qkv, pe, e, o, lse, lens, mask, ln_w, ln_b, wq, bq, wk, bk, wv, bv, wo, bo, wp, bp,
@@ -883,16 +936,13 @@ class AttentionModuleFn(torch.autograd.Function):
         dy = _f32c(dy.reshape(M, D))
         if patch > 1:
             doo = empty((Mp, D), adt, dy)
-            rng = rt.rng_state(dy.device).data_ptr() if drop_p > 0 else None
-            lib.patch_unpool_bwd(rt.dt(), dy.data_ptr(), doo.data_ptr(), drop_p, rng, sid, B, T, D, patch, rt.stream())
+            lib.patch_unpool_bwd(rt.dt(), dy.data_ptr(), doo.data_ptr(), drop_p, _rng(dy.device, drop_p), sid, B, T, D, patch, rt.stream())
         else:
             doo = _take_prep(dy, M, D, 1.0, drop_p, sid)
             if doo is None:
                 doo = grad_prep(dy, M, D, drop_p=drop_p, sid=sid)
         linear_bwd_weight(doo, o, wo, Mp, bias=bo)
-        # dV = P^T dO reads dO per head in whole 16-byte chunks (gemm_tn_batched: J = d rounded up to the vector width): for head widths that are not a multiple of it
-        # (d = 45, 90) the last head's last chunk ends up to 12 bytes behind the row -- behind the TENSOR in its last row: 16 readable bytes follow it
-        do = torch.empty(Mp * D + 8, dtype=adt, device=dy.device)[:Mp * D].view(Mp, D)
+        do = torch.empty(Mp * D + 8, dtype=adt, device=dy.device)[:Mp * D].view(Mp, D)          # 16 readable bytes behind the last row (see _attn_backward)
         do = linear_bwd_input(doo, wo, Mp, out_f32=False, out=do)
         dqkv = empty((Mp, 3 * D), adt, dy)
         pg, pgi = ctx.pos_group
@@ -904,42 +954,12 @@ class AttentionModuleFn(torch.autograd.Function):
         else:
             de = rt.zeros_scratch((2 * Tp - 1) * D, dy.device).view(2 * Tp - 1, D)      # pre-zeroed pool: no fill launch per layer (-0.15 ms per step)
         a = _attn_args(qkv, e, lens, patch, mask, o, lse, B, H, Tp, d, D, T // patch if (patch > 1 and mask is None) else 0)
-        a.dout = do.data_ptr()
-        esz = dqkv.element_size()
-        a.dq, a.lddq = dqkv.data_ptr(), 3 * D
-        a.dk, a.dv, a.ldd = dqkv.data_ptr() + D * esz, dqkv.data_ptr() + 2 * D * esz, 3 * D
-        a.de, a.ldde = de.data_ptr(), de.stride(0)
-        Tld, Rld = (Tp + 7) // 8 * 8, (2 * Tp - 1 + 7) // 8 * 8
-        scratch = empty((2, B * H, Tp, Tld), adt, dy)                # P and dS of every (batch, head), row stride padded to 8
-        a.pbuf, a.dsbuf, a.ldt = scratch.data_ptr(), scratch.data_ptr() + scratch[0].numel() * esz, Tld
-        use_mfma = d % 2 == 0 or not ATTN_ODD_VALU                   # odd head widths (d = 45): the batched products read their Q operand from odd element offsets (unaligned dword loads)
-        if use_mfma:
-            n_rel = H * B * Tp * Rld                         # zero-initialised, from the step's pre-zeroed pool (was a fill launch per layer on the dependent chain)
-            if adt == torch.bfloat16:
-                dsrel = rt.zeros_scratch((n_rel + 1) // 2, dy.device).view(torch.bfloat16)[:n_rel].view(H, B * Tp, Rld)
-            else:
-                dsrel = rt.zeros_scratch(n_rel, dy.device).view(H, B * Tp, Rld)
-            a.dsrel, a.ldr = dsrel.data_ptr(), Rld
-        lib.relpos_attention_bwd(rt.dt(), _byref(a), rt.stream())
-        if use_mfma:
-            # dK = dS^T Q and dV = P^T dO per (batch, head); dE_h = sum_b skew(dS)^T Q : batched TN MFMA GEMMs, fp32 accumulation
-            # dK and dV: one workgroup per (batch, head, tile) reduces over all Tp rows and stores straight into the K / V thirds of dqkv (no zero-filled
-            # fp32 staging, no atomics, no cast pass); dE sums over the batch, so it keeps the accumulate form
-            L6 = ctypes.c_longlong * 6
-            sK, sV, sE = L6(H * Tp * Tld, Tp * Tld, Tp * 3 * D, d, Tp * 3 * D, d), L6(H * Tp * Tld, Tp * Tld, Tp * D, d, Tp * 3 * D, d), L6(0, B * Tp * Rld, 0, d, 0, d)
-            if TN_MULTI:          # the three products as ONE launch (avec_gemm_tn_batched_multi)
-                it = (TnBatched * 3)()
-                it[0].P, it[0].ldp, it[0].Q, it[0].ldq, it[0].O_act, it[0].ldo = a.dsbuf, Tld, qkv.data_ptr(), 3 * D, dqkv.data_ptr() + D * esz, 3 * D
-                it[0].M, it[0].I, it[0].J, it[0].nb_outer, it[0].nb_inner, it[0].strides6 = Tp, Tp, d, B, H, sK
-                it[1].P, it[1].ldp, it[1].Q, it[1].ldq, it[1].O_act, it[1].ldo = a.pbuf, Tld, do.data_ptr(), D, dqkv.data_ptr() + 2 * D * esz, 3 * D
-                it[1].M, it[1].I, it[1].J, it[1].nb_outer, it[1].nb_inner, it[1].strides6 = Tp, Tp, d, B, H, sV
-                it[2].P, it[2].ldp, it[2].Q, it[2].ldq, it[2].O, it[2].ldo = dsrel.data_ptr(), Rld, qkv.data_ptr(), 3 * D, de.data_ptr(), de.stride(0)
-                it[2].M, it[2].I, it[2].J, it[2].nb_outer, it[2].nb_inner, it[2].strides6 = B * Tp, 2 * Tp - 1, d, 1, H, sE
-                lib.gemm_tn_batched_multi(rt.dt(), it, 3, rt.stream())
-            else:
-                lib.gemm_tn_batched_store(rt.dt(), a.dsbuf, Tld, qkv.data_ptr(), 3 * D, dqkv.data_ptr() + D * esz, 3 * D, Tp, Tp, d, B, H, sK, rt.stream())
-                lib.gemm_tn_batched_store(rt.dt(), a.pbuf, Tld, do.data_ptr(), D, dqkv.data_ptr() + 2 * D * esz, 3 * D, Tp, Tp, d, B, H, sV, rt.stream())
-                lib.gemm_tn_batched(rt.dt(), dsrel.data_ptr(), Rld, qkv.data_ptr(), 3 * D, de.data_ptr(), de.stride(0), B * Tp, 2 * Tp - 1, d, 1, H, sE, rt.stream())
+        n_rel = H * B * Tp * _pad8(2 * Tp - 1)                       # zero-initialised, from the step's pre-zeroed pool (was a fill launch per layer on the dependent chain)
+        if adt == torch.bfloat16:
+            dsrel = rt.zeros_scratch((n_rel + 1) // 2, dy.device).view(torch.bfloat16)[:n_rel].view(H, B * Tp, -1)
+        else:
+            dsrel = rt.zeros_scratch(n_rel, dy.device).view(H, B * Tp, -1)
+        _attn_backward(a, do, dqkv, dsrel, de, products=True, one_launch=True)
         dhp = None
         grp = rt.fused_group(wq)
         if grp is not None and grp.weights[1] is wk and grp.weights[2] is wv and bq is not None:
@@ -985,8 +1005,7 @@ class RelPosCoreFn(torch.autograd.Function):
             mask = mask.reshape(mask.shape[0], T, T).float().contiguous()
         o = empty((B * T, D), adt, qkv)
         lse = empty((B * H, T, 2), torch.float32, qkv)
-        a = _attn_args(qkv, e, lens, len_div, mask, o, lse, B, H, T, d, D)
-        a.scale = scale
+        a = _attn_args(qkv, e, lens, len_div, mask, o, lse, B, H, T, d, D, scale=scale)
         lib.relpos_attention_fwd(rt.dt(), _byref(a), rt.stream())
         ctx.saved = (qkv, e, o, lse, lens, len_div, mask, B, H, T, d, scale)
         return o
@@ -998,26 +1017,9 @@ class RelPosCoreFn(torch.autograd.Function):
         do = do.to(adt).contiguous()
         dqkv = empty((B * T, 3 * D), adt, do)
         de = torch.zeros((2 * T - 1, D), dtype=torch.float32, device=do.device)
-        a = _attn_args(qkv, e, lens, len_div, mask, o, lse, B, H, T, d, D)
-        a.scale = scale
-        a.dout = do.data_ptr()
-        esz = dqkv.element_size()
-        a.dq, a.lddq = dqkv.data_ptr(), 3 * D
-        a.dk, a.dv, a.ldd = dqkv.data_ptr() + D * esz, dqkv.data_ptr() + 2 * D * esz, 3 * D
-        a.de, a.ldde = de.data_ptr(), D
-        Tld, Rld = (T + 7) // 8 * 8, (2 * T - 1 + 7) // 8 * 8
-        scratch = empty((2, B * H, T, Tld), adt, do)
-        a.pbuf, a.dsbuf, a.ldt = scratch.data_ptr(), scratch.data_ptr() + scratch[0].numel() * esz, Tld
-        dsrel = torch.zeros((H, B * T, Rld), dtype=adt, device=do.device)
-        a.dsrel, a.ldr = dsrel.data_ptr(), Rld
-        lib.relpos_attention_bwd(rt.dt(), _byref(a), rt.stream())
-        L6 = ctypes.c_longlong * 6
-        lib.gemm_tn_batched_store(rt.dt(), a.dsbuf, Tld, qkv.data_ptr(), 3 * D, dqkv.data_ptr() + D * esz, 3 * D, T, T, d, B, H,
-                                  L6(H * T * Tld, T * Tld, T * 3 * D, d, T * 3 * D, d), rt.stream())
-        lib.gemm_tn_batched_store(rt.dt(), a.pbuf, Tld, do.data_ptr(), D, dqkv.data_ptr() + 2 * D * esz, 3 * D, T, T, d, B, H,
-                                  L6(H * T * Tld, T * Tld, T * D, d, T * 3 * D, d), rt.stream())
-        lib.gemm_tn_batched(rt.dt(), dsrel.data_ptr(), Rld, qkv.data_ptr(), 3 * D, de.data_ptr(), D, B * T, 2 * T - 1, d, 1, H,
-                            L6(0, B * T * Rld, 0, d, 0, d), rt.stream())
+        a = _attn_args(qkv, e, lens, len_div, mask, o, lse, B, H, T, d, D, scale=scale)
+        dsrel = torch.zeros((H, B * T, _pad8(2 * T - 1)), dtype=adt, device=do.device)
+        _attn_backward(a, do, dqkv, dsrel, de, products=True)
         return dqkv, de.to(adt), None, None, None, None, None, None, None, None
 
 
@@ -1033,27 +1035,15 @@ def relpos_core_infer(q, k, v, e, lens, mask, B, H, T, Tk, d, scale, want_probs=
         mask = mask.reshape(mask.shape[0], T, Tk).float().contiguous()
     o = empty((B * T, D), adt, q)
     lse = empty((B * H, T, 2), torch.float32, q)
-    a = Attn()
-    a.q, a.k, a.v, a.ld = q.data_ptr(), k.data_ptr(), v.data_ptr(), D
-    a.e, a.lde = e.data_ptr(), D
-    a.lens, a.len_div = _p(lens), 1
-    if mask is not None:
-        a.mask, a.mask_bstride = mask.data_ptr(), (T * Tk if mask.shape[0] > 1 else 0)
-    a.o, a.ldo, a.lse = o.data_ptr(), D, lse.data_ptr()
-    a.B, a.H, a.T, a.d, a.scale, a.Tk = B, H, T, d, scale, Tk
+    a = _attn_args(q, e, lens, 1, mask, o, lse, B, H, T, d, D, kv=(k, v, D), Tk=Tk, scale=scale)
     lib.relpos_attention_fwd(rt.dt(), _byref(a), rt.stream())
     if not want_probs:
         return o, None
-    Tld = (Tk + 7) // 8 * 8
-    scratch = empty((2, B * H, T, Tld), adt, q)
     dq = empty((B * T, D), adt, q)
     zero = torch.zeros((B * T, D), dtype=adt, device=q.device)
-    dsrel = torch.zeros((H, B * T, (Tk + T - 1 + 7) // 8 * 8), dtype=adt, device=q.device)
-    a.dout, a.dq, a.lddq = zero.data_ptr(), dq.data_ptr(), D
-    a.pbuf, a.dsbuf, a.ldt = scratch.data_ptr(), scratch.data_ptr() + scratch[0].numel() * scratch.element_size(), Tld
-    a.dsrel, a.ldr = dsrel.data_ptr(), dsrel.shape[2]
-    lib.relpos_attention_bwd(rt.dt(), _byref(a), rt.stream())         # the row pass recomputes the probabilities from (max, sum) and stores them
-    return o, scratch[0].view(B, H, T, Tld)[..., :Tk].float()
+    dsrel = torch.zeros((H, B * T, _pad8(Tk + T - 1)), dtype=adt, device=q.device)
+    scratch = _attn_backward(a, zero, dq, dsrel)                      # the row pass recomputes the probabilities from (max, sum) and stores them
+    return o, scratch[0].view(B, H, T, -1)[..., :Tk].float()
 
 
 def _pool_mask(mask, T, P):
@@ -1090,12 +1080,17 @@ def bn_finalize(bn, st, count, training):
         # SyncBatchNorm: collapse the replicas, append the local count, sum over ranks (one small RCCL all-reduce)
         st.red = rt.sync_bn_stats(st.stats, st.NREP, C, count, key=(id(bn), "f"))
         sptr, nrep, cptr = st.red.data_ptr(), 1, st.red.data_ptr() + 2 * C * 4
-    mom = bn.momentum if bn.momentum is not None else 0.1
-    track = bn.track_running_stats and bn.running_mean is not None
-    lib.bn_finalize(sptr, nrep, cptr, float(count), bn.weight.data_ptr(), bn.bias.data_ptr(),
-                    bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-                    bn.num_batches_tracked.data_ptr() if (track and training) else None, mom, bn.eps, st.ss.data_ptr(), C, int(training), rt.stream())
+    lib.bn_finalize(sptr, nrep, cptr, float(count), bn.weight.data_ptr(), bn.bias.data_ptr(), *_bn_running(bn, training), bn.eps, st.ss.data_ptr(), C, int(training),
+                    rt.stream())
     return cptr
+
+
+def _bn_running(bn, training):
+    """(running_mean, running_var, num_batches_tracked pointers, momentum) as the finalize kernels take them: null without tracked statistics; the batch counter
+    only moves in training"""
+    track = bn.track_running_stats and bn.running_mean is not None
+    return (bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
+            bn.num_batches_tracked.data_ptr() if (track and training) else None, bn.momentum if bn.momentum is not None else 0.1)
 
 
 def bn_backward(bn, st, cptr, count, dout, y, out, act, M, want_dres=False, pre=None, mask=None):
@@ -1111,10 +1106,7 @@ def bn_backward(bn, st, cptr, count, dout, y, out, act, M, want_dres=False, pre=
         lib.bn_bwd_reduce_mask(rt.dt(), dout.data_ptr(), y.data_ptr(), mask.data_ptr(), st.ss.data_ptr(), dstats.data_ptr(), M, C, rt.stream())
     else:
         lib.bn_bwd_reduce(rt.dt(), dout.data_ptr(), y.data_ptr(), _p(out), st.ss.data_ptr(), act, dstats.data_ptr(), M, C, rt.stream())
-    gw, gb = grad_of(bn.weight), grad_of(bn.bias)
-    dstats, synced = _add_local_affine_grads(dstats, gw, gb, C, (id(bn), "b"))
-    if synced:
-        gw = gb = None                    # (SyncBatchNorm) already added from the LOCAL sums; the kernel must not add the global ones
+    dstats, gw, gb = _bn_sync_grads(bn, dstats, C)
     dy = empty((M, C), adt, dout)
     dres = empty((M, C), adt, dout) if want_dres else None
     if mask is not None:
@@ -1139,6 +1131,14 @@ def _add_local_affine_grads(dstats, gw, gb, C, key):
     lib.bn_affine_grads(dstats.data_ptr(), gw.data_ptr(), gb.data_ptr(), C, rt.stream())
     return rt.all_reduce_small(dstats, key), True
 
+
+def _bn_sync_grads(bn, dstats, C):
+    """the step between the two passes of a training-mode BatchNorm backward: dstats = the local [sum d | sum d*y].  Returns (the dstats the apply pass reads,
+    d(gamma), d(beta) accumulators for it to add to).  SyncBatchNorm: the global sums, and (None, None) -- the affine gradients are already added from the LOCAL
+    sums; the kernel must not add the global ones."""
+    gw, gb = grad_of(bn.weight), grad_of(bn.bias)
+    dstats, synced = _add_local_affine_grads(dstats, gw, gb, C, (id(bn), "b"))
+    return (dstats, None, None) if synced else (dstats, gw, gb)
 
 
 def dw_pad_left(conv):
@@ -1171,10 +1171,8 @@ class ConvModuleFn(torch.autograd.Function):
         use_batch = training and not getattr(bn, "frozen", False)
         if use_batch and not rt.sync_batchnorm() and CONVMOD_BN_FUSE:
             # local batch statistics: the finalize reads the depthwise kernel's column-reduction partials (one launch less in the block's dependent chain)
-            track = bn.track_running_stats and bn.running_mean is not None
             lib.glu_dwconv_fwd_bn(rt.dt(), u.data_ptr(), dw.weight.data_ptr(), _p(dw.bias), c.data_ptr(), st.stats.data_ptr(), B, T, Dp, K, stride, dw_pad_left(dw),
-                                  bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-                                  bn.num_batches_tracked.data_ptr() if track else None, bn.momentum if bn.momentum is not None else 0.1, bn.eps, st.ss.data_ptr(), rt.stream())
+                                  bn.weight.data_ptr(), bn.bias.data_ptr(), *_bn_running(bn, use_batch), bn.eps, st.ss.data_ptr(), rt.stream())
             cptr = None
         else:
             lib.glu_dwconv_fwd(rt.dt(), u.data_ptr(), dw.weight.data_ptr(), _p(dw.bias), c.data_ptr(), st.stats.data_ptr() if use_batch else None,
@@ -1474,25 +1472,22 @@ def conv2d_fwd(x, weight, N, H, W, Cin, stride, stats=None):
     sh = rt.shadow(weight)
     y = empty((M, Cout), rt.act_dtype(), x)
     if _slab_conv(H, W, Cin, Cout, KH, KW, stride):
-        ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
+        ev = KERNEL_TIMER.start()
         lib.conv3x3_c64(x.data_ptr(), sh.fwd.data_ptr(), y.data_ptr(), None, _p(stats), N, H, W, 0, rt.stream())
-        if ev is not None:
-            KERNEL_TIMER.stop(ev, (2, 0), 2.0 * M * Cout * KH * KW * Cin, 2.0 * (N * H * W * Cin + Cout * KH * KW * Cin + M * Cout))
+        KERNEL_TIMER.stop(ev, (2, 0), 2.0 * M * Cout * KH * KW * Cin, 2.0 * (N * H * W * Cin + Cout * KH * KW * Cin + M * Cout))
         return y, OH, OW
     gemm_nt(x, sh.fwd, y, M, Cout, KH * KW * Cin, rows=rows_conv(H, W, Cin, KH, KW, stride, pad, OH, OW), mode=ROWS_CONV_FWD, stats=stats,
             abytes=2.0 * (N * H * W * Cin + Cout * KH * KW * Cin + M * Cout))
     return y, OH, OW
 
 
-SLAB_CONV = True
-SLAB_WGRAD128 = True
 SHORTCUT_SUBGRID = True        # ResNet projection shortcuts: input gradient on the subsampled grid (res_cls0)
 GROUP_WGRAD128 = True          # the wide layers' weight gradients as one grouped launch at the end of the backward pass
 
 
 def _slab_conv(H, W, Cin, Cout, KH, KW, stride):
     """ResNet stage 1 (3x3, stride 1, 64 -> 64 channels, 22x22 images), bf16: weights resident in LDS + one image slab per iteration (csrc/conv3x3.hip)"""
-    return SLAB_CONV and rt.act_dtype() == torch.bfloat16 and bool(lib.raw("avec_conv3x3_c64_supported")(H, W, Cin, Cout, KH, KW, stride))
+    return rt.act_dtype() == torch.bfloat16 and bool(lib.raw("avec_conv3x3_c64_supported")(H, W, Cin, Cout, KH, KW, stride))
 
 
 class BnbFuse:
@@ -1518,8 +1513,7 @@ def conv2d_bwd(dy, x, weight, N, H, W, Cin, stride, OH, OW, need_dx=True, dx_res
     M = N * OH * OW
     sh = rt.shadow(weight)
     slab64 = _slab_conv(H, W, Cin, Cout, KH, KW, stride) and H * (W + 1) <= 512
-    wide = (not slab64 and SLAB_CONV and SLAB_WGRAD128 and rt.act_dtype() == torch.bfloat16 and
-            bool(lib.raw("avec_wgrad3x3_c128_supported")(H, W, Cin, Cout, KH, KW, stride)))
+    wide = not slab64 and rt.act_dtype() == torch.bfloat16 and bool(lib.raw("avec_wgrad3x3_c128_supported")(H, W, Cin, Cout, KH, KW, stride))
     if slab64 or wide:
         if GROUP_WGRAD128 and _in_backward():
             # queued: one grouped launch for all the layers of a kind when the backward pass is through (the final atomics of a launch of its own are ~30 % of it)
@@ -1527,26 +1521,24 @@ def conv2d_bwd(dy, x, weight, N, H, W, Cin, stride, OH, OW, need_dx=True, dx_res
             it.x, it.dy, it.dw, it.images, it.C, it.H, it.W = x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, Cin, H, W
             _pass().pending().push("cw64" if slab64 else "cw", it, [x, dy], 2.0 * M * Cout * KH * KW * Cin)
         else:
-            ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
+            ev = KERNEL_TIMER.start()
             if slab64:
                 lib.wgrad3x3_c64(x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, H, W, rt.stream())
             else:
                 lib.wgrad3x3_c128(x.data_ptr(), dy.data_ptr(), grad_of(weight).data_ptr(), N, Cin, H, W, rt.stream())
-            if ev is not None:
-                KERNEL_TIMER.stop(ev, (2, 2), 2.0 * M * Cout * KH * KW * Cin)
+            KERNEL_TIMER.stop(ev, (2, 2), 2.0 * M * Cout * KH * KW * Cin)
     else:
         gemm_tn(dy, x, grad_of(weight), M, Cout, KH * KW * Cin, q_rows=rows_conv(H, W, Cin, KH, KW, stride, pad, OH, OW), q_mode=ROWS_CONV_FWD, side=True)
     if not need_dx:
         return None
     dx = empty((N * H * W, Cin), rt.act_dtype(), dy)
     if _slab_conv(H, W, Cin, Cout, KH, KW, stride):
-        ev = KERNEL_TIMER.start() if KERNEL_TIMER.enabled else None
+        ev = KERNEL_TIMER.start()
         if dx_res_mask is not None:
             lib.conv3x3_c64_res_masked(dy.data_ptr(), sh.bwd.data_ptr(), dx.data_ptr(), dx_res.data_ptr(), dx_res_mask.data_ptr(), N, H, W, 1, rt.stream())
         else:
             lib.conv3x3_c64(dy.data_ptr(), sh.bwd.data_ptr(), dx.data_ptr(), _p(dx_res), None, N, H, W, 1, rt.stream())
-        if ev is not None:
-            KERNEL_TIMER.stop(ev, (2, 1), 2.0 * N * H * W * Cin * KH * KW * Cout, 2.0 * (2 * N * H * W * Cin + Cout * KH * KW * Cin + M * Cout))
+        KERNEL_TIMER.stop(ev, (2, 1), 2.0 * N * H * W * Cin * KH * KW * Cout, 2.0 * (2 * N * H * W * Cin + Cout * KH * KW * Cin + M * Cout))
         return dx
     # algorithmic work of the backward-data product: one MAC per (output pixel, tap, Cin, Cout) -- for stride 2 three of four taps of the implicit GEMM
     # over input pixels are structurally zero and are skipped by the parity-class kernel: they are not counted
@@ -1557,9 +1549,6 @@ def conv2d_bwd(dy, x, weight, N, H, W, Cin, stride, OH, OW, need_dx=True, dx_res
     if fuse is not None:
         fuse.done = True
     return dx
-
-
-RES_MASK = True      # identity-residual ResNet blocks: the block-output gradient enters the first convolution's backward-data epilogue through the 1-bit ReLU mask (no masked copy of it is written)
 
 
 def res_mask_ok(H, W, Cin, Cout, stride):
@@ -1638,7 +1627,7 @@ class ResNetBlockFn(torch.autograd.Function):
             raise RuntimeError("ResNetBlock backward: a fused BatchNorm-backward request does not belong to this block (the block output has another consumer?)")
         # the gradient that passed the block's final ReLU is needed twice more (second BatchNorm's backward above all, then as the residual branch's gradient): with the bit
         # mask at hand nobody needs it as a tensor -- the consumers below apply the mask themselves
-        lazy_dres = (RES_MASK and not BNB_FUSE and ctx.relu_mask is not None and pre2 is None and
+        lazy_dres = (not BNB_FUSE and ctx.relu_mask is not None and pre2 is None and
                      (has_proj or (conv1.weight.shape[2] == 3 and res_mask_ok(H, W, Cin, Cout, stride) and not KERNEL_TIMER.enabled)))
         dy2, dres = bn_backward(bn2, st2, c2, Mo, dout, y2, out, ACT_RELU, Mo, want_dres=not lazy_dres, pre=pre2, mask=ctx.relu_mask)
         f1 = BnbFuse(y1, st1.ss, None, Cout)        # BatchNorm 1 + ReLU: the mask comes from the pre-activation itself
@@ -1677,7 +1666,6 @@ class ResNetBlockFn(torch.autograd.Function):
 
 STEM3D_DIRECT = True      # direct (no im2col) bf16 visual-stem kernels
 STEM3P_FUSED_WGRAD = True  # ... and the weight gradient computed from the recomputed tiles in the same kernel (no dz tensor)
-STEM_GRAD_CLONE = False   # the stem's backward masks the incoming gradient IN PLACE (it is the first ResNet block's dx: 99 MB, nothing else reads it); 1 = work on a copy
 STEM3P = True                    # ... with the max pool inside the convolution kernel and the pre-pool tensor recomputed in backward (stem3p.hip)
 
 
@@ -1739,19 +1727,14 @@ class VideoStemFn(torch.autograd.Function):
     def backward(ctx, dpool):
         v, y, idx, st, cp, conv, bn, r, B, T, OH, OW, C, M, K, training, ymax = ctx.saved
         assert training, "VideoStem backward is implemented for training-mode BatchNorm"
-        dpool_in = dpool
         dpool = dpool.to(rt.act_dtype()).contiguous()
-        if isinstance(r, tuple) and dpool.data_ptr() == dpool_in.data_ptr() and STEM_GRAD_CLONE:
-            dpool = dpool.clone()                               # stem3p_reduce masks it in place (AVEC_STEM_GRAD_CLONE=1: for code that inspects the stem output's gradient through hooks / retain_grad)
         if isinstance(r, tuple):                                # stem3p: ReLU mask + BatchNorm-backward sums over the pooled tensor, then dz from the RECOMPUTED conv output
             _, vb, w8, zp, PH, PW = r
             H, W = v.shape[2], v.shape[3]
             dstats = torch.zeros(2 * C, dtype=torch.float32, device=v.device)
-            lib.stem3p_reduce(dpool.data_ptr(), zp.data_ptr(), st.ss.data_ptr(), dstats.data_ptr(), B * T, PH, PW, rt.stream())      # (dpool is masked in place)
-            gw, gb = grad_of(bn.weight), grad_of(bn.bias)
-            dstats, synced = _add_local_affine_grads(dstats, gw, gb, C, (id(bn), "b"))
-            if synced:
-                gw = gb = None
+            # dpool is masked IN PLACE: it is the first ResNet block's dx (99 MB), which nothing else reads -- a hook or retain_grad on the stem's output sees the masked gradient
+            lib.stem3p_reduce(dpool.data_ptr(), zp.data_ptr(), st.ss.data_ptr(), dstats.data_ptr(), B * T, PH, PW, rt.stream())
+            dstats, gw, gb = _bn_sync_grads(bn, dstats, C)
             if STEM3P_FUSED_WGRAD and lib.raw("avec_stem3p_wgrad_supported")(B, T, H, W):
                 # recompute + routing + weight gradient in ONE kernel: neither z nor dz exist in memory
                 lib.stem3p_wgrad(vb.data_ptr(), w8.data_ptr(), _p(conv.bias), dpool.data_ptr(), idx.data_ptr(), st.ss.data_ptr(), bn.weight.data_ptr(), dstats.data_ptr(), cp, float(M),
@@ -1766,18 +1749,16 @@ class VideoStemFn(torch.autograd.Function):
             stamp("v_stem_end:b")
             return None, None, None, None, None
         dstats = torch.zeros(2 * C, dtype=torch.float32, device=v.device)
-        args = (dpool.data_ptr(), idx.data_ptr(), y.data_ptr(), st.ss.data_ptr(), bn.weight.data_ptr(), dstats.data_ptr(), cp, float(M))
+
+        def common(ds):          # what both phases of avec_stem_pool_bwd take; ds: the sums phase 0 writes / phase 1 reads
+            return dpool.data_ptr(), idx.data_ptr(), y.data_ptr(), st.ss.data_ptr(), bn.weight.data_ptr(), ds.data_ptr(), cp, float(M)
         if ymax is not None:
             lib.stem_pool_bwd_reduce_pooled(rt.dt(), dpool.data_ptr(), idx.data_ptr(), ymax.data_ptr(), st.ss.data_ptr(), dstats.data_ptr(), B * T, OH, OW, C, rt.stream())
         else:
-            lib.stem_pool_bwd(rt.dt(), *args, 0, None, None, None, B * T, OH, OW, C, rt.stream())
-        gw, gb = grad_of(bn.weight), grad_of(bn.bias)
-        dstats, synced = _add_local_affine_grads(dstats, gw, gb, C, (id(bn), "b"))
-        if synced:
-            gw = gb = None
-            args = args[:5] + (dstats.data_ptr(),) + args[6:]
+            lib.stem_pool_bwd(rt.dt(), *common(dstats), 0, None, None, None, B * T, OH, OW, C, rt.stream())
+        dstats, gw, gb = _bn_sync_grads(bn, dstats, C)
         dy = empty((M, C), rt.act_dtype(), v)
-        lib.stem_pool_bwd(rt.dt(), *args, 1, dy.data_ptr(), _p(gw), _p(gb), B * T, OH, OW, C, rt.stream())
+        lib.stem_pool_bwd(rt.dt(), *common(dstats), 1, dy.data_ptr(), _p(gw), _p(gb), B * T, OH, OW, C, rt.stream())
         if r is None:
             H, W = v.shape[2], v.shape[3]
             lib.stem3d_wgrad(v.data_ptr(), dy.data_ptr(), grad_of(conv.weight).data_ptr(), B, T, H, W, rt.stream())
@@ -1838,14 +1819,12 @@ class AudioStemFn(torch.autograd.Function):
         flush_param_grads()                                   # last node of the audio branch: its queued parameter gradients go out on this (the branch's) stream
         da = da.to(rt.act_dtype()).contiguous()
         dstats = torch.zeros(2 * C, dtype=torch.float32, device=mel.device)
-        base = (da.data_ptr(), y.data_ptr(), mel.data_ptr(), st.ss.data_ptr(), bn.weight.data_ptr(), dstats.data_ptr(), cp, float(count))
-        lib.audio_stem_bwd(rt.dt(), *base, 0, None, None, None, None, B, NM, F, C, rt.stream())
-        gw, gb = grad_of(bn.weight), grad_of(bn.bias)
-        dstats, synced = _add_local_affine_grads(dstats, gw, gb, C, (id(bn), "b"))
-        if synced:
-            gw = gb = None
-            base = base[:5] + (dstats.data_ptr(),) + base[6:]
-        lib.audio_stem_bwd(rt.dt(), *base, 1, grad_of(conv.weight).data_ptr(), None if conv.bias is None else grad_of(conv.bias).data_ptr(),
+
+        def common(ds):          # what both phases of avec_audio_stem_bwd take; ds: the sums phase 0 writes / phase 1 reads
+            return da.data_ptr(), y.data_ptr(), mel.data_ptr(), st.ss.data_ptr(), bn.weight.data_ptr(), ds.data_ptr(), cp, float(count)
+        lib.audio_stem_bwd(rt.dt(), *common(dstats), 0, None, None, None, None, B, NM, F, C, rt.stream())
+        dstats, gw, gb = _bn_sync_grads(bn, dstats, C)
+        lib.audio_stem_bwd(rt.dt(), *common(dstats), 1, grad_of(conv.weight).data_ptr(), None if conv.bias is None else grad_of(conv.bias).data_ptr(),
                            _p(gw), _p(gb), B, NM, F, C, rt.stream())
         stamp("a_stem_end:b")
         arena = rt.arena_of(bn)
@@ -1873,7 +1852,7 @@ def mel_spectrogram(audio, window, dft, fb, n_fft, win, hop, n_mels):
 def spec_augment_(mel, lens, mF, Fp, mT, pS, sid):
     B, NM, F = mel.shape
     lens_ = None if lens is None else lens.to(device=mel.device, dtype=torch.int64).contiguous()
-    lib.specaugment(mel.data_ptr(), _p(lens_), B, NM, F, mF, Fp, mT, pS, rt.rng_state(mel.device).data_ptr(), sid, rt.stream())
+    lib.specaugment(mel.data_ptr(), _p(lens_), B, NM, F, mF, Fp, mT, pS, _rng(mel.device), sid, rt.stream())
     return mel
 
 
