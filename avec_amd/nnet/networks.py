@@ -7,7 +7,7 @@ import torch.nn as nn
 from .. import ops
 from .. import runtime as rt
 from . import attentions, blocks, layers, modules, preprocessing, transforms
-from .streaming import AudioFrontStreamSession, AudioStreamSession, ConformerStreamSession
+from .streaming import AudioFrontStreamSession, AudioStreamSession, ConformerStreamSession, VisualFrontStreamSession, VisualStreamSession
 
 
 class ResNet(nn.Module):
@@ -254,6 +254,14 @@ class VisualEfficientConformerEncoder(nn.Module):
     def forward(self, x, lengths):
         """x: (B, 1, T, H, W)"""
         return self.forward_back(self.forward_front(x), lengths)
+
+    def stream_front(self, batch_size, chunk_frames):
+        """A VisualFrontStreamSession: video chunks -> the 256-wide per-frame features the back-end consumes, with the offline front-end's arithmetic."""
+        return VisualFrontStreamSession(self, batch_size, chunk_frames)
+
+    def stream(self, batch_size, chunk_frames):
+        """A VisualStreamSession: video chunks -> logits, the front session + back_end.stream() + head (the back-end's refusals are ConformerInterCTC.stream()'s)."""
+        return VisualStreamSession(self, batch_size, chunk_frames)
 
 
 def audio_first_env():

@@ -1,6 +1,7 @@
-"""Streaming sessions: a causal Conformer stack, the audio front-end and the CTC beam search run chunk by chunk over a fixed number of utterance slots.  None of
-them has a counterpart in the reference; the factories (ConformerInterCTC.stream, AudioEfficientConformerEncoder.stream_front / .stream, CTCBeamSearchDecoder.stream)
-stay with the classes they wrap.  A session owns its device state; nothing is added to a module tree or a state_dict."""
+"""Streaming sessions: a causal Conformer stack, the audio and the visual front-end and the CTC beam search run chunk by chunk over a fixed number of utterance slots.
+None of them has a counterpart in the reference; the factories (ConformerInterCTC.stream, AudioEfficientConformerEncoder.stream_front / .stream,
+VisualEfficientConformerEncoder.stream_front / .stream, CTCBeamSearchDecoder.stream) stay with the classes they wrap.  A session owns its device state; nothing is
+added to a module tree or a state_dict."""
 import torch
 import torch.nn as nn
 
@@ -9,7 +10,8 @@ from .. import runtime as rt
 from . import attentions, normalizations
 from .captured import CapturedStep
 
-__all__ = ["slot_mask", "ConformerStreamSession", "AudioFrontStreamSession", "AudioStreamSession", "CTCBeamStreamSession"]
+__all__ = ["slot_mask", "ConformerStreamSession", "AudioFrontStreamSession", "AudioStreamSession", "VisualFrontStreamSession", "VisualStreamSession",
+           "CTCBeamStreamSession"]
 
 
 def slot_mask(flags, B):
@@ -479,6 +481,220 @@ class AudioStreamSession:
     def capture(self, device=None):
         """capture both halves (AudioFrontStreamSession.capture, ConformerStreamSession.capture); call it before the first push"""
         self.front.capture(device)
+        self.back.capture(device)
+        return self
+
+
+class VisualFrontStreamSession(_CapturableSession):
+    """VisualEfficientConformerEncoder.stream_front(): the visual front-end (Conv3d stem + BatchNorm3d + ReLU + max pool -> ResNet-18 -> Linear) run on video chunks.
+    The frames a slot has produced after any sequence of pushes equal the offline front-end's frames on the frames pushed so far (and, once the utterance has ended, on
+    the whole utterance: both temporal zero paddings included).  Everything behind the Conv3d works per frame and eval-mode BatchNorm uses running statistics, so the
+    only coupling in time is the five-tap window: output frame t reads input frames t - 2 .. t + 2, with n frames heard E(n) = max(0, n - 2) frames exist, n at the
+    end; the look-ahead is 2 frames.  Schedule: first_frames = Tc + 2 in an utterance's first push, chunk_frames = Tc in every later one; every push but the last then
+    yields exactly Tc frames, the last at most Tc + 2.  The carried state is a ring of the last 4 input frames per slot, a counter and an `ended` flag, on the device
+    (ops.video_stream_state).  The stem launch writes its frames frame-major, so the first Tc * B of them are a plain view: the ResNet and the Linear run on B * Tc
+    frames, and on the 2 B tail frames only in a push where some slot can yield more than Tc (`resnet_frames` records what the last push ran)."""
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        super().__init__(enc, batch_size)
+        self.enc, self.Tc = enc, int(chunk_frames)
+        self._check(enc)
+        if self.B < 1:
+            raise ValueError("stream_front: batch_size %d" % self.B)
+        if self.Tc < 1:
+            raise ValueError("stream_front: chunk_frames = %d: at least 1 frame per push" % self.Tc)
+        self.first_frames, self.chunk_frames = self.Tc + 2, self.Tc
+        self.Tmax = self.Tc + 2                    # any count up to first_frames, at the end of an utterance too, gives at most Tc + 2 frames
+        self._n = [0] * self.B                     # host mirror of the device counters (None: unknown after a push with device-tensor counts)
+        self._ended = [False] * self.B
+        self._nf_up = None                         # what self.nframes holds
+        self._frames = self._feat = None           # the stem's frames and the features of the last push (static after capture())
+        self.resnet_frames = 0                     # frames the ResNet and the Linear ran on in the last push
+
+    def _check(self, enc):
+        if enc.training:
+            raise RuntimeError("stream_front: the encoder is in training mode (BatchNorm batch statistics are not functions of the past): call .eval() first")
+        stem = enc.front_end[0].layers[0]
+        conv, bn = stem[0], stem[1]
+        if not (bn.track_running_stats and bn.running_mean is not None):
+            raise NotImplementedError("stream_front: the stem's BatchNorm keeps no running statistics")
+        if not (tuple(conv.weight.shape) == (64, 1, 5, 7, 7) and tuple(conv.stride) == (1, 2, 2) and getattr(conv, "padding_type", "same") == "same"):
+            raise NotImplementedError("stream_front: the stem is not the (5, 7, 7) / stride (1, 2, 2) 'same' convolution of one input channel into 64 (weight %s, stride %s)"
+                                      % (tuple(conv.weight.shape), tuple(conv.stride)))
+
+    @staticmethod
+    def _ready(n):
+        return max(0, n - 2)
+
+    def _allocate(self, dev):
+        self.nframes = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        self.reset_flags, self.last_flags = self._flags(dev), self._flags(dev)
+        stem = self.enc.front_end[0].layers[0]
+        st = ops.BNState(64, self.nframes)
+        ops.bn_finalize(stem[1], st, 1, False)         # eval mode: scale | shift from the running statistics
+        self.ss = st.ss
+        self.w8 = ops.video_stem_w8(stem[0].weight)    # once per session, not once per push
+        self.state = {"ring": None}                    # the ring's size depends on the frame: allocated by the first _run
+
+    def _resnet(self, frames, f0, f1, feat):
+        """frames f0 .. f1 - 1 of the frame-major stem output through the ResNet and the Linear -> feat[:, f0:f1]"""
+        nf, B = f1 - f0, self.B
+        y = self.enc.front_end[3].forward_nhwc(frames[f0:f1].reshape(nf * B, *frames.shape[2:]))
+        feat[:, f0:f1].copy_(y.view(nf, B, -1).transpose(0, 1))
+
+    def _run(self, video):
+        if not (video.dtype == torch.float32 and video.is_contiguous()):
+            video = video.float().contiguous()
+        B, Tc = self.B, self.Tc
+        if self.state["ring"] is None:
+            self.state["ring"] = ops.video_stream_state(B, video.shape[2], video.shape[3], video.device)
+        conv = self.enc.front_end[0].layers[0][0]
+        frames, out_len = ops.video_stem_stream(video, self.state["ring"], self.w8, conv.bias, self.ss, self.nframes, self.reset_flags, self.last_flags, Tmax=self.Tmax)
+        ops.video_stream_advance(video, self.state["ring"], self.nframes, self.reset_flags, self.last_flags)
+        feat = torch.zeros(B, self.Tmax, self.enc.front_end[3].head[1].weight.shape[0], dtype=torch.float32, device=video.device)
+        self._resnet(frames, 0, Tc, feat)
+        self._frames, self._feat = frames, feat
+        return feat, out_len
+
+    # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
+    def _controls(self, n_frames, last, reset):
+        """-> (reset mask, last mask, host counts or None for a device tensor, frames per slot or None): checks a host-list push against the contract, changes nothing"""
+        B = self.B
+        rmask = self._reset_mask(reset) or [False] * B
+        lmask = slot_mask(last, B)
+        if torch.is_tensor(n_frames):
+            return rmask, lmask, None, None
+        if n_frames is not None and len(n_frames) != B:
+            raise ValueError("push: n_frames %r for %d slots" % (list(n_frames), B))
+        counts, frames = [], []
+        for b in range(B):
+            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
+            if n0 is None:
+                raise RuntimeError("push: slot %d was last pushed with device-tensor counts, which the host does not mirror: go on with a tensor, or reset the slot" % b)
+            cap = self.first_frames if n0 == 0 else self.chunk_frames
+            c = (0 if ended else cap) if n_frames is None else int(n_frames[b])
+            if c < 0 or c > cap:
+                raise ValueError("push: n_frames[%d] = %d outside 0 .. %d (first_frames = %d at the start of an utterance, chunk_frames = %d later)"
+                                 % (b, c, cap, self.first_frames, self.chunk_frames))
+            if ended:
+                if c > 0:
+                    raise RuntimeError("push: slot %d has ended (last) and was not reset: it takes no frames until reset=[%d] starts the next utterance" % (b, b))
+                frames.append(0)
+            elif lmask[b]:
+                frames.append(n0 + c - self._ready(n0))
+            else:
+                frames.append(self._ready(n0 + c) - self._ready(n0))
+            counts.append(c)
+        return rmask, lmask, counts, frames
+
+    def _upload(self, rmask, lmask, counts, n_frames):
+        B = self.B
+        self._raise_flags(self.reset_flags, rmask)
+        self._raise_flags(self.last_flags, lmask)
+        if counts is None:
+            self.nframes.copy_(n_frames.view(B), non_blocking=True)
+            self._nf_up = None
+            self._n, self._ended = [None] * B, [None] * B                 # a device tensor's contract is the caller's
+            return
+        if counts != self._nf_up:
+            self.nframes.copy_(torch.tensor(counts, dtype=torch.int64), non_blocking=True)
+            self._nf_up = list(counts)
+        for b in range(B):
+            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
+            self._n[b], self._ended[b] = n0 + counts[b], ended or lmask[b]
+
+    def _static_input(self, dev):
+        B = self.B
+        H, W = self._capture_frame
+        return torch.zeros(B, self.first_frames, H, W, dtype=torch.float32, device=dev), ([True] * B, [False] * B, [self.first_frames] * B, None)
+
+    def _forget(self):
+        self._n, self._ended = [0] * self.B, [False] * self.B
+
+    def capture(self, device=None, frame=(88, 88)):
+        """As the other sessions' capture(); `frame` = (H, W) of the video the session will be fed.  The captured push covers the Tc-frame case; a push in which some
+        slot can yield more than Tc frames runs the ResNet on the 2 B tail frames eagerly behind the replay."""
+        self._capture_frame = (int(frame[0]), int(frame[1]))
+        return super().capture(device)
+
+    def push(self, video, n_frames=None, last=None, reset=None):
+        """video [B, Tc + 2, H, W] fp32 ([B, 1, Tc + 2, H, W] is viewed) -> (feat [B, Tc + 2, 256] fp32, out_len [B] int64 on the device): slot b takes the first
+        n_frames[b] frames (a Python list or an int64 device tensor [B]; default: the schedule's count, first_frames after a restart, chunk_frames later, 0 for an
+        ended slot) and yields out_len[b] frames; rows at or past out_len carry no information.  last: slots whose utterance ends with these frames; reset: slots to
+        restart before them (each a list of indices or a host bool mask [B]); the first push restarts every slot.  With host counts the contract is checked on the
+        host, without a synchronisation: counts within 0 .. chunk_frames (0 .. first_frames for a slot at its start), no frames to an ended slot.  With a device
+        tensor it is the caller's.  No host synchronisation after the first push; after capture() the results are static tensors that the next push overwrites."""
+        if video.dim() == 5 and video.shape[1] == 1:
+            video = video[:, 0]
+        if video.dim() != 4 or video.shape[0] != self.B or video.shape[1] != self.first_frames:
+            raise ValueError("push: video %s for a session of %d slots x %d frames" % (tuple(video.shape), self.B, self.first_frames))
+        rt.require_gpu(video)
+        if self.enc.training:
+            raise RuntimeError("push: the encoder went back to training mode; call .eval()")
+        if self._capture is not None and tuple(video.shape[2:]) != self._capture_frame:
+            raise ValueError("push: frames of %dx%d for a push captured at %dx%d" % (video.shape[2], video.shape[3], *self._capture_frame))
+        rmask, lmask, counts, frames = self._controls(n_frames, last, reset)
+        feat, out_len = self._push(video, rmask, lmask, counts, n_frames)
+        self.resnet_frames = self.B * self.Tc
+        if frames is None or any(f > self.Tc for f in frames):          # (device-tensor counts: the host cannot know, the tail always runs)
+            with torch.no_grad():
+                self._resnet(self._frames, self.Tc, self.Tmax, self._feat)
+            self.resnet_frames = self.B * self.Tmax
+        return feat, out_len
+
+
+class VisualStreamSession:
+    """VisualEfficientConformerEncoder.stream(): video chunks -> logits.  The front session feeds back_end.stream() (a ConformerStreamSession, with its refusals) and
+    the head.  The front's schedule makes every push but an utterance's last yield exactly Tc frames, one chunk of the stack; a last push may yield Tc + 1 or Tc + 2:
+    the stack is then pushed a second time with those tail frames for the slots concerned and 0 frames (no change of state) for the others, and the rows it yields
+    are appended."""
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        self.enc = enc
+        self.front = VisualFrontStreamSession(enc, batch_size, chunk_frames)
+        self.back = enc.back_end.stream(batch_size, chunk_frames)
+        self.B, self.Tc, self.S = self.front.B, self.front.Tc, self.back.S
+        if self.Tc < 2:
+            raise ValueError("stream: chunk_frames = %d: at least 2, so that a last push's tail of up to 2 frames fits one chunk of the stack" % self.Tc)
+        self.first_frames, self.chunk_frames = self.front.first_frames, self.front.chunk_frames
+        self._x2 = None
+
+    def _head(self, y):
+        return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
+
+    def push(self, video, n_frames=None, last=None, reset=None):
+        """video [B, Tc + 2, H, W] fp32 -> (logits [B, R, V] fp32, out_len [B] int64 on the device, inter: loss_prefix_i -> [logits chunk, lengths] as offline).
+        n_frames / last / reset: host lists as VisualFrontStreamSession.push; counts must follow the schedule (every push of a slot but its last yields exactly
+        chunk_frames frames; a slot may idle on 0 frames).  R = Tc / S, or Tc / S + ceil(tail / S) in a push where some slot's last chunk left a tail of 1 or 2
+        frames beyond Tc (one more row for every S >= 2)."""
+        if torch.is_tensor(n_frames):
+            raise TypeError("push: the combined session takes host lists for n_frames (it decides on the host whether the stack needs a second push)")
+        B, Tc, S = self.B, self.Tc, self.S
+        rmask, lmask, counts, frames = self.front._controls(n_frames, last, reset)
+        for b in range(B):
+            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 2)):
+                raise ValueError("push: slot %d would yield %d frames from %d: off the schedule (first_frames = %d in an utterance's first push, chunk_frames = %d later, "
+                                 "fewer only with last)" % (b, frames[b], counts[b], self.first_frames, self.chunk_frames))
+        with torch.no_grad():
+            feat, _ = self.front.push(video, counts, lmask, rmask)
+            tail = [max(0, f - Tc) for f in frames]
+            y, ylen, inter = self.back.push(feat[:, :Tc], torch.tensor([min(f, Tc) for f in frames], dtype=torch.int64), rmask)
+            if not any(tail):
+                return self._head(y), ylen, inter
+            # (a captured stack's results are static: keep this push's before the second one refills them)
+            logits, ylen, inter = self._head(y).clone(), ylen.clone(), {k: [v[0].clone(), v[1].clone()] for k, v in inter.items()}
+            if self._x2 is None:
+                self._x2 = torch.zeros(B, Tc, feat.shape[2], dtype=feat.dtype, device=feat.device)
+            self._x2[:, :2].copy_(feat[:, Tc:Tc + 2])
+            y2, ylen2, inter2 = self.back.push(self._x2, torch.tensor(tail, dtype=torch.int64), None)
+            R2 = -(-max(tail) // S)
+            for k, v in inter.items():
+                inter[k] = [torch.cat([v[0], inter2[k][0][:, :R2]], dim=1), v[1] + inter2[k][1]]
+            return torch.cat([logits, self._head(y2[:, :R2].contiguous())], dim=1), ylen + ylen2, inter
+
+    def capture(self, device=None, frame=(88, 88)):
+        """capture both halves (VisualFrontStreamSession.capture, ConformerStreamSession.capture); call it before the first push"""
+        self.front.capture(device, frame)
         self.back.capture(device)
         return self
 

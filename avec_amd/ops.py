@@ -2323,3 +2323,69 @@ def audio_stream_advance(wave, state, n_samples=None, reset=None, last=None, *, 
     B, W = wave.shape
     lib.audio_stream_advance(wave.data_ptr(), wave.stride(0), state.data_ptr(), state.numel(), _p(n_samples), _p(reset), _p(last), B, W, int(n_fft), int(win), int(hop), rt.stream())
     return state
+
+
+# ============================================================================================
+# Streamed visual stem (nnet.VisualFrontStreamSession): video chunks -> the pooled NHWC frames with the offline arithmetic (include/avec_hip.h, csrc/video_stream.hip)
+# ============================================================================================
+def video_stream_state(B, H, W, device):
+    """what ops.video_stem_stream / video_stream_advance carry between pushes: per slot a ring of the last 4 input frames in the compute dtype, the frame counter and
+    the `ended` flag (one uint8 blob of avec_video_stream_state_bytes; never cleared: the first push restarts every slot)"""
+    n = lib.raw("avec_video_stream_state_bytes")(rt.dt(), int(B), int(H), int(W))
+    if n <= 0:
+        raise ValueError("video_stream_state: no state for B=%d frames of %dx%d (W must be a multiple of 8)" % (B, H, W))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def video_stem_w8(weight):
+    """Conv3d weight [64, 1, 5, 7, 7] -> [64][36][8] in the compute dtype as VideoStemFn packs it for stem3p.hip: per (kd, kh) row a zero slot, then the 7 taps; row 35
+    zero.  A session packs once, not once per push."""
+    if tuple(weight.shape) != (64, 1, 5, 7, 7):
+        raise ValueError("video_stem_w8: weight %s is not the [64, 1, 5, 7, 7] stem convolution" % (tuple(weight.shape),))
+    w8 = torch.zeros((64, 36, 8), dtype=rt.act_dtype(), device=weight.device)
+    w8[:, :35, 1:] = weight.detach().reshape(64, 35, 7).to(rt.act_dtype())
+    return w8
+
+
+def _video_stream_ctl(name, chunk, state, n_frames, reset, last):
+    if not (chunk.dim() == 4 and chunk.dtype == torch.float32 and chunk[0].is_contiguous() and state.dtype == torch.uint8 and state.is_contiguous() and state.device == chunk.device):
+        raise ValueError("%s: chunk fp32 [B, Tin, H, W] with contiguous slots and a uint8 state blob on its device (got %s %s, %s)" % (name, tuple(chunk.shape), chunk.dtype, state.dtype))
+    B = chunk.shape[0]
+    _slot_vec(name, "n_frames", n_frames, B, chunk.device)
+    _slot_vec(name, "reset", reset, B, chunk.device, mask=True)
+    _slot_vec(name, "last", last, B, chunk.device, mask=True)
+
+
+def video_stem_stream(chunk, state, w8, bias, ss, n_frames=None, reset=None, last=None, *, Tmax, out=None):
+    """The stem launch of one push: chunk [B, Tin, H, W] fp32 (slot b takes its first n_frames[b] frames; default all Tin) behind the carried ring -> (frames
+    [Tmax, B, PH, PW, 64] act, FRAME-major: local output frame r of slot b in row r * B + b, zeros at or past out_len; out_len [B] int64).  Conv3d + bias, eval-mode
+    BatchNorm (ss: the scale | shift of ops.bn_finalize), ReLU and the 3x3 / s2 max pool in one launch; w8 from ops.video_stem_w8.  Reads the state only:
+    ops.video_stream_advance ends the push.  out: (frames, out_len) to write into.  No synchronisation."""
+    rt.require_gpu(chunk)
+    _video_stream_ctl("video_stem_stream", chunk, state, n_frames, reset, last)
+    B, Tin, H, W = chunk.shape
+    adt = rt.act_dtype()
+    if not (w8.dtype == adt and w8.is_contiguous() and tuple(w8.shape) == (64, 36, 8) and ss.dtype == torch.float32 and ss.numel() >= 128 and ss.is_contiguous()
+            and (bias is None or (bias.dtype == torch.float32 and bias.numel() == 64 and bias.is_contiguous()))):
+        raise ValueError("video_stem_stream: w8 [64, 36, 8] in the compute dtype %s (ops.video_stem_w8), bias fp32 [64], ss fp32 [>= 128] (got %s %s, %s)"
+                         % (adt, tuple(w8.shape), w8.dtype, tuple(ss.shape)))
+    PH, PW = ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1
+    if out is None:
+        out = (torch.empty(int(Tmax), B, PH, PW, 64, dtype=adt, device=chunk.device), torch.empty(B, dtype=torch.int64, device=chunk.device))
+    frames, out_len = out
+    if not (frames.dtype == adt and frames.is_contiguous() and tuple(frames.shape) == (int(Tmax), B, PH, PW, 64) and out_len.dtype == torch.int64 and out_len.is_contiguous()
+            and out_len.numel() == B):
+        raise ValueError("video_stem_stream: out = (frames [Tmax, B, PH, PW, 64] in the activation dtype, out_len int64 [B]), contiguous")
+    lib.video_stem_stream(rt.dt(), chunk.data_ptr(), chunk.stride(0), state.data_ptr(), state.numel(), _p(n_frames), _p(reset), _p(last), w8.data_ptr(), _p(bias), ss.data_ptr(),
+                          frames.data_ptr(), out_len.data_ptr(), B, Tin, int(Tmax), H, W, rt.stream())
+    return frames, out_len
+
+
+def video_stream_advance(chunk, state, n_frames=None, reset=None, last=None):
+    """end of a push: the chunk's last min(n_frames, 4) frames go into their ring slots, n += n_frames, ended |= last, in place; the reset and last flags are cleared
+    (consumed).  A launch of its own behind the stem launch, whose workgroups read the ring slots it overwrites."""
+    rt.require_gpu(chunk)
+    _video_stream_ctl("video_stream_advance", chunk, state, n_frames, reset, last)
+    B, Tin, H, W = chunk.shape
+    lib.video_stream_advance(rt.dt(), chunk.data_ptr(), chunk.stride(0), state.data_ptr(), state.numel(), _p(n_frames), _p(reset), _p(last), B, Tin, H, W, rt.stream())
+    return state

@@ -363,6 +363,35 @@ int avec_audio_stem_stream(int dtype, const float* mel, const float* w, const fl
 int avec_audio_stream_advance(const float* wave, long long ldw, void* state, long long state_bytes, const long long* n_samples, unsigned char* reset,
                               unsigned char* last, int B, int W, int n_fft, int win, int hop, hipStream_t stream);
 
+/* ---- streamed visual stem (nnet.VisualFrontStreamSession; avec_amd/csrc/video_stream.hip) ----------------------------------------------------------------------
+ * Video chunks -> the pooled NHWC frames of the visual stem, with the offline arithmetic: Conv3d(1 -> 64, (5,7,7), stride (1,2,2), zero pad (2,3,3)) + bias, then
+ * y * ss[c] + ss[64 + c] (eval-mode BatchNorm, the scale | shift of avec_bn_finalize), ReLU, max pool 3x3 / stride 2 / pad 1 per frame.  Output frame t reads input
+ * frames t - 2 .. t + 2; a frame index < 0 is zero, and so is one >= n once the utterance has ended (the offline paddings).  With n frames heard E(n) = max(0, n - 2)
+ * output frames exist, n once the utterance has ended.  state (caller-owned, avec_video_stream_state_bytes, 16-byte aligned, never cleared): per slot a ring
+ * [4][H][W] of the last input frames in the compute dtype (frame f in ring slot f & 3; bf16 for AVEC_BF16: the format the conv loop consumes, so a carried frame is
+ * bit-identical to a fresh one), the frame counter n and an `ended` flag.
+ * Controls of a push, [B] each: n_frames int64 (NULL: Tin) = how many frames of chunk row b ([B] rows of Tin frames of H x W fp32, row stride ldc floats) the slot
+ * takes, clamped to 0 .. Tin; reset bytes (NULL: none): the slot restarts (n = 0, not ended) before the frames -- whatever the state holds is older and counts as
+ * absent; last bytes (NULL: none): the utterance ends with these frames; the slot is then ended: until a reset it takes no frames and yields 0.  Frames at or past
+ * n_frames and a state never written are not read into a valid output: a zero is sourced, never multiplied.
+ * One push = avec_video_stem_stream -> avec_video_stream_advance.
+ *
+ * avec_video_stem_stream: with n0 = reset ? 0 : n and c = n_frames[b], slot b yields output frames E0 .. E1 - 1, E0 = max(0, n0 - 2), E1 = last ? n0 + c :
+ *   max(0, n0 + c - 2) (E1 - E0 clamped to Tmax; an ended slot that was not reset yields 0).  Input frame f comes from ring slot f & 3 for n0 - 4 <= f < n0, from
+ *   chunk[b][f - n0] for n0 <= f < n0 + c, from a zero page otherwise.  out is FRAME-major, [Tmax][B][PH][PW][64] in the activation dtype (PH = ceil(ceil(H/2)/2)):
+ *   local frame r of slot b in row r * B + b, the NHWC activation ResNet consumes; rows at or past out_len[b] = E1 - E0 are written as zeros.  w8: the weights
+ *   repacked [64][36][8] in the compute dtype, row (kd, kh) = slot 0 zero, slots 1 .. 7 = kw 0 .. 6, row 35 zero (what avec_stem3p_fwd takes).  An output element is
+ *   one fixed-order reduction over (kd, kh, kw) inside one workgroup: it depends on the values of its five input frames alone, not on where they came from nor on
+ *   the push.  Reads the state only.  W % 8 == 0, W >= 32, H >= 8; chunk, state, w8 and out 16-byte aligned.  AVEC_BF16: MFMA 32x32x16 bf16, fp32 accumulation.
+ * avec_video_stream_advance: ends the push: the chunk's last min(c, 4) frames go into their ring slots (converted to the compute dtype), n = n0 + c, ended |= last,
+ *   and the reset and last flags are cleared (they are consumed).  A launch of its own: it overwrites ring slots that workgroups of the stem launch read. */
+long long avec_video_stream_state_bytes(int dtype, int B, int H, int W);
+int avec_video_stem_stream(int dtype, const float* chunk, long long ldc, const void* state, long long state_bytes, const long long* n_frames,
+                           const unsigned char* reset, const unsigned char* last, const void* w8, const float* bias, const float* ss, void* out,
+                           long long* out_len, int B, int Tin, int Tmax, int H, int W, hipStream_t stream);
+int avec_video_stream_advance(int dtype, const float* chunk, long long ldc, void* state, long long state_bytes, const long long* n_frames, unsigned char* reset,
+                              unsigned char* last, int B, int Tin, int H, int W, hipStream_t stream);
+
 /* ---- front-ends (avec_amd/csrc/frontend.hip) ------------------------------------------------ */
 /* AudioPreprocessing (nnet/preprocessing.py:57-85; torchaudio Spectrogram/MelScale restated): frames -> [DFT via avec_gemm_nt fp32] -> power/mel/log */
 int avec_mel_frames(const float* audio, const float* window, float* frames, int B, long long L, int n_fft, int win, int hop, hipStream_t stream);
