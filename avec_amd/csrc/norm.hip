@@ -6,6 +6,7 @@
 #include "avec_hip.h"
 
 #include "vec.h"
+#include <type_traits>
 
 // second pass of the two-pass column reductions (vec.h): dst[n][colblock*W + w] += sum over slots of partial[colblock][slot][n][w]
 __global__ __launch_bounds__(256) void col_finalize_kernel(ColFin f) {
@@ -615,6 +616,239 @@ constexpr int BN8_UR = AVEC_BN8_UR;       // ... in the reduction pass (2 measur
 constexpr unsigned BN8_CAP_FWD = 8192, BN8_CAP_BWD = 3072;      // grid caps: the 3-operand backward pass likes fewer, longer-running blocks (115200 x 256: 41.5 -> 36.7 us,
                                                                 // 28800 x 512: 28.0 -> 21.9 us), the forward pass the opposite (32.9 vs 33.9 us); tools/bench_bn.py
 
+// ---- slice-streaming skeleton of the three 8-wide passes (bf16, 256 % (C/8) == 0, < 2^31 chunks) -------------------------------------------------------
+// Every workgroup owns ONE contiguous range of 16-byte chunks (`slice`, a multiple of 256 chunks and so of C/8: a thread keeps its eight channels) and walks it in
+// units of 256 threads x P pieces.  All P loads of every input stream of a unit are issued before the first use, and the next unit's loads go out before the
+// current unit's arithmetic (two register sets) -- the access shape at which tools/ubench_hbm_stream.hip (mode 2) reads at 6.1-6.2 TB/s.  A unit that crosses the
+// slice end is guarded per piece: nothing at or beyond `end` (<= n8) is loaded or stored, the loads issued ahead included.
+// The arithmetic is that of the grid-stride kernels with every a * b + c written as the fused multiply-add the compiler contracts it to there: with the product
+// and the sum of one expression in different basic blocks it leaves some unfused, and the apply passes would no longer be bit-identical.
+// What the sweeps of tools/bench_bn.py made of it (profiles/bn_slice_notes.txt): the apply passes want SHORT slices -- one unit (forward) or one and a half
+// (backward) per workgroup and as many workgroups as that takes -- so what wins there, 4-19 % per launch, is four pieces per stream in flight per thread, the
+// contiguous range and non-temporal loads, not the two-set pipeline; the reduction keeps long slices (every workgroup costs a workspace row and a share of
+// col_finalize) and only its bit-mask variant beat bn_bwd_reduce8_kernel (5-11 %).
+// AVEC_BN_SLICE=0: the grid-stride kernels everywhere (A/B runs, tests); they stay for fp32, other channel counts, >= 2^31 chunks, tensors below the size
+// threshold and the reductions that read `out` or recompute the pre-activation.
+constexpr int BNS_P = 4;                              // pieces per thread and unit (2: no better anywhere, worse in the reduction)
+constexpr unsigned BNS_SLICE_FWD = 1024, BNS_SLICE_BWD = 1536;      // chunks per workgroup of the apply passes: short slices and many workgroups won every sweep (bn_slice_notes.txt)
+constexpr unsigned BNS_GRID_RED = 2048, BNS_RED_MIN_UNITS = 4;      // reduction: every workgroup costs a workspace row and a share of col_finalize -- at most 2048 of them, each
+                                                                    // with at least 4 units, never fewer than 256
+constexpr long long BNS_MIN_CHUNKS = 1ll << 20;       // smaller tensors keep the grid-stride kernels (the smallest ResNet stage of the B = 32 step, 1.8 M chunks, is the
+                                                      // smallest size measured)
+// 0: the grid-stride kernels; 1 (default): the slice kernels from BNS_MIN_CHUNKS up; 2: the slice kernels at every eligible size (tests: the edges of the range
+// guard show at sizes below the threshold).  Read from AVEC_BN_SLICE once; avec_bn_slice_mode() below changes it in-process.
+static int& bns_mode() { static int mode = getenv("AVEC_BN_SLICE") ? atoi(getenv("AVEC_BN_SLICE")) : 1; return mode; }
+static inline bool bns_ok(int dtype, long long M, int C) {
+  const int mode = bns_mode();
+  if (mode == 0 || dtype != AVEC_BF16 || C % 8 != 0 || 256 % (C / 8) != 0) return false;
+  const long long n8 = M * C / 8;
+  return n8 < (1ll << 31) && (mode == 2 || n8 >= BNS_MIN_CHUNKS);
+}
+// 16 bytes of an operand; NT: non-temporal, for what no kernel reads again soon (the apply passes: 5-10 % in the forward pass, bn_slice_notes.txt)
+template <bool NT> __device__ __forceinline__ void bns_ld(Raw8<bf16>& r, const bf16* p) {
+  if (NT) { typedef unsigned v4u __attribute__((ext_vector_type(4))); const v4u t = __builtin_nontemporal_load((const v4u*)p); r.t = make_uint4(t.x, t.y, t.z, t.w); }
+  else r.load(p);
+}
+static inline unsigned bns_slice(long long n8, unsigned grid) { return (unsigned)(((n8 + grid - 1) / grid + 255) / 256 * 256); }      // chunks per workgroup of a given grid
+static inline unsigned bns_grid(long long n8, unsigned slice) { return (unsigned)((n8 + slice - 1) / slice); }                        // workgroups of a given slice
+static inline unsigned bns_red_grid(long long n8) {
+  long long g = n8 / (256ll * BNS_P * BNS_RED_MIN_UNITS) / 256 * 256; if (g > BNS_GRID_RED) g = BNS_GRID_RED; if (g < 256) g = 256;
+  return (unsigned)g;
+}
+template <int P, typename Set, typename Load, typename Use>
+__device__ __forceinline__ void bns_walk(unsigned begin, unsigned end, Load load, Use use) {
+  constexpr unsigned UNIT = 256 * P;
+  constexpr std::true_type full{}; constexpr std::false_type ragged{};
+  if (begin >= end) return;
+  Set a, b;
+  unsigned base = begin;
+  load(a, base, ragged);
+  // steady state, whole units only: no branch around a load, so the waits before a use are counted and leave the loads issued after it in flight (a load under a
+  // condition makes the compiler wait for everything, the loads issued ahead included)
+  while (end - base >= 3 * UNIT) {
+    load(b, base + UNIT, full); use(a, base, full);
+    load(a, base + 2 * UNIT, full); use(b, base + UNIT, full);
+    base += 2 * UNIT;
+  }
+  // at most three units are left, the last of them possibly ragged; `a` holds the first
+  if (end - base > UNIT) {
+    load(b, base + UNIT, ragged); use(a, base, full);
+    if (end - base > 2 * UNIT) { load(a, base + 2 * UNIT, ragged); use(b, base + UNIT, full); use(a, base + 2 * UNIT, ragged); }
+    else use(b, base + UNIT, ragged);
+  } else use(a, base, ragged);
+}
+// the chunk of piece p of the unit at `base`; in a ragged unit a piece at or beyond `end` loads the slice's last chunk instead (in range, never used): the loads
+// stay unconditional
+template <bool FULL> __device__ __forceinline__ unsigned bns_chunk(unsigned base, int p, unsigned end) {
+  const unsigned j = base + threadIdx.x + p * 256; return FULL || j < end ? j : end - 1;
+}
+// this workgroup's [begin, end) in chunks
+__device__ __forceinline__ void bns_range(unsigned slice, unsigned n8, unsigned& begin, unsigned& end) {
+  const unsigned long long b = (unsigned long long)blockIdx.x * slice;
+  begin = b < n8 ? (unsigned)b : n8; end = n8 - begin > slice ? begin + slice : n8;
+}
+
+template <int P, bool RES> struct BnsFwdSet { Raw8<bf16> y[P], r[RES ? P : 1]; };
+template <int P, bool RES, bool MASK>
+__global__ __launch_bounds__(256) void bn_apply8s_kernel(const bf16* __restrict__ y, const float* __restrict__ ss, const bf16* __restrict__ res, int act,
+                                                         bf16* __restrict__ out, unsigned n8, int C, unsigned slice, unsigned char* __restrict__ mask,
+                                                         const float* __restrict__ res_ss) {
+  unsigned begin, end; bns_range(slice, n8, begin, end);
+  const int c = (int)(threadIdx.x % ((unsigned)C >> 3)) * 8;
+  float sc[8], sh[8]; ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh);
+  float rsc[8], rsh[8];
+  if (RES && res_ss) { ld8<float>(res_ss + c, rsc); ld8<float>(res_ss + C + c, rsh);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sh[e] += rsh[e]; }
+  typedef BnsFwdSet<P, RES> Set;
+  auto load = [&](Set& s, unsigned base, auto full) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) { const long long off = (long long)bns_chunk<decltype(full)::value>(base, p, end) * 8; bns_ld<true>(s.y[p], y + off); if (RES) bns_ld<true>(s.r[p], res + off); }
+  };
+  auto use = [&](Set& s, unsigned base, auto full) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const unsigned j = base + threadIdx.x + p * 256; if (!decltype(full)::value && j >= end) break;
+      float v[8]; s.y[p].get(v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(v[e], sc[e], sh[e]);
+      if (RES) { float r[8]; s.r[p].get(r);
+        if (res_ss) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(r[e], rsc[e], v[e]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] += r[e]; } }
+      if (act == 1) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = swishf_(v[e]);
+      } else if (act == 2) {
+        if (MASK) {
+          unsigned b = 0;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) b |= (v[e] > 0.f ? 1u : 0u) << e;
+          mask[j] = (unsigned char)b;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+      }
+      st8<bf16>(out + (long long)j * 8, v);
+    }
+  };
+  bns_walk<P, Set>(begin, end, load, use);
+}
+template <bool MASK>
+static int bns_apply_fwd(const void* y, const float* ss, const void* residual, const float* residual_ss, int act, void* out, unsigned char* mask, long long n8, int C,
+                         hipStream_t st) {
+  const unsigned grid = bns_grid(n8, BNS_SLICE_FWD);
+  if (residual) hipLaunchKernelGGL((bn_apply8s_kernel<BNS_P, true, MASK>), dim3(grid), dim3(256), 0, st, (const bf16*)y, ss, (const bf16*)residual, act, (bf16*)out,
+                                   (unsigned)n8, C, BNS_SLICE_FWD, mask, residual_ss);
+  else hipLaunchKernelGGL((bn_apply8s_kernel<BNS_P, false, MASK>), dim3(grid), dim3(256), 0, st, (const bf16*)y, ss, (const bf16*)nullptr, act, (bf16*)out,
+                          (unsigned)n8, C, BNS_SLICE_FWD, mask, (const float*)nullptr);
+  AVEC_LAUNCH_CHECK(); return 0;
+}
+
+// third operand of the backward passes: BNS_NONE = none (no activation, or the pre-activation is recomputed from y), BNS_OUT = the saved output, BNS_BITS = the bit mask
+enum { BNS_NONE = 0, BNS_OUT = 1, BNS_BITS = 2 };
+template <int P, int SRC> struct BnsBwdSet { Raw8<bf16> d[P], v[P], o[SRC == BNS_OUT ? P : 1]; unsigned mb[SRC == BNS_BITS ? P : 1]; };
+template <bool FULL, bool NT, int P, int SRC>
+__device__ __forceinline__ void bns_bwd_load(BnsBwdSet<P, SRC>& s, unsigned base, unsigned end, const bf16* __restrict__ dout, const bf16* __restrict__ y,
+                                             const bf16* __restrict__ out, const unsigned char* __restrict__ mask) {
+#pragma unroll
+  for (int p = 0; p < P; ++p) { const unsigned j = bns_chunk<FULL>(base, p, end); const long long off = (long long)j * 8; bns_ld<NT>(s.d[p], dout + off); bns_ld<NT>(s.v[p], y + off);
+    if (SRC == BNS_BITS) s.mb[p] = mask[j]; else if (SRC == BNS_OUT) bns_ld<NT>(s.o[p], out + off); }
+}
+// d = dout * act'(.) of piece p, v = y
+template <int P, int SRC>
+__device__ __forceinline__ void bns_bwd_dr(const BnsBwdSet<P, SRC>& s, int p, int act, const float (&sc)[8], const float (&sh)[8], float (&d)[8], float (&v)[8]) {
+  s.d[p].get(d); s.v[p].get(v);
+  if (SRC == BNS_BITS) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d[e] = (s.mb[p] >> e) & 1u ? d[e] : 0.f;
+  } else if (SRC == BNS_OUT) { float q[8]; s.o[p].get(q);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d[e] = q[e] > 0.f ? d[e] : 0.f;
+  } else if (act == 2) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d[e] = __builtin_fmaf(v[e], sc[e], sh[e]) > 0.f ? d[e] : 0.f;
+  } else if (act == 1) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float x = __builtin_fmaf(v[e], sc[e], sh[e]), sg = sigmoidf_(x); d[e] *= sg * __builtin_fmaf(x, 1.f - sg, 1.f); }      // dswishf_
+  }
+}
+template <int P, int SRC>
+__global__ __launch_bounds__(256) void bn_bwd_reduce8s_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ y, const bf16* __restrict__ out, const float* __restrict__ ss,
+                                                              int act, float* dstats, unsigned n8, int C, unsigned slice, ColWs ws, const unsigned char* __restrict__ mask) {
+  unsigned begin, end; bns_range(slice, n8, begin, end);
+  const Col8 m = col8_map(C);                    // 256 % (C/8) == 0: every thread is active and m.l is its lane for the whole slice
+  const int c = m.l * 8;
+  float part[2][8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) part[0][e] = part[1][e] = 0.f;
+  float mu[8], rs[8], sc[8], sh[8]; ld8<float>(ss + 2 * C + c, mu); ld8<float>(ss + 3 * C + c, rs);
+  if (SRC == BNS_NONE && act != 0) { ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh); }
+  typedef BnsBwdSet<P, SRC> Set;
+  auto load = [&](Set& s, unsigned base, auto full) { bns_bwd_load<decltype(full)::value, false, P, SRC>(s, base, end, dout, y, out, mask); };
+  auto use = [&](Set& s, unsigned base, auto full) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      if (!decltype(full)::value && base + threadIdx.x + p * 256 >= end) break;
+      float d[8], v[8]; bns_bwd_dr<P, SRC>(s, p, act, sc, sh, d, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { part[0][e] += d[e]; part[1][e] += d[e] * (v[e] - mu[e]) * rs[e]; }
+    }
+  };
+  bns_walk<P, Set>(begin, end, load, use);
+  float* const dst[2] = {dstats, dstats + C};
+  colreduce8_atomic<2>(part, dst, m, ws);
+}
+// the bit-mask variant only: with `out` or a recomputed pre-activation the slice form measured 0-6 % slower than bn_bwd_reduce8_kernel at every stage
+static int bns_bwd_reduce_mask(const void* dout, const void* y, const unsigned char* mask, const float* ss, float* dstats, long long n8, int C, hipStream_t st) {
+  const ColPlan plan = ColPlan::flat<2>(bns_red_grid(n8), C, st).cap_without_ws(256);
+  hipLaunchKernelGGL((bn_bwd_reduce8s_kernel<BNS_P, BNS_BITS>), dim3(plan.nslots), dim3(256), 0, st, (const bf16*)dout, (const bf16*)y, (const bf16*)nullptr, ss, 2,
+                     dstats, (unsigned)n8, C, bns_slice(n8, plan.nslots), plan.ws, mask);
+  AVEC_LAUNCH_CHECK();
+  return plan.finish({dstats, dstats + C}, C, st);
+}
+template <int P, int SRC>
+__global__ __launch_bounds__(256) void bn_bwd_apply8s_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ y, const bf16* __restrict__ out, const float* __restrict__ ss,
+                                                             const float* __restrict__ gamma, const float* __restrict__ dstats, const float* count_ptr, float count, int act,
+                                                             bf16* __restrict__ dy, bf16* __restrict__ dres, float* dgamma, float* dbeta, unsigned n8, int C, unsigned slice,
+                                                             const unsigned char* __restrict__ mask) {
+  const float inv_n = 1.f / (count_ptr ? *count_ptr : count);
+  if (blockIdx.x == 0 && dgamma) for (int cc = threadIdx.x; cc < C; cc += 256) { atomicAdd(dgamma + cc, dstats[C + cc]); atomicAdd(dbeta + cc, dstats[cc]); }
+  unsigned begin, end; bns_range(slice, n8, begin, end);
+  const int c = (int)(threadIdx.x % ((unsigned)C >> 3)) * 8;
+  float mu[8], rs[8], A[8], m1[8], m2[8], sc[8], sh[8];
+  { float g[8], s1[8], s2[8]; ld8<float>(ss + 2 * C + c, mu); ld8<float>(ss + 3 * C + c, rs); ld8<float>(gamma + c, g); ld8<float>(dstats + c, s1); ld8<float>(dstats + C + c, s2);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { A[e] = g[e] * rs[e]; m1[e] = s1[e] * inv_n; m2[e] = s2[e] * inv_n; } }
+  if (SRC == BNS_NONE && act != 0) { ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh); }
+  typedef BnsBwdSet<P, SRC> Set;
+  auto load = [&](Set& s, unsigned base, auto full) { bns_bwd_load<decltype(full)::value, true, P, SRC>(s, base, end, dout, y, out, mask); };
+  auto use = [&](Set& s, unsigned base, auto full) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const unsigned j = base + threadIdx.x + p * 256; if (!decltype(full)::value && j >= end) break;
+      const long long off = (long long)j * 8;
+      float d[8], v[8], o[8]; bns_bwd_dr<P, SRC>(s, p, act, sc, sh, d, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = A[e] * __builtin_fmaf(-((v[e] - mu[e]) * rs[e]), m2[e], d[e] - m1[e]);
+      st8<bf16>(dy + off, o);
+      if (dres) st8<bf16>(dres + off, d);
+    }
+  };
+  bns_walk<P, Set>(begin, end, load, use);
+}
+static int bns_bwd_apply(const void* dout, const void* y, const void* out, const unsigned char* mask, const float* ss, const float* gamma, const float* dstats,
+                         const float* count_ptr, float count, int act, void* dy, void* dres, float* dgamma, float* dbeta, long long n8, int C, hipStream_t st) {
+#define BNS_BWD(SRC) hipLaunchKernelGGL((bn_bwd_apply8s_kernel<BNS_P, SRC>), dim3(bns_grid(n8, BNS_SLICE_BWD)), dim3(256), 0, st, (const bf16*)dout, (const bf16*)y, (const bf16*)out, ss, gamma, dstats, \
+                                        count_ptr, count, act, (bf16*)dy, (bf16*)dres, dgamma, dbeta, (unsigned)n8, C, BNS_SLICE_BWD, mask)
+  if (mask) BNS_BWD(BNS_BITS); else if (act == 2 && out) BNS_BWD(BNS_OUT); else BNS_BWD(BNS_NONE);
+#undef BNS_BWD
+  AVEC_LAUNCH_CHECK(); return 0;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_apply8_kernel(const T* __restrict__ y, const float* __restrict__ ss, const T* __restrict__ res, int act,
                                                         T* __restrict__ out, unsigned n8, int C, unsigned char* __restrict__ mask = nullptr,
@@ -663,12 +897,14 @@ __global__ __launch_bounds__(256) void bn_apply8_kernel(const T* __restrict__ y,
 extern "C" int avec_bn_apply_fwd_mask(int dtype, const void* y, const float* ss, const void* residual, const float* residual_ss, void* out, unsigned char* mask, long long M, int C,
                                       hipStream_t st) {
   AVEC_CHECK_ARG(y && ss && out && mask && M > 0 && C > 0 && C % 8 == 0 && M * C / 8 < (1ll << 31) && (residual || !residual_ss), "bn_apply_fwd_mask: bad arguments (C %% 8 == 0, M*C < 2^34)");
+  if (bns_ok(dtype, M, C)) return bns_apply_fwd<true>(y, ss, residual, residual_ss, 2, out, mask, M * C / 8, C, st);
   const long long n8 = M * C / 8; const unsigned nb8 = bn8_blocks(n8, C, BN8_CAP_FWD);
   DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply8_kernel<T>, dim3((unsigned)nb8), dim3(256), 0, st, (const T*)y, ss, (const T*)residual, 2, (T*)out, (unsigned)n8, C, mask, residual_ss));
   AVEC_LAUNCH_CHECK(); return 0;
 }
 extern "C" int avec_bn_apply_fwd(int dtype, const void* y, const float* ss, const void* residual, int act, void* out, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(y && ss && out && M > 0 && C > 0 && C % 4 == 0, "bn_apply_fwd: bad arguments");
+  if (bns_ok(dtype, M, C)) return bns_apply_fwd<false>(y, ss, residual, nullptr, act, out, nullptr, M * C / 8, C, st);
   if (C % 8 == 0 && M * C / 8 < (1ll << 31)) {
     const long long n8 = M * C / 8; const unsigned nb8 = bn8_blocks(n8, C, BN8_CAP_FWD);
     DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply8_kernel<T>, dim3((unsigned)nb8), dim3(256), 0, st, (const T*)y, ss, (const T*)residual, act, (T*)out, (unsigned)n8, C));
@@ -747,6 +983,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce8_kernel(const T* __restrict
 }
 extern "C" int avec_bn_bwd_reduce_mask(int dtype, const void* dout, const void* y, const unsigned char* mask, const float* ss, float* dstats, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(dout && y && mask && ss && dstats && M > 0 && col8_ok(C), "bn_bwd_reduce_mask: bad arguments");
+  if (bns_ok(dtype, M, C)) return bns_bwd_reduce_mask(dout, y, mask, ss, dstats, M * C / 8, C, st);
   const ColPlan plan = ColPlan::flat8<2>(M, C, st);
   DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce8_kernel<T>, dim3(plan.nslots), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)nullptr, ss, 2, dstats, M, C, plan.ws, mask));
   AVEC_LAUNCH_CHECK();
@@ -828,6 +1065,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply8_kernel(const T* __restrict_
 extern "C" int avec_bn_bwd_apply_mask(int dtype, const void* dout, const void* y, const unsigned char* mask, const float* ss, const float* gamma, const float* dstats,
                                       const float* count_ptr, float count, void* dy, void* dres, float* dgamma, float* dbeta, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(dout && y && mask && ss && gamma && dstats && dy && M > 0 && C % 8 == 0 && M * C / 8 < (1ll << 31), "bn_bwd_apply_mask: bad arguments");
+  if (bns_ok(dtype, M, C)) return bns_bwd_apply(dout, y, nullptr, mask, ss, gamma, dstats, count_ptr, count, 2, dy, dres, dgamma, dbeta, M * C / 8, C, st);
   const long long n8 = M * C / 8; const unsigned nb8 = bn8_blocks(n8, C, BN8_CAP_BWD);
   DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply8_kernel<T>, dim3((unsigned)nb8), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)nullptr, ss, gamma, dstats,
                                        count_ptr, count, 2, (T*)dy, (T*)dres, dgamma, dbeta, (unsigned)n8, C, mask));
@@ -836,6 +1074,7 @@ extern "C" int avec_bn_bwd_apply_mask(int dtype, const void* dout, const void* y
 extern "C" int avec_bn_bwd_apply(int dtype, const void* dout, const void* y, const void* out, const float* ss, const float* gamma, const float* dstats,
                                  const float* count_ptr, float count, int act, void* dy, void* dres, float* dgamma, float* dbeta, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(dout && y && ss && gamma && dstats && dy && M > 0 && C % 4 == 0, "bn_bwd_apply: bad arguments");
+  if (bns_ok(dtype, M, C)) return bns_bwd_apply(dout, y, out, nullptr, ss, gamma, dstats, count_ptr, count, act, dy, dres, dgamma, dbeta, M * C / 8, C, st);
   if (C % 8 == 0 && M * C / 8 < (1ll << 31)) {
     const long long n8 = M * C / 8; const unsigned nb8 = bn8_blocks(n8, C, BN8_CAP_BWD);
     DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply8_kernel<T>, dim3((unsigned)nb8), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, gamma, dstats,
@@ -846,6 +1085,21 @@ extern "C" int avec_bn_bwd_apply(int dtype, const void* dout, const void* y, con
   DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, gamma, dstats,
                                        count_ptr, count, act, (T*)dy, (T*)dres, dgamma, dbeta, n4, C));
   AVEC_LAUNCH_CHECK(); return 0;
+}
+// what the slice-streaming path does with an (M, C) bf16 tensor, for tests and tools: pass 0 = forward apply, 1 = backward reduce by the bit mask, 2 = backward apply.
+// Returns 1 when such a launch takes the slice path (0: the grid-stride kernels) and stores the pieces per thread and unit, the workgroups and the chunks per
+// workgroup (backward reduce: with the reduction workspace bound to `st`, as avec_bn_bwd_reduce_mask sees it).
+extern "C" int avec_bn_slice_mode(int mode) { const int old = bns_mode(); if (mode >= 0 && mode <= 2) bns_mode() = mode; return old; }      // the AVEC_BN_SLICE value in force; mode < 0 only reads it
+extern "C" int avec_bn_slice_plan(int pass, long long M, int C, int* P, unsigned* grid, unsigned* slice, hipStream_t st) {
+  if (P) *P = BNS_P;
+  if (M <= 0 || C <= 0 || C % 8 != 0 || pass < 0 || pass > 2 || !bns_ok(AVEC_BF16, M, C)) return 0;
+  const long long n8 = M * C / 8;
+  unsigned g, sl;
+  if (pass == 1) { g = ColPlan::flat<2>(bns_red_grid(n8), C, st).cap_without_ws(256).nslots; sl = bns_slice(n8, g); }
+  else { sl = pass == 0 ? BNS_SLICE_FWD : BNS_SLICE_BWD; g = bns_grid(n8, sl); }
+  if (grid) *grid = g;
+  if (slice) *slice = sl;
+  return 1;
 }
 
 // =============================================================================================
