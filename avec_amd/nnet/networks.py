@@ -7,7 +7,7 @@ import torch.nn as nn
 from .. import ops
 from .. import runtime as rt
 from . import attentions, blocks, layers, modules, preprocessing, transforms
-from .streaming import AudioFrontStreamSession, AudioStreamSession, ConformerStreamSession, VisualFrontStreamSession, VisualStreamSession
+from .streaming import AudioFrontStreamSession, AudioStreamSession, AudioVisualStreamSession, ConformerStreamSession, VisualFrontStreamSession, VisualStreamSession
 
 
 class ResNet(nn.Module):
@@ -350,3 +350,8 @@ class AudioVisualEfficientConformerEncoder(nn.Module):
         if not isinstance(self.head, nn.Identity):
             x = self.head(x)
         return x, lengths, inter
+
+    def stream(self, batch_size, chunk_frames):
+        """An AudioVisualStreamSession: video and waveform chunks -> logits; chunk_frames in video frames (the audio branch runs at twice as many stem frames).  Both
+        branch sessions, the row pairing of ops.av_fuse_stream, the fusion module, audio_visual_encoder.stream() and the head (the refusals are the sub-sessions')."""
+        return AudioVisualStreamSession(self, batch_size, chunk_frames)

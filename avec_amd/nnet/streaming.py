@@ -1,7 +1,7 @@
-"""Streaming sessions: a causal Conformer stack, the audio and the visual front-end and the CTC beam search run chunk by chunk over a fixed number of utterance slots.
-None of them has a counterpart in the reference; the factories (ConformerInterCTC.stream, AudioEfficientConformerEncoder.stream_front / .stream,
-VisualEfficientConformerEncoder.stream_front / .stream, CTCBeamSearchDecoder.stream) stay with the classes they wrap.  A session owns its device state; nothing is
-added to a module tree or a state_dict."""
+"""Streaming sessions: a causal Conformer stack, the audio and the visual front-end, the audio-visual encoder and the CTC beam search run chunk by chunk over a fixed number
+of utterance slots.  None of them has a counterpart in the reference; the factories (ConformerInterCTC.stream, AudioEfficientConformerEncoder.stream_front / .stream,
+VisualEfficientConformerEncoder.stream_front / .stream, AudioVisualEfficientConformerEncoder.stream, CTCBeamSearchDecoder.stream) stay with the classes they wrap.
+A session owns its device state; nothing is added to a module tree or a state_dict."""
 import torch
 import torch.nn as nn
 
@@ -11,7 +11,7 @@ from . import attentions, normalizations
 from .captured import CapturedStep
 
 __all__ = ["slot_mask", "ConformerStreamSession", "AudioFrontStreamSession", "AudioStreamSession", "VisualFrontStreamSession", "VisualStreamSession",
-           "CTCBeamStreamSession"]
+           "AudioVisualStreamSession", "CTCBeamStreamSession"]
 
 
 def slot_mask(flags, B):
@@ -450,18 +450,24 @@ class AudioStreamSession:
     def _head(self, y):
         return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
 
+    def _plan(self, n_samples, last, reset):
+        """the host side of a push, before anything is launched: the front's controls (reset mask, last mask, counts, frames per slot), checked against the schedule"""
+        if torch.is_tensor(n_samples):
+            raise TypeError("push: the combined session takes host lists for n_samples (it decides on the host whether the stack needs a second push)")
+        Tc = self.Tc
+        rmask, lmask, counts, frames = self.front._controls(n_samples, last, reset)
+        for b in range(self.B):
+            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 1)):
+                raise ValueError("push: slot %d would yield %d frames from %d samples: off the schedule (first_samples = %d in an utterance's first push, chunk_samples = %d "
+                                 "later, fewer only with last)" % (b, frames[b], counts[b], self.first_samples, self.chunk_samples))
+        return rmask, lmask, counts, frames
+
     def push(self, wave, n_samples=None, last=None, reset=None):
         """wave [B, first_samples] fp32 -> (logits [B, R, V] fp32, out_len [B] int64 on the device, inter: loss_prefix_i -> [logits chunk, lengths] as offline).
         n_samples / last / reset: host lists as AudioFrontStreamSession.push; counts must follow the schedule (every push of a slot but its last yields exactly
         chunk_frames frames; a slot may idle on 0 samples).  R = Tc / S, or Tc / S + 1 in a push where some slot's last chunk produced Tc + 1 frames."""
-        if torch.is_tensor(n_samples):
-            raise TypeError("push: the combined session takes host lists for n_samples (it decides on the host whether the stack needs a second push)")
         B, Tc = self.B, self.Tc
-        rmask, lmask, counts, frames = self.front._controls(n_samples, last, reset)
-        for b in range(B):
-            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 1)):
-                raise ValueError("push: slot %d would yield %d frames from %d samples: off the schedule (first_samples = %d in an utterance's first push, chunk_samples = %d "
-                                 "later, fewer only with last)" % (b, frames[b], counts[b], self.first_samples, self.chunk_samples))
+        rmask, lmask, counts, frames = self._plan(n_samples, last, reset)
         with torch.no_grad():
             feat, _ = self.front.push(wave, counts, lmask, rmask)
             tail = [f > Tc for f in frames]
@@ -662,19 +668,25 @@ class VisualStreamSession:
     def _head(self, y):
         return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
 
+    def _plan(self, n_frames, last, reset):
+        """the host side of a push, before anything is launched: the front's controls (reset mask, last mask, counts, frames per slot), checked against the schedule"""
+        if torch.is_tensor(n_frames):
+            raise TypeError("push: the combined session takes host lists for n_frames (it decides on the host whether the stack needs a second push)")
+        Tc = self.Tc
+        rmask, lmask, counts, frames = self.front._controls(n_frames, last, reset)
+        for b in range(self.B):
+            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 2)):
+                raise ValueError("push: slot %d would yield %d frames from %d: off the schedule (first_frames = %d in an utterance's first push, chunk_frames = %d later, "
+                                 "fewer only with last)" % (b, frames[b], counts[b], self.first_frames, self.chunk_frames))
+        return rmask, lmask, counts, frames
+
     def push(self, video, n_frames=None, last=None, reset=None):
         """video [B, Tc + 2, H, W] fp32 -> (logits [B, R, V] fp32, out_len [B] int64 on the device, inter: loss_prefix_i -> [logits chunk, lengths] as offline).
         n_frames / last / reset: host lists as VisualFrontStreamSession.push; counts must follow the schedule (every push of a slot but its last yields exactly
         chunk_frames frames; a slot may idle on 0 frames).  R = Tc / S, or Tc / S + ceil(tail / S) in a push where some slot's last chunk left a tail of 1 or 2
         frames beyond Tc (one more row for every S >= 2)."""
-        if torch.is_tensor(n_frames):
-            raise TypeError("push: the combined session takes host lists for n_frames (it decides on the host whether the stack needs a second push)")
         B, Tc, S = self.B, self.Tc, self.S
-        rmask, lmask, counts, frames = self.front._controls(n_frames, last, reset)
-        for b in range(B):
-            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 2)):
-                raise ValueError("push: slot %d would yield %d frames from %d: off the schedule (first_frames = %d in an utterance's first push, chunk_frames = %d later, "
-                                 "fewer only with last)" % (b, frames[b], counts[b], self.first_frames, self.chunk_frames))
+        rmask, lmask, counts, frames = self._plan(n_frames, last, reset)
         with torch.no_grad():
             feat, _ = self.front.push(video, counts, lmask, rmask)
             tail = [max(0, f - Tc) for f in frames]
@@ -695,6 +707,159 @@ class VisualStreamSession:
     def capture(self, device=None, frame=(88, 88)):
         """capture both halves (VisualFrontStreamSession.capture, ConformerStreamSession.capture); call it before the first push"""
         self.front.capture(device, frame)
+        self.back.capture(device)
+        return self
+
+
+class AudioVisualStreamSession(_StreamSession):
+    """AudioVisualEfficientConformerEncoder.stream(): video and waveform chunks -> logits.  video_encoder.stream(B, Tv) and audio_encoder.stream(B, 2 Tv) (both built
+    without a head: they return their stacks' rows, with their refusals) feed ops.av_fuse_stream, the fusion module's two Linears, audio_visual_encoder.stream(B, R)
+    and the head; R = Tv / S_v = 2 Tv / S_a rows per regular push.  An utterance of T video frames has 640 T - 160 samples and both branches yield ceil(T / 2) rows at
+    the 80 ms rate, but not in the same pushes: the audio front-end looks 40 samples ahead and the video stem 2 frames, so for T mod Tv in {1, 2} the video branch ends
+    one push before the audio branch and is, for one push, one row ahead.  The fuse launch keeps the unpaired rows per slot in two rings of cap = R + 2 rows and emits
+    at most R pairs; where some slot still has a pair pending (an utterance's last push can bring R + 1 rows), a second fuse launch without new rows and a second
+    stack push follow and their rows are appended, as in the two branch sessions.  The host mirrors the rings' counters (rows pending per branch, rows since the
+    restart, `ended` per branch): ring overflow and branches whose row totals differ at the end of an utterance are refused before anything is launched."""
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        super().__init__(batch_size)
+        self.enc, self.Tv = enc, int(chunk_frames)
+        if enc.training:
+            raise RuntimeError("stream: the encoder is in training mode (BatchNorm batch statistics, SpecAugment and dropout are not functions of the past): call .eval() first")
+        self.video = enc.video_encoder.stream(batch_size, self.Tv)
+        self.audio = enc.audio_encoder.stream(batch_size, 2 * self.Tv)
+        if self.Tv % self.video.S or 2 * self.Tv % self.audio.S or self.Tv // self.video.S != 2 * self.Tv // self.audio.S:
+            raise ValueError("stream: chunk_frames = %d gives %g rows per push behind the video stack (stride %d) and %g behind the audio stack (stride %d, %d stem frames): "
+                             "the two branches must yield the same whole number of rows" % (self.Tv, self.Tv / self.video.S, self.video.S, 2 * self.Tv / self.audio.S,
+                                                                                                self.audio.S, 2 * self.Tv))
+        self.R = self.Tv // self.video.S
+        self.cap = self.R + 2
+        self.back = enc.audio_visual_encoder.stream(batch_size, self.R)
+        self.first_frames, self.chunk_frames = self.video.first_frames, self.video.chunk_frames
+        self.first_samples, self.chunk_samples = self.audio.first_samples, self.audio.chunk_samples
+        self._forget()
+
+    def _forget(self):
+        B = self.B
+        self._pend_a, self._pend_v = [0] * B, [0] * B          # host mirrors: rows received and not yet paired, per branch
+        self._rows_a, self._rows_v = [0] * B, [0] * B          # rows received since the restart
+        self._end_a, self._end_v = [False] * B, [False] * B
+
+    def _head(self, y):
+        return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
+
+    def schedule(self, n_video_frames, n_audio_samples):
+        """-> per push (n_frames, n_samples, last_video, last_audio) for one utterance on both branch sessions' schedules: first_frames / first_samples in the first
+        push, chunk_frames / chunk_samples later, the rest in each branch's last; a branch that has ended idles on 0"""
+        T, Ta = int(n_video_frames), int(n_audio_samples)
+        if T < 1 or Ta < 1:
+            raise ValueError("schedule: an utterance of %d frames and %d samples" % (T, Ta))
+        v, a = [], []
+        while sum(v) < T:
+            v.append(min(T - sum(v), self.chunk_frames if v else self.first_frames))
+        while sum(a) < Ta:
+            a.append(min(Ta - sum(a), self.chunk_samples if a else self.first_samples))
+        return [(v[i] if i < len(v) else 0, a[i] if i < len(a) else 0, i == len(v) - 1, i == len(a) - 1) for i in range(max(len(v), len(a)))]
+
+    @staticmethod
+    def _rows(frames, Tc, S):
+        """rows a branch session returns for `frames` front-end frames: the chunk of the stack's first push and the tail of its second, each rounded up"""
+        return -(-min(frames, Tc) // S) + -(-max(0, frames - Tc) // S)
+
+    def _plan(self, n_frames, n_samples, last_video, last_audio, reset):
+        """the host side of a push, before anything is launched: both branches' controls, the mirrors after the push and the pairs of every fuse launch"""
+        B, R = self.B, self.R
+        rmask = self._reset_mask(reset) or [False] * B
+        vplan = self.video._plan(n_frames, last_video, rmask)
+        aplan = self.audio._plan(n_samples, last_audio, rmask)
+        pend_a, pend_v, rows_a, rows_v, end_a, end_v = [], [], [], [], [], []
+        for b in range(B):
+            pa, pv, ta, tv, ea, ev = (0, 0, 0, 0, False, False) if rmask[b] else (self._pend_a[b], self._pend_v[b], self._rows_a[b], self._rows_v[b], self._end_a[b], self._end_v[b])
+            na, nv = self._rows(aplan[3][b], 2 * self.Tv, self.audio.S), self._rows(vplan[3][b], self.Tv, self.video.S)
+            if pa + na > self.cap or pv + nv > self.cap:
+                raise RuntimeError("push: slot %d would hold %d audio and %d video rows that are not paired yet: the rings keep %d (one branch ran ahead of the other; "
+                                   "both must follow one utterance's schedule)" % (b, pa + na, pv + nv, self.cap))
+            ends = (aplan[1][b] and not ea) or (vplan[1][b] and not ev)
+            ea, ev = ea or aplan[1][b], ev or vplan[1][b]
+            if ends and ea and ev and ta + na != tv + nv:
+                raise ValueError("push: slot %d ends its utterance with %d audio rows and %d video rows: the branches must yield the same number (the offline forward fails "
+                                 "in cat); T video frames go with 640 T - 160 samples" % (b, ta + na, tv + nv))
+            pend_a.append(pa + na), pend_v.append(pv + nv), rows_a.append(ta + na), rows_v.append(tv + nv), end_a.append(ea), end_v.append(ev)
+        launches = []                                          # pairs per slot of every fuse launch: the first always runs, further ones while a pair is pending
+        while True:
+            m = [min(pend_a[b], pend_v[b], R) for b in range(B)]
+            if launches and not any(m):
+                break
+            launches.append(m)
+            pend_a, pend_v = [p - k for p, k in zip(pend_a, m)], [p - k for p, k in zip(pend_v, m)]
+        return rmask, vplan, aplan, launches, (pend_a, pend_v, rows_a, rows_v, end_a, end_v)
+
+    def _ensure_fuse(self, ya, yv):
+        if self.state is None:
+            dev = ya.device
+            self.state = ops.av_fuse_stream_state(self.B, ya.shape[2], yv.shape[2], self.cap, dev)
+            self.reset_flags = self._flags(dev)
+            self._no_rows = torch.zeros(self.B, dtype=torch.int64, device=dev)
+
+    def _fuse(self, ya, alen, yv, vlen, flags):
+        """the fuse launch -> the fusion module on the pairs (the two Linears of ops.FusionFn.forward on the operand the kernel wrote) -> (x [B, R, F] fp32, pair_len)"""
+        l1, l2 = self.enc.fusion_module.layers[0], self.enc.fusion_module.layers[2]
+        B, R = self.B, self.R
+        xc, plen = ops.av_fuse_stream(ya, alen, yv, vlen, self.state, flags, R)
+        h = ops.linear_fwd(xc.view(B * R, -1), l1.weight, l1.bias, B * R, in_f32=False, out_f32=False, act=ops.ACT_SWISH)
+        return ops.linear_fwd(h, l2.weight, l2.bias, B * R, in_f32=False, out_f32=True).view(B, R, -1), plen
+
+    def push(self, video, wave, n_frames=None, n_samples=None, last_video=None, last_audio=None, reset=None):
+        """video [B, Tv + 2, H, W] fp32, wave [B, first_samples] fp32 -> (logits [B, R or R + n2, V] fp32, out_len [B] int64 on the device, inter: the v_ctc_*, a_ctc_* and
+        f_ctc_* entries of the offline forward, [logits chunk, lengths] each with its own lengths).  n_frames / n_samples / last_video / last_audio / reset: host lists
+        as in VisualStreamSession.push and AudioStreamSession.push (schedule() gives one utterance's); one reset restarts the slot in both branches, the rings and the
+        fusion stack.  n2: the most pairs any slot still had pending behind the first R (at most R).  No host synchronisation after the first push; after capture() the
+        entries of inter are static tensors that the next push overwrites."""
+        B, R = self.B, self.R
+        if video.dim() == 5 and video.shape[1] == 1:
+            video = video[:, 0]
+        if video.dim() != 4 or video.shape[0] != B or video.shape[1] != self.first_frames:
+            raise ValueError("push: video %s for a session of %d slots x %d frames" % (tuple(video.shape), B, self.first_frames))
+        if wave.dim() != 2 or wave.shape[0] != B or wave.shape[1] != self.first_samples:
+            raise ValueError("push: wave %s for a session of %d slots x %d samples" % (tuple(wave.shape), B, self.first_samples))
+        rt.require_gpu(video)
+        rt.require_gpu(wave)
+        if self.enc.training:
+            raise RuntimeError("push: the encoder went back to training mode; call .eval()")
+        rmask, vplan, aplan, launches, mirrors = self._plan(n_frames, n_samples, last_video, last_audio, reset)
+        with torch.no_grad():
+            yv, vlen, inter = self.video.push(video, vplan[2], vplan[1], rmask)
+            ya, alen, a_inter = self.audio.push(wave, aplan[2], aplan[1], rmask)
+            inter = dict(inter)
+            inter.update(a_inter)
+            ya, yv = ya.contiguous(), yv.contiguous()
+            self._ensure_fuse(ya, yv)
+            self._first = False
+            self._pend_a, self._pend_v, self._rows_a, self._rows_v, self._end_a, self._end_v = mirrors
+            x, plen = self._fuse(ya, alen, yv, vlen, self._raise_flags(self.reset_flags, rmask))
+            y, ylen, f_inter = self.back.push(x, plen, rmask)
+            logits = self._head(y)
+            if len(launches) > 1:
+                # (a captured stack's results are static: keep this push's before the next one refills them)
+                logits, ylen, f_inter = [logits.clone()], ylen.clone(), {k: [[v[0].clone()], v[1].clone()] for k, v in f_inter.items()}
+                for m in launches[1:]:
+                    x, plen = self._fuse(ya, self._no_rows, yv, self._no_rows, None)
+                    y, ylen2, inter2 = self.back.push(x, plen, None)
+                    n2 = -(-max(m) // self.back.S)
+                    logits.append(self._head(y[:, :n2].contiguous()))
+                    ylen = ylen + ylen2
+                    for k, v in f_inter.items():
+                        v[0].append(inter2[k][0][:, :n2].clone())
+                        v[1] = v[1] + inter2[k][1]
+                logits, f_inter = torch.cat(logits, dim=1), {k: [torch.cat(v[0], dim=1), v[1]] for k, v in f_inter.items()}
+            inter.update(f_inter)
+            return logits, ylen, inter
+
+    def capture(self, device=None, frame=(88, 88)):
+        """capture the three sub-sessions (VisualStreamSession.capture, AudioStreamSession.capture, ConformerStreamSession.capture); the fuse launch, the fusion module
+        and the head stay eager launches between the replays.  Call it before the first push"""
+        self.video.capture(device, frame)
+        self.audio.capture(device)
         self.back.capture(device)
         return self
 

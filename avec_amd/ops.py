@@ -2389,3 +2389,45 @@ def video_stream_advance(chunk, state, n_frames=None, reset=None, last=None):
     B, Tin, H, W = chunk.shape
     lib.video_stream_advance(rt.dt(), chunk.data_ptr(), chunk.stride(0), state.data_ptr(), state.numel(), _p(n_frames), _p(reset), _p(last), B, Tin, H, W, rt.stream())
     return state
+
+
+# ============================================================================================
+# Streamed audio-visual fusion input (nnet.AudioVisualStreamSession): the branches' rows paired across pushes -> the first fusion Linear's operand (csrc/av_stream.hip)
+# ============================================================================================
+def av_fuse_stream_state(B, Da, Dv, cap, device):
+    """what ops.av_fuse_stream carries between pushes: per slot two rings of `cap` rows in the activation dtype and three int64 counters (one uint8 blob of
+    avec_av_fuse_stream_state_bytes; never cleared: the first push restarts every slot)"""
+    n = lib.raw("avec_av_fuse_stream_state_bytes")(rt.dt(), int(B), int(Da), int(Dv), int(cap))
+    if n <= 0:
+        raise ValueError("av_fuse_stream_state: no state for B=%d rows of %d | %d, cap=%d (the widths must be multiples of 4)" % (B, Da, Dv, cap))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def av_fuse_stream(a, a_len, v, v_len, state, reset=None, max_emit=1, *, out=None):
+    """One launch: a [B, Ra, Da] / v [B, Rv, Dv] fp32 (slot b appends its first a_len[b] / v_len[b] rows; int64 [B] on the device) behind the carried rings ->
+    (xc [B, max_emit, Da + Dv] act: the oldest unpaired rows [audio | video], zeros at or past pair_len; pair_len [B] int64).  reset: uint8 flags [B], consumed
+    (cleared) by the launch.  cap is read off the state's size.  out: (xc, pair_len) to write into.  No synchronisation."""
+    rt.require_gpu(a)
+    if not (a.dim() == 3 and v.dim() == 3 and a.dtype == torch.float32 and v.dtype == torch.float32 and a.is_contiguous() and v.is_contiguous() and a.shape[0] == v.shape[0]
+            and v.device == a.device and state.dtype == torch.uint8 and state.is_contiguous() and state.device == a.device):
+        raise ValueError("av_fuse_stream: a [B, Ra, Da] and v [B, Rv, Dv] fp32, contiguous, with a uint8 state blob on their device (got %s %s, %s %s, %s)"
+                         % (tuple(a.shape), a.dtype, tuple(v.shape), v.dtype, state.dtype))
+    B, Ra, Da = a.shape
+    _, Rv, Dv = v.shape
+    _slot_vec("av_fuse_stream", "a_len", a_len, B, a.device)
+    _slot_vec("av_fuse_stream", "v_len", v_len, B, a.device)
+    _slot_vec("av_fuse_stream", "reset", reset, B, a.device, mask=True)
+    if a_len is None or v_len is None:
+        raise ValueError("av_fuse_stream: a_len and v_len are required (int64 [B] on the device)")
+    adt, max_emit = rt.act_dtype(), int(max_emit)
+    esz = 2 if adt == torch.bfloat16 else 4
+    cap = (state.numel() - 24 * B) // (B * (Da + Dv) * esz)         # the library checks the size exactly: a state of another shape is an argument error
+    if out is None:
+        out = (torch.empty(B, max_emit, Da + Dv, dtype=adt, device=a.device), torch.empty(B, dtype=torch.int64, device=a.device))
+    xc, pair_len = out
+    if not (xc.dtype == adt and xc.is_contiguous() and tuple(xc.shape) == (B, max_emit, Da + Dv) and pair_len.dtype == torch.int64 and pair_len.is_contiguous()
+            and pair_len.numel() == B):
+        raise ValueError("av_fuse_stream: out = (xc [B, max_emit, Da + Dv] in the activation dtype, pair_len int64 [B]), contiguous")
+    lib.av_fuse_stream(rt.dt(), a.data_ptr(), a_len.data_ptr(), v.data_ptr(), v_len.data_ptr(), state.data_ptr(), state.numel(), _p(reset), xc.data_ptr(), pair_len.data_ptr(),
+                       B, Ra, Rv, Da, Dv, cap, max_emit, rt.stream())
+    return xc, pair_len

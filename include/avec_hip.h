@@ -392,6 +392,23 @@ int avec_video_stem_stream(int dtype, const float* chunk, long long ldc, const v
 int avec_video_stream_advance(int dtype, const float* chunk, long long ldc, void* state, long long state_bytes, const long long* n_frames, unsigned char* reset,
                               unsigned char* last, int B, int Tin, int H, int W, hipStream_t stream);
 
+/* ---- streamed audio-visual fusion input (nnet.AudioVisualStreamSession; avec_amd/csrc/av_stream.hip) -------------------------------------------------------------
+ * Pairs the 80 ms rows of the audio and the visual branch across pushes and writes the operand of the fusion module's first Linear.  state (caller-owned,
+ * avec_av_fuse_stream_state_bytes, 16-byte aligned, never cleared): per slot two rings of `cap` rows in the activation dtype (absolute row p of a branch in ring row
+ * p mod cap, cast as avec_cast_rows casts: a carried row is bit-identical to a freshly cast one) and three int64 counters: audio rows received, video rows received,
+ * pairs emitted.
+ * avec_av_fuse_stream, for slot b: with reset[b] (bytes, NULL: none) the three counters count as 0 -- whatever the rings hold is older and counts as absent; the
+ *   first a_len[b] rows of a [B][Ra][Da] fp32 and the first v_len[b] rows of v [B][Rv][Dv] fp32 are appended (lengths int64, clamped to 0 .. Ra / Rv; rows at or past
+ *   them are never loaded); m = min(audio rows - pairs, video rows - pairs, max_emit); xc[b][i] = [audio row (pairs + i) | video row (pairs + i)] for i < m and zeros
+ *   for m <= i < max_emit (xc [B][max_emit][Da + Dv] in the activation dtype); pair_len[b] = m; pairs += m; the counters are stored and reset[b] is cleared (consumed).
+ *   A launch with a_len = v_len = 0 emits what an earlier one left pending.  One workgroup per slot: every read of the old state precedes a barrier, every write to it
+ *   follows; an output element is a copy of one input element through one cast, no atomics.  Da % 4 == 0, Dv % 4 == 0; a, v, state and xc 16-byte aligned, the int64
+ *   vectors 8-byte aligned; cap >= max_emit + 2, Ra <= cap, Rv <= cap, state_bytes exactly avec_av_fuse_stream_state_bytes: argument errors before any launch.  A
+ *   slot whose pending + incoming rows exceed cap loses rows: that cannot be reported from the device and is the caller's contract. */
+long long avec_av_fuse_stream_state_bytes(int dtype, int B, int Da, int Dv, int cap);
+int avec_av_fuse_stream(int dtype, const float* a, const long long* a_len, const float* v, const long long* v_len, void* state, long long state_bytes,
+                        unsigned char* reset, void* xc, long long* pair_len, int B, int Ra, int Rv, int Da, int Dv, int cap, int max_emit, hipStream_t stream);
+
 /* ---- front-ends (avec_amd/csrc/frontend.hip) ------------------------------------------------ */
 /* AudioPreprocessing (nnet/preprocessing.py:57-85; torchaudio Spectrogram/MelScale restated): frames -> [DFT via avec_gemm_nt fp32] -> power/mel/log */
 int avec_mel_frames(const float* audio, const float* window, float* frames, int B, long long L, int n_fft, int win, int hop, hipStream_t stream);
