@@ -1,7 +1,17 @@
-"""Streaming sessions: a causal Conformer stack, the audio and the visual front-end, the audio-visual encoder and the CTC beam search run chunk by chunk over a fixed number
-of utterance slots.  None of them has a counterpart in the reference; the factories (ConformerInterCTC.stream, AudioEfficientConformerEncoder.stream_front / .stream,
-VisualEfficientConformerEncoder.stream_front / .stream, AudioVisualEfficientConformerEncoder.stream, CTCBeamSearchDecoder.stream) stay with the classes they wrap.
-A session owns its device state; nothing is added to a module tree or a state_dict."""
+"""Streaming sessions: models run chunk by chunk over a fixed number of utterance slots.  None has a counterpart in the reference; the factories (.stream_front() /
+.stream() of the encoders, ConformerInterCTC.stream, CTCBeamSearchDecoder.stream) stay with the classes they wrap.  A session owns its device state; nothing is added to
+a module tree or a state_dict.
+
+    _StreamSession                      B slots, `_first`, flag vectors uploaded only when a flag is set
+      _CapturableSession                a push is a fixed sequence of launches: the device side of push, capture()
+        ConformerStreamSession          a causal Conformer stack
+        _FrontStreamSession             a front-end: count / last / reset controls, their host mirror, the schedule rules (_controls) and _commit
+          AudioFrontStreamSession       waveform chunks -> stem frames
+          VisualFrontStreamSession      video chunks -> ResNet features
+      AudioVisualStreamSession          both branch sessions -> row pairing -> the fusion stack
+      CTCBeamStreamSession              the beam search over logit chunks
+    _BranchStreamSession                a front session -> the stack -> the head; a last push's tail of up to TAIL frames goes through _push_again
+      AudioStreamSession (TAIL 1), VisualStreamSession (TAIL 2)"""
 import torch
 import torch.nn as nn
 
@@ -298,13 +308,14 @@ class ConformerStreamSession(_CapturableSession):
         return self._push(x_chunk, mask, host_len, chunk_len)
 
 
-class AudioFrontStreamSession(_CapturableSession):
-    """AudioEfficientConformerEncoder.stream_front(): the audio front-end (log-mel -> Conv2d + BatchNorm2d + Swish stem -> Linear) run on waveform chunks.  The frames a
-    slot has produced after any sequence of pushes equal the offline front-end's frames on the samples pushed so far (and, once the utterance has ended, on the whole
-    utterance: both STFT reflections and both zero paddings of the stem included), up to the DFT GEMM's tile choice.  Mel frame f reads samples [160 f - 200, 160 f + 200),
-    stem frame t reads mel frames 2t - 1, 2t, 2t + 1: with n samples heard E(n) = 0 if n < 360 else (n - 40) // 320 frames exist, Ta // 320 + 1 at the end.  Schedule:
-    first_samples = 320 Tc + 40 in an utterance's first push, chunk_samples = 320 Tc in every later one; every push but the last then yields exactly Tc frames, the last at
-    most Tc + 1.  The carried state is a sample tail of fewer than 720 samples per slot, a counter and an `ended` flag, on the device (ops.audio_stream_state)."""
+class _FrontStreamSession(_CapturableSession):
+    """A front-end run on input chunks of which slot b takes a count of units (UNIT: samples or frames) per push.  Here, once: the device count and flag vectors,
+    their host mirror (`_n` units heard and `_ended` per slot; None: unknown after a push with device-tensor counts), the schedule rules of a host-list push
+    (_controls), the upload and the mirror's update (_commit).  A subclass gives UNIT, INPUT (the input's name and rank), `_sched` = (first, chunk) counts, `_caps`
+    (the most a slot may take at the start of its utterance, and later), _ready(n) (frames that exist after n units), _frames_at_last(b, n0, c), _zero_input(dev), and its _check,
+    _allocate (which calls _allocate_controls) and _run."""
+
+    _cap_note = ""                                 # what the refusal of a count above its cap adds about the schedule
 
     def __init__(self, enc, batch_size, chunk_frames):
         super().__init__(enc, batch_size)
@@ -312,14 +323,105 @@ class AudioFrontStreamSession(_CapturableSession):
         self._check(enc)
         if self.B < 1:
             raise ValueError("stream_front: batch_size %d" % self.B)
+        self.Tmax = self.Tc + 2                    # any count up to the first push's, at the end of an utterance too, gives at most Tc + 2 frames
+        self._forget()
+        self._up = None                            # what self._count holds
+
+    def _allocate_controls(self, dev, bn):
+        """the count and flag vectors, and `ss`: the eval-mode scale | shift of the stem's BatchNorm from its running statistics"""
+        self._count = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        self.reset_flags, self.last_flags = self._flags(dev), self._flags(dev)
+        st = ops.BNState(bn.num_features, self._count)
+        ops.bn_finalize(bn, st, 1, False)
+        self.ss = st.ss
+
+    # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
+    def _controls(self, n_units, last, reset):
+        """-> (reset mask, last mask, host counts or None for a device tensor, frames per slot or None): checks a host-list push against the contract, changes nothing"""
+        B, unit = self.B, self.UNIT
+        first, chunk = self._sched
+        rmask = self._reset_mask(reset) or [False] * B
+        lmask = slot_mask(last, B)
+        if torch.is_tensor(n_units):
+            return rmask, lmask, None, None
+        if n_units is not None and len(n_units) != B:
+            raise ValueError("push: n_%s %r for %d slots" % (unit, list(n_units), B))
+        counts, frames = [], []
+        (cap0, cap1), ready = self._caps, self._ready      # (a push is partly host-bound: no attribute lookups per slot)
+        for b in range(B):
+            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
+            if n0 is None:
+                raise RuntimeError("push: slot %d was last pushed with device-tensor counts, which the host does not mirror: go on with a tensor, or reset the slot" % b)
+            c = (0 if ended else (first if n0 == 0 else chunk)) if n_units is None else int(n_units[b])
+            cap = cap0 if n0 == 0 else cap1
+            if c < 0 or c > cap:
+                raise ValueError("push: n_%s[%d] = %d outside 0 .. %d%s" % (unit, b, c, cap, self._cap_note))
+            if ended:
+                if c > 0:
+                    raise RuntimeError("push: slot %d has ended (last) and was not reset: it takes no %s until reset=[%d] starts the next utterance" % (b, unit, b))
+                frames.append(0)
+            elif lmask[b]:
+                frames.append(self._frames_at_last(b, n0, c))
+            else:
+                frames.append(ready(n0 + c) - ready(n0))
+            counts.append(c)
+        return rmask, lmask, counts, frames
+
+    def _commit(self, rmask, lmask, counts):
+        """the host mirror after a push of these controls (counts None: device-tensor counts, whose contract is the caller's)"""
+        B = self.B
+        if counts is None:
+            self._n, self._ended = [None] * B, [None] * B
+            return
+        for b in range(B):
+            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
+            self._n[b], self._ended[b] = n0 + counts[b], ended or lmask[b]
+
+    def _upload(self, rmask, lmask, counts, dev_counts):
+        self._raise_flags(self.reset_flags, rmask)
+        self._raise_flags(self.last_flags, lmask)
+        if counts is None:
+            self._count.copy_(dev_counts.view(self.B), non_blocking=True)
+            self._up = None
+        elif counts != self._up:
+            self._count.copy_(torch.tensor(counts, dtype=torch.int64), non_blocking=True)
+            self._up = list(counts)
+        self._commit(rmask, lmask, counts)
+
+    def _static_input(self, dev):
+        B, first = self.B, self._sched[0]
+        return self._zero_input(dev), ([True] * B, [False] * B, [first] * B, None)
+
+    def _forget(self):
+        self._n, self._ended = [0] * self.B, [False] * self.B
+
+    def _check_input(self, x):
+        """what every push checks of its input before the controls"""
+        name, rank = self.INPUT
+        if x.dim() != rank or x.shape[0] != self.B or x.shape[1] != self._sched[0]:
+            raise ValueError("push: %s %s for a session of %d slots x %d %s" % (name, tuple(x.shape), self.B, self._sched[0], self.UNIT))
+        rt.require_gpu(x)
+        if self.enc.training:
+            raise RuntimeError("push: the encoder went back to training mode; call .eval()")
+
+
+class AudioFrontStreamSession(_FrontStreamSession):
+    """AudioEfficientConformerEncoder.stream_front(): the audio front-end (log-mel -> Conv2d + BatchNorm2d + Swish stem -> Linear) run on waveform chunks.  The frames a
+    slot has produced after any sequence of pushes equal the offline front-end's frames on the samples pushed so far (and, once the utterance has ended, on the whole
+    utterance: both STFT reflections and both zero paddings of the stem included), up to the DFT GEMM's tile choice.  Mel frame f reads samples [160 f - 200, 160 f + 200),
+    stem frame t reads mel frames 2t - 1, 2t, 2t + 1: with n samples heard E(n) = 0 if n < 360 else (n - 40) // 320 frames exist, Ta // 320 + 1 at the end.  Schedule:
+    first_samples = 320 Tc + 40 in an utterance's first push, chunk_samples = 320 Tc in every later one; every push but the last then yields exactly Tc frames, the last at
+    most Tc + 1.  The carried state is a sample tail of fewer than 720 samples per slot, a counter and an `ended` flag, on the device (ops.audio_stream_state)."""
+
+    UNIT, INPUT = "samples", ("wave", 2)
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        super().__init__(enc, batch_size, chunk_frames)
         if self.Tc < 2:
             raise ValueError("stream_front: chunk_frames = %d: a push of %d samples would be shorter than one %d-sample analysis window; at least 2 frames (80 ms) per push"
                              % (self.Tc, 2 * self.hop * self.Tc, self.win))
-        self.first_samples, self.chunk_samples = 2 * self.hop * self.Tc + (self.win // 2 - self.hop), 2 * self.hop * self.Tc
-        self.Tmax = self.Tc + 2                    # any count up to first_samples, at the end of an utterance too, gives at most Tc + 2 frames
-        self._n = [0] * self.B                     # host mirror of the device counters (None: unknown after a push with device-tensor counts)
-        self._ended = [False] * self.B
-        self._ns_up = None                         # what self.nsamp holds
+        self.first_samples, self.chunk_samples = self._sched = 2 * self.hop * self.Tc + (self.win // 2 - self.hop), 2 * self.hop * self.Tc
+        self._caps = (self.first_samples, self.first_samples)
 
     def _check(self, enc):
         if enc.training:
@@ -340,14 +442,16 @@ class AudioFrontStreamSession(_CapturableSession):
         a = self.hop + self.win // 2
         return 0 if n < a else (n - a) // (2 * self.hop) + 1
 
+    def _frames_at_last(self, b, n0, c):
+        if n0 + c <= self.n_fft // 2:
+            raise ValueError("push: slot %d ends after %d samples: an utterance of at most n_fft / 2 = %d samples cannot be reflect-padded (refused offline as well)"
+                             % (b, n0 + c, self.n_fft // 2))
+        return (n0 + c) // (2 * self.hop) + 1 - self._ready(n0)
+
     def _allocate(self, dev):
-        bn = self.enc.subsampling_module.layers[0][1]
         self.state = ops.audio_stream_state(self.B, dev)
-        self.nsamp = torch.zeros(self.B, dtype=torch.int64, device=dev)
-        self.reset_flags, self.last_flags = self._flags(dev), self._flags(dev)
-        st = ops.BNState(bn.num_features, self.state)
-        ops.bn_finalize(bn, st, 1, False)              # eval mode: scale | shift from the running statistics
-        self.ss = st.ss
+        self._allocate_controls(dev, self.enc.subsampling_module.layers[0][1])
+        self.nsamp = self._count
 
     def _run(self, wave):
         if not (wave.dtype == torch.float32 and wave.stride(1) == 1):
@@ -363,60 +467,8 @@ class AudioFrontStreamSession(_CapturableSession):
         feat = ops.linear_fwd(a.view(B * Tmax, -1), lin.weight, lin.bias, B * Tmax, in_f32=False, out_f32=True)
         return feat.view(B, Tmax, -1), out_len
 
-    # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
-    def _controls(self, n_samples, last, reset):
-        """-> (reset mask, last mask, host counts or None for a device tensor, frames per slot or None): checks a host-list push against the contract, changes nothing"""
-        B = self.B
-        rmask = self._reset_mask(reset) or [False] * B
-        lmask = slot_mask(last, B)
-        if torch.is_tensor(n_samples):
-            return rmask, lmask, None, None
-        if n_samples is not None and len(n_samples) != B:
-            raise ValueError("push: n_samples %r for %d slots" % (list(n_samples), B))
-        counts, frames = [], []
-        for b in range(B):
-            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
-            if n0 is None:
-                raise RuntimeError("push: slot %d was last pushed with device-tensor counts, which the host does not mirror: go on with a tensor, or reset the slot" % b)
-            c = (0 if ended else (self.first_samples if n0 == 0 else self.chunk_samples)) if n_samples is None else int(n_samples[b])
-            if c < 0 or c > self.first_samples:
-                raise ValueError("push: n_samples[%d] = %d outside 0 .. %d" % (b, c, self.first_samples))
-            if ended:
-                if c > 0:
-                    raise RuntimeError("push: slot %d has ended (last) and was not reset: it takes no samples until reset=[%d] starts the next utterance" % (b, b))
-                frames.append(0)
-            elif lmask[b]:
-                if n0 + c <= self.n_fft // 2:
-                    raise ValueError("push: slot %d ends after %d samples: an utterance of at most n_fft / 2 = %d samples cannot be reflect-padded (refused offline as well)"
-                                     % (b, n0 + c, self.n_fft // 2))
-                frames.append((n0 + c) // (2 * self.hop) + 1 - self._ready(n0))
-            else:
-                frames.append(self._ready(n0 + c) - self._ready(n0))
-            counts.append(c)
-        return rmask, lmask, counts, frames
-
-    def _upload(self, rmask, lmask, counts, n_samples):
-        B = self.B
-        self._raise_flags(self.reset_flags, rmask)
-        self._raise_flags(self.last_flags, lmask)
-        if counts is None:
-            self.nsamp.copy_(n_samples.view(B), non_blocking=True)
-            self._ns_up = None
-            self._n, self._ended = [None] * B, [None] * B                 # a device tensor's contract is the caller's
-            return
-        if counts != self._ns_up:
-            self.nsamp.copy_(torch.tensor(counts, dtype=torch.int64), non_blocking=True)
-            self._ns_up = list(counts)
-        for b in range(B):
-            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
-            self._n[b], self._ended[b] = n0 + counts[b], ended or lmask[b]
-
-    def _static_input(self, dev):
-        B = self.B
-        return torch.zeros(B, self.first_samples, dtype=torch.float32, device=dev), ([True] * B, [False] * B, [self.first_samples] * B, None)
-
-    def _forget(self):
-        self._n, self._ended = [0] * self.B, [False] * self.B
+    def _zero_input(self, dev):
+        return torch.zeros(self.B, self.first_samples, dtype=torch.float32, device=dev)
 
     def push(self, wave, n_samples=None, last=None, reset=None):
         """wave [B, first_samples] fp32 -> (feat [B, Tc + 2, 180] fp32, out_len [B] int64 on the device): slot b takes the first n_samples[b] samples (a Python list
@@ -425,73 +477,12 @@ class AudioFrontStreamSession(_CapturableSession):
         of indices or a host bool mask [B]); the first push restarts every slot.  With host counts the contract is checked on the host, without a synchronisation:
         counts within 0 .. first_samples, an utterance longer than n_fft / 2 = 256 samples at `last`, no samples to an ended slot.  With a device tensor it is the
         caller's.  No host synchronisation after the first push; after capture() the results are static tensors that the next push overwrites."""
-        if wave.dim() != 2 or wave.shape[0] != self.B or wave.shape[1] != self.first_samples:
-            raise ValueError("push: wave %s for a session of %d slots x %d samples" % (tuple(wave.shape), self.B, self.first_samples))
-        rt.require_gpu(wave)
-        if self.enc.training:
-            raise RuntimeError("push: the encoder went back to training mode; call .eval()")
+        self._check_input(wave)
         rmask, lmask, counts, _ = self._controls(n_samples, last, reset)
         return self._push(wave, rmask, lmask, counts, n_samples)
 
 
-class AudioStreamSession:
-    """AudioEfficientConformerEncoder.stream(): waveform chunks -> logits.  The front session feeds back_end.stream() (a ConformerStreamSession, with its refusals) and
-    the head.  The front's schedule makes every push but an utterance's last yield exactly Tc frames, one chunk of the stack; a last push may yield Tc + 1: the stack
-    is then pushed a second time with that one frame for the slots concerned and 0 frames (no change of state) for the others, and its first output row is appended."""
-
-    def __init__(self, enc, batch_size, chunk_frames):
-        self.enc = enc
-        self.front = AudioFrontStreamSession(enc, batch_size, chunk_frames)
-        self.back = enc.back_end.stream(batch_size, chunk_frames)
-        self.B, self.Tc, self.S = self.front.B, self.front.Tc, self.back.S
-        self.first_samples, self.chunk_samples = self.front.first_samples, self.front.chunk_samples
-        self._x2 = None
-
-    def _head(self, y):
-        return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
-
-    def _plan(self, n_samples, last, reset):
-        """the host side of a push, before anything is launched: the front's controls (reset mask, last mask, counts, frames per slot), checked against the schedule"""
-        if torch.is_tensor(n_samples):
-            raise TypeError("push: the combined session takes host lists for n_samples (it decides on the host whether the stack needs a second push)")
-        Tc = self.Tc
-        rmask, lmask, counts, frames = self.front._controls(n_samples, last, reset)
-        for b in range(self.B):
-            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 1)):
-                raise ValueError("push: slot %d would yield %d frames from %d samples: off the schedule (first_samples = %d in an utterance's first push, chunk_samples = %d "
-                                 "later, fewer only with last)" % (b, frames[b], counts[b], self.first_samples, self.chunk_samples))
-        return rmask, lmask, counts, frames
-
-    def push(self, wave, n_samples=None, last=None, reset=None):
-        """wave [B, first_samples] fp32 -> (logits [B, R, V] fp32, out_len [B] int64 on the device, inter: loss_prefix_i -> [logits chunk, lengths] as offline).
-        n_samples / last / reset: host lists as AudioFrontStreamSession.push; counts must follow the schedule (every push of a slot but its last yields exactly
-        chunk_frames frames; a slot may idle on 0 samples).  R = Tc / S, or Tc / S + 1 in a push where some slot's last chunk produced Tc + 1 frames."""
-        B, Tc = self.B, self.Tc
-        rmask, lmask, counts, frames = self._plan(n_samples, last, reset)
-        with torch.no_grad():
-            feat, _ = self.front.push(wave, counts, lmask, rmask)
-            tail = [f > Tc for f in frames]
-            y, ylen, inter = self.back.push(feat[:, :Tc], torch.tensor([min(f, Tc) for f in frames], dtype=torch.int64), rmask)
-            if not any(tail):
-                return self._head(y), ylen, inter
-            # (a captured stack's results are static: keep this push's before the second one refills them)
-            logits, ylen, inter = self._head(y).clone(), ylen.clone(), {k: [v[0].clone(), v[1].clone()] for k, v in inter.items()}
-            if self._x2 is None:
-                self._x2 = torch.zeros(B, Tc, feat.shape[2], dtype=feat.dtype, device=feat.device)
-            self._x2[:, 0].copy_(feat[:, Tc])
-            y2, ylen2, inter2 = self.back.push(self._x2, torch.tensor([1 if t else 0 for t in tail], dtype=torch.int64), None)
-            for k, v in inter.items():
-                inter[k] = [torch.cat([v[0], inter2[k][0][:, :1]], dim=1), v[1] + inter2[k][1]]
-            return torch.cat([logits, self._head(y2[:, :1].contiguous())], dim=1), ylen + ylen2, inter
-
-    def capture(self, device=None):
-        """capture both halves (AudioFrontStreamSession.capture, ConformerStreamSession.capture); call it before the first push"""
-        self.front.capture(device)
-        self.back.capture(device)
-        return self
-
-
-class VisualFrontStreamSession(_CapturableSession):
+class VisualFrontStreamSession(_FrontStreamSession):
     """VisualEfficientConformerEncoder.stream_front(): the visual front-end (Conv3d stem + BatchNorm3d + ReLU + max pool -> ResNet-18 -> Linear) run on video chunks.
     The frames a slot has produced after any sequence of pushes equal the offline front-end's frames on the frames pushed so far (and, once the utterance has ended, on
     the whole utterance: both temporal zero paddings included).  Everything behind the Conv3d works per frame and eval-mode BatchNorm uses running statistics, so the
@@ -501,19 +492,14 @@ class VisualFrontStreamSession(_CapturableSession):
     (ops.video_stream_state).  The stem launch writes its frames frame-major, so the first Tc * B of them are a plain view: the ResNet and the Linear run on B * Tc
     frames, and on the 2 B tail frames only in a push where some slot can yield more than Tc (`resnet_frames` records what the last push ran)."""
 
+    UNIT, INPUT = "frames", ("video", 4)
+
     def __init__(self, enc, batch_size, chunk_frames):
-        super().__init__(enc, batch_size)
-        self.enc, self.Tc = enc, int(chunk_frames)
-        self._check(enc)
-        if self.B < 1:
-            raise ValueError("stream_front: batch_size %d" % self.B)
+        super().__init__(enc, batch_size, chunk_frames)
         if self.Tc < 1:
             raise ValueError("stream_front: chunk_frames = %d: at least 1 frame per push" % self.Tc)
-        self.first_frames, self.chunk_frames = self.Tc + 2, self.Tc
-        self.Tmax = self.Tc + 2                    # any count up to first_frames, at the end of an utterance too, gives at most Tc + 2 frames
-        self._n = [0] * self.B                     # host mirror of the device counters (None: unknown after a push with device-tensor counts)
-        self._ended = [False] * self.B
-        self._nf_up = None                         # what self.nframes holds
+        self.first_frames, self.chunk_frames = self._sched = self._caps = self.Tc + 2, self.Tc
+        self._cap_note = " (first_frames = %d at the start of an utterance, chunk_frames = %d later)" % self._sched
         self._frames = self._feat = None           # the stem's frames and the features of the last push (static after capture())
         self.resnet_frames = 0                     # frames the ResNet and the Linear ran on in the last push
 
@@ -532,13 +518,13 @@ class VisualFrontStreamSession(_CapturableSession):
     def _ready(n):
         return max(0, n - 2)
 
+    def _frames_at_last(self, b, n0, c):
+        return n0 + c - self._ready(n0)
+
     def _allocate(self, dev):
-        self.nframes = torch.zeros(self.B, dtype=torch.int64, device=dev)
-        self.reset_flags, self.last_flags = self._flags(dev), self._flags(dev)
         stem = self.enc.front_end[0].layers[0]
-        st = ops.BNState(64, self.nframes)
-        ops.bn_finalize(stem[1], st, 1, False)         # eval mode: scale | shift from the running statistics
-        self.ss = st.ss
+        self._allocate_controls(dev, stem[1])
+        self.nframes = self._count
         self.w8 = ops.video_stem_w8(stem[0].weight)    # once per session, not once per push
         self.state = {"ring": None}                    # the ring's size depends on the frame: allocated by the first _run
 
@@ -562,60 +548,8 @@ class VisualFrontStreamSession(_CapturableSession):
         self._frames, self._feat = frames, feat
         return feat, out_len
 
-    # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
-    def _controls(self, n_frames, last, reset):
-        """-> (reset mask, last mask, host counts or None for a device tensor, frames per slot or None): checks a host-list push against the contract, changes nothing"""
-        B = self.B
-        rmask = self._reset_mask(reset) or [False] * B
-        lmask = slot_mask(last, B)
-        if torch.is_tensor(n_frames):
-            return rmask, lmask, None, None
-        if n_frames is not None and len(n_frames) != B:
-            raise ValueError("push: n_frames %r for %d slots" % (list(n_frames), B))
-        counts, frames = [], []
-        for b in range(B):
-            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
-            if n0 is None:
-                raise RuntimeError("push: slot %d was last pushed with device-tensor counts, which the host does not mirror: go on with a tensor, or reset the slot" % b)
-            cap = self.first_frames if n0 == 0 else self.chunk_frames
-            c = (0 if ended else cap) if n_frames is None else int(n_frames[b])
-            if c < 0 or c > cap:
-                raise ValueError("push: n_frames[%d] = %d outside 0 .. %d (first_frames = %d at the start of an utterance, chunk_frames = %d later)"
-                                 % (b, c, cap, self.first_frames, self.chunk_frames))
-            if ended:
-                if c > 0:
-                    raise RuntimeError("push: slot %d has ended (last) and was not reset: it takes no frames until reset=[%d] starts the next utterance" % (b, b))
-                frames.append(0)
-            elif lmask[b]:
-                frames.append(n0 + c - self._ready(n0))
-            else:
-                frames.append(self._ready(n0 + c) - self._ready(n0))
-            counts.append(c)
-        return rmask, lmask, counts, frames
-
-    def _upload(self, rmask, lmask, counts, n_frames):
-        B = self.B
-        self._raise_flags(self.reset_flags, rmask)
-        self._raise_flags(self.last_flags, lmask)
-        if counts is None:
-            self.nframes.copy_(n_frames.view(B), non_blocking=True)
-            self._nf_up = None
-            self._n, self._ended = [None] * B, [None] * B                 # a device tensor's contract is the caller's
-            return
-        if counts != self._nf_up:
-            self.nframes.copy_(torch.tensor(counts, dtype=torch.int64), non_blocking=True)
-            self._nf_up = list(counts)
-        for b in range(B):
-            n0, ended = (0, False) if rmask[b] else (self._n[b], self._ended[b])
-            self._n[b], self._ended[b] = n0 + counts[b], ended or lmask[b]
-
-    def _static_input(self, dev):
-        B = self.B
-        H, W = self._capture_frame
-        return torch.zeros(B, self.first_frames, H, W, dtype=torch.float32, device=dev), ([True] * B, [False] * B, [self.first_frames] * B, None)
-
-    def _forget(self):
-        self._n, self._ended = [0] * self.B, [False] * self.B
+    def _zero_input(self, dev):
+        return torch.zeros(self.B, self.first_frames, *self._capture_frame, dtype=torch.float32, device=dev)
 
     def capture(self, device=None, frame=(88, 88)):
         """As the other sessions' capture(); `frame` = (H, W) of the video the session will be fed.  The captured push covers the Tc-frame case; a push in which some
@@ -632,11 +566,7 @@ class VisualFrontStreamSession(_CapturableSession):
         tensor it is the caller's.  No host synchronisation after the first push; after capture() the results are static tensors that the next push overwrites."""
         if video.dim() == 5 and video.shape[1] == 1:
             video = video[:, 0]
-        if video.dim() != 4 or video.shape[0] != self.B or video.shape[1] != self.first_frames:
-            raise ValueError("push: video %s for a session of %d slots x %d frames" % (tuple(video.shape), self.B, self.first_frames))
-        rt.require_gpu(video)
-        if self.enc.training:
-            raise RuntimeError("push: the encoder went back to training mode; call .eval()")
+        self._check_input(video)
         if self._capture is not None and tuple(video.shape[2:]) != self._capture_frame:
             raise ValueError("push: frames of %dx%d for a push captured at %dx%d" % (video.shape[2], video.shape[3], *self._capture_frame))
         rmask, lmask, counts, frames = self._controls(n_frames, last, reset)
@@ -649,66 +579,112 @@ class VisualFrontStreamSession(_CapturableSession):
         return feat, out_len
 
 
-class VisualStreamSession:
+def _head(enc, y):
+    return y if isinstance(enc.head, nn.Identity) else enc.head(y)
+
+
+def _push_again(back, enc, first, feed, n):
+    """(logits, lengths, inter) of a push of the stack session `back` -> the same with the first n rows of a second push appended, whose (input, chunk lengths)
+    feed() gives.  A captured stack's results are static tensors that the second push refills: they are cloned before feed() and the push launch anything."""
+    logits, ylen, inter = first[0].clone(), first[1].clone(), {k: [v[0].clone(), v[1].clone()] for k, v in first[2].items()}
+    y2, ylen2, inter2 = back.push(*feed(), None)
+    for k, v in inter.items():
+        inter[k] = [torch.cat([v[0], inter2[k][0][:, :n]], dim=1), v[1] + inter2[k][1]]
+    return torch.cat([logits, _head(enc, y2[:, :n].contiguous())], dim=1), ylen + ylen2, inter
+
+
+class _BranchStreamSession:
+    """FRONT(enc, B, Tc) feeds enc.back_end.stream(B, Tc) (a ConformerStreamSession, with its refusals) and the head.  The front's schedule makes every push but an
+    utterance's last yield exactly Tc frames, one chunk of the stack; a last push may leave a tail of up to TAIL frames beyond Tc: the stack is then pushed a second
+    time with the tail frames of the slots concerned and 0 frames (no change of state) for the others, and the rows that yields are appended."""
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        self.enc = enc
+        self.front = self.FRONT(enc, batch_size, chunk_frames)
+        self.back = enc.back_end.stream(batch_size, chunk_frames)
+        self.B, self.Tc, self.S = self.front.B, self.front.Tc, self.back.S
+        if self.Tc < self.TAIL:
+            raise ValueError("stream: chunk_frames = %d: at least %d, so that a last push's tail of up to %d frames fits one chunk of the stack" % (self.Tc, self.TAIL, self.TAIL))
+        self._x2 = None
+
+    def _plan(self, n_units, last, reset):
+        """the host side of a push, before anything is launched: the front's controls (reset mask, last mask, counts, frames per slot), checked against the schedule"""
+        unit = self.front.UNIT
+        if torch.is_tensor(n_units):
+            raise TypeError("push: the combined session takes host lists for n_%s (it decides on the host whether the stack needs a second push)" % unit)
+        Tc = self.Tc
+        rmask, lmask, counts, frames = self.front._controls(n_units, last, reset)
+        for b in range(self.B):
+            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + self.TAIL)):
+                raise ValueError("push: slot %d would yield %d frames from %s: off the schedule (first_%s = %d in an utterance's first push, chunk_%s = %d later, "
+                                 "fewer only with last)" % (b, frames[b], self.FROM % counts[b], unit, self.front._sched[0], unit, self.front._sched[1]))
+        return rmask, lmask, counts, frames
+
+    def _tail_input(self, feat, tail):
+        """a chunk of the stack whose first TAIL rows are the front's rows behind Tc, and the tail per slot as its chunk lengths"""
+        if self._x2 is None:
+            self._x2 = torch.zeros(self.B, self.Tc, feat.shape[2], dtype=feat.dtype, device=feat.device)
+        self._x2[:, :self.TAIL].copy_(feat[:, self.Tc:self.Tc + self.TAIL])
+        return self._x2, torch.tensor(tail, dtype=torch.int64)
+
+    def _push_branch(self, x, n_units, last, reset):
+        Tc = self.Tc
+        rmask, lmask, counts, frames = self._plan(n_units, last, reset)
+        with torch.no_grad():
+            feat, _ = self.front.push(x, counts, lmask, rmask)
+            tail = [max(0, f - Tc) for f in frames]
+            y, ylen, inter = self.back.push(feat[:, :Tc], torch.tensor([min(f, Tc) for f in frames], dtype=torch.int64), rmask)
+            if not any(tail):
+                return _head(self.enc, y), ylen, inter
+            return _push_again(self.back, self.enc, (_head(self.enc, y), ylen, inter), lambda: self._tail_input(feat, tail), -(-max(tail) // self.S))
+
+    def capture(self, device=None, **front_args):
+        """capture both halves (the front session's capture with front_args, ConformerStreamSession.capture); call it before the first push"""
+        self.front.capture(device, **front_args)
+        self.back.capture(device)
+        return self
+
+
+class AudioStreamSession(_BranchStreamSession):
+    """AudioEfficientConformerEncoder.stream(): waveform chunks -> logits.  The front session feeds back_end.stream() (a ConformerStreamSession, with its refusals) and
+    the head.  The front's schedule makes every push but an utterance's last yield exactly Tc frames, one chunk of the stack; a last push may yield Tc + 1: the stack
+    is then pushed a second time with that one frame for the slots concerned and 0 frames (no change of state) for the others, and its first output row is appended."""
+
+    FRONT, TAIL, FROM = AudioFrontStreamSession, 1, "%d samples"
+
+    def __init__(self, enc, batch_size, chunk_frames):
+        super().__init__(enc, batch_size, chunk_frames)
+        self.first_samples, self.chunk_samples = self.front._sched
+
+    def push(self, wave, n_samples=None, last=None, reset=None):
+        """wave [B, first_samples] fp32 -> (logits [B, R, V] fp32, out_len [B] int64 on the device, inter: loss_prefix_i -> [logits chunk, lengths] as offline).
+        n_samples / last / reset: host lists as AudioFrontStreamSession.push; counts must follow the schedule (every push of a slot but its last yields exactly
+        chunk_frames frames; a slot may idle on 0 samples).  R = Tc / S, or Tc / S + 1 in a push where some slot's last chunk produced Tc + 1 frames."""
+        return self._push_branch(wave, n_samples, last, reset)
+
+
+class VisualStreamSession(_BranchStreamSession):
     """VisualEfficientConformerEncoder.stream(): video chunks -> logits.  The front session feeds back_end.stream() (a ConformerStreamSession, with its refusals) and
     the head.  The front's schedule makes every push but an utterance's last yield exactly Tc frames, one chunk of the stack; a last push may yield Tc + 1 or Tc + 2:
     the stack is then pushed a second time with those tail frames for the slots concerned and 0 frames (no change of state) for the others, and the rows it yields
     are appended."""
 
+    FRONT, TAIL, FROM = VisualFrontStreamSession, 2, "%d"
+
     def __init__(self, enc, batch_size, chunk_frames):
-        self.enc = enc
-        self.front = VisualFrontStreamSession(enc, batch_size, chunk_frames)
-        self.back = enc.back_end.stream(batch_size, chunk_frames)
-        self.B, self.Tc, self.S = self.front.B, self.front.Tc, self.back.S
-        if self.Tc < 2:
-            raise ValueError("stream: chunk_frames = %d: at least 2, so that a last push's tail of up to 2 frames fits one chunk of the stack" % self.Tc)
-        self.first_frames, self.chunk_frames = self.front.first_frames, self.front.chunk_frames
-        self._x2 = None
-
-    def _head(self, y):
-        return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
-
-    def _plan(self, n_frames, last, reset):
-        """the host side of a push, before anything is launched: the front's controls (reset mask, last mask, counts, frames per slot), checked against the schedule"""
-        if torch.is_tensor(n_frames):
-            raise TypeError("push: the combined session takes host lists for n_frames (it decides on the host whether the stack needs a second push)")
-        Tc = self.Tc
-        rmask, lmask, counts, frames = self.front._controls(n_frames, last, reset)
-        for b in range(self.B):
-            if not (frames[b] == Tc or counts[b] == 0 or (lmask[b] and frames[b] <= Tc + 2)):
-                raise ValueError("push: slot %d would yield %d frames from %d: off the schedule (first_frames = %d in an utterance's first push, chunk_frames = %d later, "
-                                 "fewer only with last)" % (b, frames[b], counts[b], self.first_frames, self.chunk_frames))
-        return rmask, lmask, counts, frames
+        super().__init__(enc, batch_size, chunk_frames)
+        self.first_frames, self.chunk_frames = self.front._sched
 
     def push(self, video, n_frames=None, last=None, reset=None):
         """video [B, Tc + 2, H, W] fp32 -> (logits [B, R, V] fp32, out_len [B] int64 on the device, inter: loss_prefix_i -> [logits chunk, lengths] as offline).
         n_frames / last / reset: host lists as VisualFrontStreamSession.push; counts must follow the schedule (every push of a slot but its last yields exactly
         chunk_frames frames; a slot may idle on 0 frames).  R = Tc / S, or Tc / S + ceil(tail / S) in a push where some slot's last chunk left a tail of 1 or 2
         frames beyond Tc (one more row for every S >= 2)."""
-        B, Tc, S = self.B, self.Tc, self.S
-        rmask, lmask, counts, frames = self._plan(n_frames, last, reset)
-        with torch.no_grad():
-            feat, _ = self.front.push(video, counts, lmask, rmask)
-            tail = [max(0, f - Tc) for f in frames]
-            y, ylen, inter = self.back.push(feat[:, :Tc], torch.tensor([min(f, Tc) for f in frames], dtype=torch.int64), rmask)
-            if not any(tail):
-                return self._head(y), ylen, inter
-            # (a captured stack's results are static: keep this push's before the second one refills them)
-            logits, ylen, inter = self._head(y).clone(), ylen.clone(), {k: [v[0].clone(), v[1].clone()] for k, v in inter.items()}
-            if self._x2 is None:
-                self._x2 = torch.zeros(B, Tc, feat.shape[2], dtype=feat.dtype, device=feat.device)
-            self._x2[:, :2].copy_(feat[:, Tc:Tc + 2])
-            y2, ylen2, inter2 = self.back.push(self._x2, torch.tensor(tail, dtype=torch.int64), None)
-            R2 = -(-max(tail) // S)
-            for k, v in inter.items():
-                inter[k] = [torch.cat([v[0], inter2[k][0][:, :R2]], dim=1), v[1] + inter2[k][1]]
-            return torch.cat([logits, self._head(y2[:, :R2].contiguous())], dim=1), ylen + ylen2, inter
+        return self._push_branch(video, n_frames, last, reset)
 
     def capture(self, device=None, frame=(88, 88)):
         """capture both halves (VisualFrontStreamSession.capture, ConformerStreamSession.capture); call it before the first push"""
-        self.front.capture(device, frame)
-        self.back.capture(device)
-        return self
+        return super().capture(device, frame=frame)
 
 
 class AudioVisualStreamSession(_StreamSession):
@@ -745,8 +721,10 @@ class AudioVisualStreamSession(_StreamSession):
         self._rows_a, self._rows_v = [0] * B, [0] * B          # rows received since the restart
         self._end_a, self._end_v = [False] * B, [False] * B
 
-    def _head(self, y):
-        return y if isinstance(self.enc.head, nn.Identity) else self.enc.head(y)
+    def _commit(self, mirrors):
+        """the host mirrors after a push: the last entry of what _plan returned for it"""
+        self._first = False
+        self._pend_a, self._pend_v, self._rows_a, self._rows_v, self._end_a, self._end_v = mirrors
 
     def schedule(self, n_video_frames, n_audio_samples):
         """-> per push (n_frames, n_samples, last_video, last_audio) for one utterance on both branch sessions' schedules: first_frames / first_samples in the first
@@ -834,24 +812,13 @@ class AudioVisualStreamSession(_StreamSession):
             inter.update(a_inter)
             ya, yv = ya.contiguous(), yv.contiguous()
             self._ensure_fuse(ya, yv)
-            self._first = False
-            self._pend_a, self._pend_v, self._rows_a, self._rows_v, self._end_a, self._end_v = mirrors
+            self._commit(mirrors)
             x, plen = self._fuse(ya, alen, yv, vlen, self._raise_flags(self.reset_flags, rmask))
             y, ylen, f_inter = self.back.push(x, plen, rmask)
-            logits = self._head(y)
-            if len(launches) > 1:
-                # (a captured stack's results are static: keep this push's before the next one refills them)
-                logits, ylen, f_inter = [logits.clone()], ylen.clone(), {k: [[v[0].clone()], v[1].clone()] for k, v in f_inter.items()}
-                for m in launches[1:]:
-                    x, plen = self._fuse(ya, self._no_rows, yv, self._no_rows, None)
-                    y, ylen2, inter2 = self.back.push(x, plen, None)
-                    n2 = -(-max(m) // self.back.S)
-                    logits.append(self._head(y[:, :n2].contiguous()))
-                    ylen = ylen + ylen2
-                    for k, v in f_inter.items():
-                        v[0].append(inter2[k][0][:, :n2].clone())
-                        v[1] = v[1] + inter2[k][1]
-                logits, f_inter = torch.cat(logits, dim=1), {k: [torch.cat(v[0], dim=1), v[1]] for k, v in f_inter.items()}
+            logits = _head(self.enc, y)
+            for m in launches[1:]:                             # a fuse launch without new rows, a push of the stack on its pairs
+                logits, ylen, f_inter = _push_again(self.back, self.enc, (logits, ylen, f_inter), lambda: self._fuse(ya, self._no_rows, yv, self._no_rows, None),
+                                                    -(-max(m) // self.back.S))
             inter.update(f_inter)
             return logits, ylen, inter
 

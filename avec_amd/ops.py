@@ -2258,13 +2258,19 @@ def audio_stream_state(B, device):
     return torch.empty(lib.raw("avec_audio_stream_state_bytes")(int(B)), dtype=torch.uint8, device=device)
 
 
-def _audio_stream_ctl(name, wave, state, n_samples, reset, last):
-    B = wave.shape[0]
-    if not (wave.dim() == 2 and wave.dtype == torch.float32 and wave.stride(1) == 1 and state.dtype == torch.uint8 and state.is_contiguous() and state.device == wave.device):
-        raise ValueError("%s: wave fp32 [B, W] with unit sample stride and a uint8 state blob on its device (got %s %s, %s)" % (name, tuple(wave.shape), wave.dtype, state.dtype))
-    _slot_vec(name, "n_samples", n_samples, B, wave.device)
-    _slot_vec(name, "reset", reset, B, wave.device, mask=True)
-    _slot_vec(name, "last", last, B, wave.device, mask=True)
+def _front_stream_ctl(name, x, state, count_name, counts, reset, last, layout_ok, layout):
+    """what the launches of a streamed front-end check of their input x (layout_ok: the caller's verdict on its layout, described by `layout`), the state blob and
+    the per-slot count / reset / last vectors"""
+    if not (layout_ok and state.dtype == torch.uint8 and state.is_contiguous() and state.device == x.device):
+        raise ValueError("%s: %s and a uint8 state blob on its device (got %s %s, %s)" % (name, layout, tuple(x.shape), x.dtype, state.dtype))
+    B = x.shape[0]
+    _slot_vec(name, count_name, counts, B, x.device)
+    _slot_vec(name, "reset", reset, B, x.device, mask=True)
+    _slot_vec(name, "last", last, B, x.device, mask=True)
+
+
+def _wave_layout(wave):
+    return wave.dim() == 2 and wave.dtype == torch.float32 and wave.stride(1) == 1, "wave fp32 [B, W] with unit sample stride"
 
 
 def mel_frames_stream(wave, window, state, n_samples=None, reset=None, last=None, *, Tmax, n_fft, win, hop, out=None):
@@ -2272,7 +2278,7 @@ def mel_frames_stream(wave, window, state, n_samples=None, reset=None, last=None
     [B * (2 Tmax + 1), win] fp32: the windowed mel frames 2 E0 - 1 .. 2 E1 - 1, zeros elsewhere; out_len [B] int64 = E1 - E0 stem frames; meta [B, 2] int64 for
     ops.audio_stem_stream).  Reads the state only: ops.audio_stream_advance ends the push.  out: (frames, out_len, meta) to write into.  No synchronisation."""
     rt.require_gpu(wave)
-    _audio_stream_ctl("mel_frames_stream", wave, state, n_samples, reset, last)
+    _front_stream_ctl("mel_frames_stream", wave, state, "n_samples", n_samples, reset, last, *_wave_layout(wave))
     B, W = wave.shape
     if out is None:
         out = (empty((B * (2 * Tmax + 1), win), torch.float32, wave), torch.empty(B, dtype=torch.int64, device=wave.device),
@@ -2319,7 +2325,7 @@ def audio_stem_stream(mel, w, bias, ss, out_len, meta, C, out=None):
 def audio_stream_advance(wave, state, n_samples=None, reset=None, last=None, *, n_fft, win, hop):
     """end of a push: the tail becomes the samples the next frames still need, n += n_samples, ended |= last, in place; the reset and last flags are cleared (consumed)"""
     rt.require_gpu(wave)
-    _audio_stream_ctl("audio_stream_advance", wave, state, n_samples, reset, last)
+    _front_stream_ctl("audio_stream_advance", wave, state, "n_samples", n_samples, reset, last, *_wave_layout(wave))
     B, W = wave.shape
     lib.audio_stream_advance(wave.data_ptr(), wave.stride(0), state.data_ptr(), state.numel(), _p(n_samples), _p(reset), _p(last), B, W, int(n_fft), int(win), int(hop), rt.stream())
     return state
@@ -2347,13 +2353,8 @@ def video_stem_w8(weight):
     return w8
 
 
-def _video_stream_ctl(name, chunk, state, n_frames, reset, last):
-    if not (chunk.dim() == 4 and chunk.dtype == torch.float32 and chunk[0].is_contiguous() and state.dtype == torch.uint8 and state.is_contiguous() and state.device == chunk.device):
-        raise ValueError("%s: chunk fp32 [B, Tin, H, W] with contiguous slots and a uint8 state blob on its device (got %s %s, %s)" % (name, tuple(chunk.shape), chunk.dtype, state.dtype))
-    B = chunk.shape[0]
-    _slot_vec(name, "n_frames", n_frames, B, chunk.device)
-    _slot_vec(name, "reset", reset, B, chunk.device, mask=True)
-    _slot_vec(name, "last", last, B, chunk.device, mask=True)
+def _video_layout(chunk):
+    return chunk.dim() == 4 and chunk.dtype == torch.float32 and chunk[0].is_contiguous(), "chunk fp32 [B, Tin, H, W] with contiguous slots"
 
 
 def video_stem_stream(chunk, state, w8, bias, ss, n_frames=None, reset=None, last=None, *, Tmax, out=None):
@@ -2362,7 +2363,7 @@ def video_stem_stream(chunk, state, w8, bias, ss, n_frames=None, reset=None, las
     BatchNorm (ss: the scale | shift of ops.bn_finalize), ReLU and the 3x3 / s2 max pool in one launch; w8 from ops.video_stem_w8.  Reads the state only:
     ops.video_stream_advance ends the push.  out: (frames, out_len) to write into.  No synchronisation."""
     rt.require_gpu(chunk)
-    _video_stream_ctl("video_stem_stream", chunk, state, n_frames, reset, last)
+    _front_stream_ctl("video_stem_stream", chunk, state, "n_frames", n_frames, reset, last, *_video_layout(chunk))
     B, Tin, H, W = chunk.shape
     adt = rt.act_dtype()
     if not (w8.dtype == adt and w8.is_contiguous() and tuple(w8.shape) == (64, 36, 8) and ss.dtype == torch.float32 and ss.numel() >= 128 and ss.is_contiguous()
@@ -2385,7 +2386,7 @@ def video_stream_advance(chunk, state, n_frames=None, reset=None, last=None):
     """end of a push: the chunk's last min(n_frames, 4) frames go into their ring slots, n += n_frames, ended |= last, in place; the reset and last flags are cleared
     (consumed).  A launch of its own behind the stem launch, whose workgroups read the ring slots it overwrites."""
     rt.require_gpu(chunk)
-    _video_stream_ctl("video_stream_advance", chunk, state, n_frames, reset, last)
+    _front_stream_ctl("video_stream_advance", chunk, state, "n_frames", n_frames, reset, last, *_video_layout(chunk))
     B, Tin, H, W = chunk.shape
     lib.video_stream_advance(rt.dt(), chunk.data_ptr(), chunk.stride(0), state.data_ptr(), state.numel(), _p(n_frames), _p(reset), _p(last), B, Tin, H, W, rt.stream())
     return state

@@ -122,10 +122,7 @@ def host_push(ses, row, reset=None):
     lv, la = [b for b, f in enumerate(lv) if f], [b for b, f in enumerate(la) if f]
     rmask, vplan, aplan, launches, mirrors = ses._plan(nf, ns, lv, la, reset)
     for front, plan in ((ses.video.front, vplan), (ses.audio.front, aplan)):
-        for b in range(ses.B):
-            n0, ended = (0, False) if rmask[b] else (front._n[b], front._ended[b])
-            front._n[b], front._ended[b] = n0 + plan[2][b], ended or plan[1][b]
+        front._commit(rmask, plan[1], plan[2])
         front._first = False
-    ses._first = False
-    ses._pend_a, ses._pend_v, ses._rows_a, ses._rows_v, ses._end_a, ses._end_v = mirrors
+    ses._commit(mirrors)
     return launches

@@ -147,8 +147,11 @@ def streamed(enc, Tc, utts=UTTS, capture=False, sync_free=False, beam=None):
         Rs.append(logits.shape[1])
         assert logits.shape[1] == lg.shape[1] and logits.shape[1] in (Tc // S, Tc // S + 1)
         ol, ll = olen.tolist(), lglen.tolist()
+        yielded = [0 if ui is None else (Tc if not fin else (at + c) // 320 + 1 - FR.ready(at)) for ui, at, c, _, fin in row]
+        tail = max(0, max(yielded) - Tc)                                # (at most 1 frame behind the stack's chunk)
+        assert tail <= 1 and logits.shape[1] == Tc // S + -(-tail // S), (pi, tail, logits.shape)
         for b, (ui, at, c, _, fin) in enumerate(row):
-            frames = 0 if ui is None else (Tc if not fin else (at + c) // 320 + 1 - FR.ready(at))
+            frames = yielded[b]
             assert ol[b] == ll[b] == -(-frames // S), (pi, b, ol, ll, frames)
             if ui is not None:
                 acc = got[b][ui]

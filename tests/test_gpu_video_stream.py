@@ -156,6 +156,8 @@ def streamed(enc, Tc, utts=UTTS, capture=False, sync_free=False, beam=None):
         raw.append((logits.clone(), olen.clone(), lg.clone(), lglen.clone()))
         Rs.append(logits.shape[1])
         assert logits.shape[1] == lg.shape[1] and logits.shape[1] in (Tc // S, Tc // S + 1)
+        tail = max(0, max(yielded(r) for r in row) - Tc)                # (at most 2 frames behind the stack's chunk)
+        assert tail <= 2 and logits.shape[1] == Tc // S + -(-tail // S), (pi, tail, logits.shape)
         ol, ll = olen.tolist(), lglen.tolist()
         for b, r in enumerate(row):
             assert ol[b] == ll[b] == -(-yielded(r) // S), (pi, b, ol, ll, yielded(r))
