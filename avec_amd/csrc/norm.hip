@@ -616,13 +616,93 @@ constexpr int BN8_UR = AVEC_BN8_UR;       // ... in the reduction pass (2 measur
 constexpr unsigned BN8_CAP_FWD = 8192, BN8_CAP_BWD = 3072;      // grid caps: the 3-operand backward pass likes fewer, longer-running blocks (115200 x 256: 41.5 -> 36.7 us,
                                                                 // 28800 x 512: 28.0 -> 21.9 us), the forward pass the opposite (32.9 vs 33.9 us); tools/bench_bn.py
 
+// ---- what the 8-wide passes do with one 16-byte chunk: one body each for the grid-stride kernels (bn_*8_kernel) and the slice-streaming kernels (bn_*8s_kernel) ---
+// Every a * b + c whose product and sum may end up in different basic blocks is an explicit fused multiply-add: the compiler contracts the rest (-ffp-contract=fast),
+// and the two tiers round alike because they run the same code.
+struct Bn8Fwd { float sc[8], sh[8], rsc[8]; };          // scale and shift of a thread's eight channels; rsc: the residual's own scale, set only with res_ss
+struct Bn8Bwd { float mu[8], rs[8], sc[8], sh[8]; };    // mean and rstd; sc, sh: set only where the pre-activation is recomputed
+struct Bn8Out { float v[8]; };                          // a forward result, returned by value: written through a reference it cost the forward kernels 4-8 VGPRs
+struct Bn8Dy { float A[8], m1[8], m2[8]; };             // dy = A (d - m1 - (v - mu) rstd m2)   with A = gamma rstd, m1 = mean(d), m2 = mean(d yhat)
+// res_ss: the residual is a raw convolution output with its own BatchNorm coefficients (projection shortcut); its shift goes into sh
+__device__ __forceinline__ void bn8_fwd_coeffs(Bn8Fwd& k, const float* __restrict__ ss, const float* __restrict__ res_ss, int C, int c) {
+  ld8<float>(ss + c, k.sc); ld8<float>(ss + C + c, k.sh);
+  if (res_ss) { float rsh[8]; ld8<float>(res_ss + c, k.rsc); ld8<float>(res_ss + C + c, rsh);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) k.sh[e] += rsh[e]; }
+}
+// act(y * scale + shift (+ residual)); under a ReLU mask[j] (mask not null) gets one bit per element: out > 0 (what the backward pass needs of `out`)
+template <typename T>
+__device__ __forceinline__ Bn8Out bn8_fwd(const Raw8<T>& ry, const Raw8<T>& rr, bool has_res, bool res_scaled, const Bn8Fwd& k, int act, unsigned char* mask, unsigned j) {
+  Bn8Out o; float (&v)[8] = o.v; ry.get(v);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(v[e], k.sc[e], k.sh[e]);
+  if (has_res) { float r[8]; rr.get(r);
+    if (res_scaled) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(r[e], k.rsc[e], v[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] += r[e]; } }
+  if (act == 1) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = swishf_(v[e]);
+  } else if (act == 2) {
+    if (mask) {
+      unsigned b = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) b |= (v[e] > 0.f ? 1u : 0u) << e;
+      mask[j] = (unsigned char)b;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+  }
+  return o;
+}
+// third operand of the backward passes: BN_SRC_NONE = none (no activation, or the pre-activation is recomputed from y), BN_SRC_OUT = the saved output, BN_SRC_BITS = the bit mask
+enum { BN_SRC_NONE = 0, BN_SRC_OUT = 1, BN_SRC_BITS = 2 };
+__device__ __forceinline__ int bn8_src(int act, const void* out, const unsigned char* mask) { return mask ? BN_SRC_BITS : (act == 2 && out) ? BN_SRC_OUT : BN_SRC_NONE; }
+__device__ __forceinline__ void bn8_bwd_coeffs(Bn8Bwd& k, const float* __restrict__ ss, bool recompute, int C, int c) {
+  ld8<float>(ss + 2 * C + c, k.mu); ld8<float>(ss + 3 * C + c, k.rs);
+  if (recompute) { ld8<float>(ss + c, k.sc); ld8<float>(ss + C + c, k.sh); }
+}
+__device__ __forceinline__ void bn8_dy_coeffs(Bn8Dy& q, const Bn8Bwd& k, const float* __restrict__ gamma, const float* __restrict__ dstats, float inv_n, int C, int c) {
+  float g[8], s1[8], s2[8]; ld8<float>(gamma + c, g); ld8<float>(dstats + c, s1); ld8<float>(dstats + C + c, s2);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { q.A[e] = g[e] * k.rs[e]; q.m1[e] = s1[e] * inv_n; q.m2[e] = s2[e] * inv_n; }
+}
+// d = dout * act'(.), v = y.  `src` is an ordinary argument: a constant in the slice kernels (it folds after inlining), derived from mask / out / act in the grid-stride ones
+template <typename T>
+__device__ __forceinline__ void bn8_bwd_d(const Raw8<T>& rd, const Raw8<T>& rv, const Raw8<T>& ro, const unsigned& mb, int src, int act, const Bn8Bwd& k, float (&d)[8], float (&v)[8]) {
+  rd.get(d); rv.get(v);
+  if (src == BN_SRC_BITS) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d[e] = (mb >> e) & 1u ? d[e] : 0.f;
+  } else if (src == BN_SRC_OUT) { float o[8]; ro.get(o);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d[e] = o[e] > 0.f ? d[e] : 0.f;
+  } else if (act == 2) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d[e] = __builtin_fmaf(v[e], k.sc[e], k.sh[e]) > 0.f ? d[e] : 0.f;
+  } else if (act == 1) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float x = __builtin_fmaf(v[e], k.sc[e], k.sh[e]), sg = sigmoidf_(x); d[e] *= sg * __builtin_fmaf(x, 1.f - sg, 1.f); }      // dswishf_
+  }
+}
+__device__ __forceinline__ void bn8_bwd_acc(float (&part)[2][8], const float (&d)[8], const float (&v)[8], const Bn8Bwd& k) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { part[0][e] += d[e]; part[1][e] += d[e] * (v[e] - k.mu[e]) * k.rs[e]; }
+}
+__device__ __forceinline__ void bn8_dy(const float (&d)[8], const float (&v)[8], const Bn8Bwd& k, const Bn8Dy& q, float (&o)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = q.A[e] * __builtin_fmaf(-((v[e] - k.mu[e]) * k.rs[e]), q.m2[e], d[e] - q.m1[e]);
+}
+
 // ---- slice-streaming skeleton of the three 8-wide passes (bf16, 256 % (C/8) == 0, < 2^31 chunks) -------------------------------------------------------
 // Every workgroup owns ONE contiguous range of 16-byte chunks (`slice`, a multiple of 256 chunks and so of C/8: a thread keeps its eight channels) and walks it in
 // units of 256 threads x P pieces.  All P loads of every input stream of a unit are issued before the first use, and the next unit's loads go out before the
 // current unit's arithmetic (two register sets) -- the access shape at which tools/ubench_hbm_stream.hip (mode 2) reads at 6.1-6.2 TB/s.  A unit that crosses the
 // slice end is guarded per piece: nothing at or beyond `end` (<= n8) is loaded or stored, the loads issued ahead included.
-// The arithmetic is that of the grid-stride kernels with every a * b + c written as the fused multiply-add the compiler contracts it to there: with the product
-// and the sum of one expression in different basic blocks it leaves some unfused, and the apply passes would no longer be bit-identical.
+// The walk is all that sets the slice kernels apart from the grid-stride ones: both call the per-chunk bodies above, so the apply passes are bit-identical.
 // What the sweeps of tools/bench_bn.py made of it (profiles/bn_slice_notes.txt): the apply passes want SHORT slices -- one unit (forward) or one and a half
 // (backward) per workgroup and as many workgroups as that takes -- so what wins there, 4-19 % per launch, is four pieces per stream in flight per thread, the
 // contiguous range and non-temporal loads, not the two-set pipeline; the reduction keeps long slices (every workgroup costs a workspace row and a share of
@@ -654,6 +734,14 @@ static inline unsigned bns_grid(long long n8, unsigned slice) { return (unsigned
 static inline unsigned bns_red_grid(long long n8) {
   long long g = n8 / (256ll * BNS_P * BNS_RED_MIN_UNITS) / 256 * 256; if (g > BNS_GRID_RED) g = BNS_GRID_RED; if (g < 256) g = 256;
   return (unsigned)g;
+}
+// workgroups and chunks per workgroup of a slice launch: pass 0 = forward apply, 1 = backward reduce (`col`: its two-pass plan, with the reduction workspace bound to
+// `st`), 2 = backward apply.  What the launches below use and what avec_bn_slice_plan reports.
+struct BnsPlan { unsigned grid, slice; ColPlan col; };
+static BnsPlan bns_plan(int pass, long long n8, int C, hipStream_t st) {
+  if (pass == 1) { const ColPlan col = ColPlan::flat<2>(bns_red_grid(n8), C, st).cap_without_ws(256); return BnsPlan{col.nslots, bns_slice(n8, col.nslots), col}; }
+  const unsigned slice = pass == 0 ? BNS_SLICE_FWD : BNS_SLICE_BWD;
+  return BnsPlan{bns_grid(n8, slice), slice, ColPlan{}};
 }
 template <int P, typename Set, typename Load, typename Use>
 __device__ __forceinline__ void bns_walk(unsigned begin, unsigned end, Load load, Use use) {
@@ -695,11 +783,7 @@ __global__ __launch_bounds__(256) void bn_apply8s_kernel(const bf16* __restrict_
                                                          const float* __restrict__ res_ss) {
   unsigned begin, end; bns_range(slice, n8, begin, end);
   const int c = (int)(threadIdx.x % ((unsigned)C >> 3)) * 8;
-  float sc[8], sh[8]; ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh);
-  float rsc[8], rsh[8];
-  if (RES && res_ss) { ld8<float>(res_ss + c, rsc); ld8<float>(res_ss + C + c, rsh);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sh[e] += rsh[e]; }
+  Bn8Fwd k; bn8_fwd_coeffs(k, ss, RES ? res_ss : nullptr, C, c);
   typedef BnsFwdSet<P, RES> Set;
   auto load = [&](Set& s, unsigned base, auto full) {
 #pragma unroll
@@ -709,72 +793,25 @@ __global__ __launch_bounds__(256) void bn_apply8s_kernel(const bf16* __restrict_
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       const unsigned j = base + threadIdx.x + p * 256; if (!decltype(full)::value && j >= end) break;
-      float v[8]; s.y[p].get(v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(v[e], sc[e], sh[e]);
-      if (RES) { float r[8]; s.r[p].get(r);
-        if (res_ss) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(r[e], rsc[e], v[e]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += r[e]; } }
-      if (act == 1) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = swishf_(v[e]);
-      } else if (act == 2) {
-        if (MASK) {
-          unsigned b = 0;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) b |= (v[e] > 0.f ? 1u : 0u) << e;
-          mask[j] = (unsigned char)b;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
-      st8<bf16>(out + (long long)j * 8, v);
+      const Bn8Out o = bn8_fwd<bf16>(s.y[p], s.r[RES ? p : 0], RES, res_ss != nullptr, k, act, MASK ? mask : nullptr, j);
+      st8<bf16>(out + (long long)j * 8, o.v);
     }
   };
   bns_walk<P, Set>(begin, end, load, use);
 }
-template <bool MASK>
-static int bns_apply_fwd(const void* y, const float* ss, const void* residual, const float* residual_ss, int act, void* out, unsigned char* mask, long long n8, int C,
-                         hipStream_t st) {
-  const unsigned grid = bns_grid(n8, BNS_SLICE_FWD);
-  if (residual) hipLaunchKernelGGL((bn_apply8s_kernel<BNS_P, true, MASK>), dim3(grid), dim3(256), 0, st, (const bf16*)y, ss, (const bf16*)residual, act, (bf16*)out,
-                                   (unsigned)n8, C, BNS_SLICE_FWD, mask, residual_ss);
-  else hipLaunchKernelGGL((bn_apply8s_kernel<BNS_P, false, MASK>), dim3(grid), dim3(256), 0, st, (const bf16*)y, ss, (const bf16*)nullptr, act, (bf16*)out,
-                          (unsigned)n8, C, BNS_SLICE_FWD, mask, (const float*)nullptr);
-  AVEC_LAUNCH_CHECK(); return 0;
-}
 
-// third operand of the backward passes: BNS_NONE = none (no activation, or the pre-activation is recomputed from y), BNS_OUT = the saved output, BNS_BITS = the bit mask
-enum { BNS_NONE = 0, BNS_OUT = 1, BNS_BITS = 2 };
-template <int P, int SRC> struct BnsBwdSet { Raw8<bf16> d[P], v[P], o[SRC == BNS_OUT ? P : 1]; unsigned mb[SRC == BNS_BITS ? P : 1]; };
+template <int P, int SRC> struct BnsBwdSet { Raw8<bf16> d[P], v[P], o[SRC == BN_SRC_OUT ? P : 1]; unsigned mb[SRC == BN_SRC_BITS ? P : 1]; };
 template <bool FULL, bool NT, int P, int SRC>
 __device__ __forceinline__ void bns_bwd_load(BnsBwdSet<P, SRC>& s, unsigned base, unsigned end, const bf16* __restrict__ dout, const bf16* __restrict__ y,
                                              const bf16* __restrict__ out, const unsigned char* __restrict__ mask) {
 #pragma unroll
   for (int p = 0; p < P; ++p) { const unsigned j = bns_chunk<FULL>(base, p, end); const long long off = (long long)j * 8; bns_ld<NT>(s.d[p], dout + off); bns_ld<NT>(s.v[p], y + off);
-    if (SRC == BNS_BITS) s.mb[p] = mask[j]; else if (SRC == BNS_OUT) bns_ld<NT>(s.o[p], out + off); }
+    if (SRC == BN_SRC_BITS) s.mb[p] = mask[j]; else if (SRC == BN_SRC_OUT) bns_ld<NT>(s.o[p], out + off); }
 }
 // d = dout * act'(.) of piece p, v = y
 template <int P, int SRC>
-__device__ __forceinline__ void bns_bwd_dr(const BnsBwdSet<P, SRC>& s, int p, int act, const float (&sc)[8], const float (&sh)[8], float (&d)[8], float (&v)[8]) {
-  s.d[p].get(d); s.v[p].get(v);
-  if (SRC == BNS_BITS) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) d[e] = (s.mb[p] >> e) & 1u ? d[e] : 0.f;
-  } else if (SRC == BNS_OUT) { float q[8]; s.o[p].get(q);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) d[e] = q[e] > 0.f ? d[e] : 0.f;
-  } else if (act == 2) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) d[e] = __builtin_fmaf(v[e], sc[e], sh[e]) > 0.f ? d[e] : 0.f;
-  } else if (act == 1) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const float x = __builtin_fmaf(v[e], sc[e], sh[e]), sg = sigmoidf_(x); d[e] *= sg * __builtin_fmaf(x, 1.f - sg, 1.f); }      // dswishf_
-  }
+__device__ __forceinline__ void bns_bwd_d(const BnsBwdSet<P, SRC>& s, int p, int act, const Bn8Bwd& k, float (&d)[8], float (&v)[8]) {
+  bn8_bwd_d<bf16>(s.d[p], s.v[p], s.o[SRC == BN_SRC_OUT ? p : 0], s.mb[SRC == BN_SRC_BITS ? p : 0], SRC, act, k, d, v);
 }
 template <int P, int SRC>
 __global__ __launch_bounds__(256) void bn_bwd_reduce8s_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ y, const bf16* __restrict__ out, const float* __restrict__ ss,
@@ -785,30 +822,20 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce8s_kernel(const bf16* __rest
   float part[2][8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) part[0][e] = part[1][e] = 0.f;
-  float mu[8], rs[8], sc[8], sh[8]; ld8<float>(ss + 2 * C + c, mu); ld8<float>(ss + 3 * C + c, rs);
-  if (SRC == BNS_NONE && act != 0) { ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh); }
+  Bn8Bwd k; bn8_bwd_coeffs(k, ss, SRC == BN_SRC_NONE && act != 0, C, c);
   typedef BnsBwdSet<P, SRC> Set;
   auto load = [&](Set& s, unsigned base, auto full) { bns_bwd_load<decltype(full)::value, false, P, SRC>(s, base, end, dout, y, out, mask); };
   auto use = [&](Set& s, unsigned base, auto full) {
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       if (!decltype(full)::value && base + threadIdx.x + p * 256 >= end) break;
-      float d[8], v[8]; bns_bwd_dr<P, SRC>(s, p, act, sc, sh, d, v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { part[0][e] += d[e]; part[1][e] += d[e] * (v[e] - mu[e]) * rs[e]; }
+      float d[8], v[8]; bns_bwd_d<P, SRC>(s, p, act, k, d, v);
+      bn8_bwd_acc(part, d, v, k);
     }
   };
   bns_walk<P, Set>(begin, end, load, use);
   float* const dst[2] = {dstats, dstats + C};
   colreduce8_atomic<2>(part, dst, m, ws);
-}
-// the bit-mask variant only: with `out` or a recomputed pre-activation the slice form measured 0-6 % slower than bn_bwd_reduce8_kernel at every stage
-static int bns_bwd_reduce_mask(const void* dout, const void* y, const unsigned char* mask, const float* ss, float* dstats, long long n8, int C, hipStream_t st) {
-  const ColPlan plan = ColPlan::flat<2>(bns_red_grid(n8), C, st).cap_without_ws(256);
-  hipLaunchKernelGGL((bn_bwd_reduce8s_kernel<BNS_P, BNS_BITS>), dim3(plan.nslots), dim3(256), 0, st, (const bf16*)dout, (const bf16*)y, (const bf16*)nullptr, ss, 2,
-                     dstats, (unsigned)n8, C, bns_slice(n8, plan.nslots), plan.ws, mask);
-  AVEC_LAUNCH_CHECK();
-  return plan.finish({dstats, dstats + C}, C, st);
 }
 template <int P, int SRC>
 __global__ __launch_bounds__(256) void bn_bwd_apply8s_kernel(const bf16* __restrict__ dout, const bf16* __restrict__ y, const bf16* __restrict__ out, const float* __restrict__ ss,
@@ -819,11 +846,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply8s_kernel(const bf16* __restr
   if (blockIdx.x == 0 && dgamma) for (int cc = threadIdx.x; cc < C; cc += 256) { atomicAdd(dgamma + cc, dstats[C + cc]); atomicAdd(dbeta + cc, dstats[cc]); }
   unsigned begin, end; bns_range(slice, n8, begin, end);
   const int c = (int)(threadIdx.x % ((unsigned)C >> 3)) * 8;
-  float mu[8], rs[8], A[8], m1[8], m2[8], sc[8], sh[8];
-  { float g[8], s1[8], s2[8]; ld8<float>(ss + 2 * C + c, mu); ld8<float>(ss + 3 * C + c, rs); ld8<float>(gamma + c, g); ld8<float>(dstats + c, s1); ld8<float>(dstats + C + c, s2);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { A[e] = g[e] * rs[e]; m1[e] = s1[e] * inv_n; m2[e] = s2[e] * inv_n; } }
-  if (SRC == BNS_NONE && act != 0) { ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh); }
+  Bn8Bwd k; bn8_bwd_coeffs(k, ss, SRC == BN_SRC_NONE && act != 0, C, c);
+  Bn8Dy q; bn8_dy_coeffs(q, k, gamma, dstats, inv_n, C, c);
   typedef BnsBwdSet<P, SRC> Set;
   auto load = [&](Set& s, unsigned base, auto full) { bns_bwd_load<decltype(full)::value, true, P, SRC>(s, base, end, dout, y, out, mask); };
   auto use = [&](Set& s, unsigned base, auto full) {
@@ -831,35 +855,21 @@ __global__ __launch_bounds__(256) void bn_bwd_apply8s_kernel(const bf16* __restr
     for (int p = 0; p < P; ++p) {
       const unsigned j = base + threadIdx.x + p * 256; if (!decltype(full)::value && j >= end) break;
       const long long off = (long long)j * 8;
-      float d[8], v[8], o[8]; bns_bwd_dr<P, SRC>(s, p, act, sc, sh, d, v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = A[e] * __builtin_fmaf(-((v[e] - mu[e]) * rs[e]), m2[e], d[e] - m1[e]);
+      float d[8], v[8], o[8]; bns_bwd_d<P, SRC>(s, p, act, k, d, v);
+      bn8_dy(d, v, k, q, o);
       st8<bf16>(dy + off, o);
       if (dres) st8<bf16>(dres + off, d);
     }
   };
   bns_walk<P, Set>(begin, end, load, use);
 }
-static int bns_bwd_apply(const void* dout, const void* y, const void* out, const unsigned char* mask, const float* ss, const float* gamma, const float* dstats,
-                         const float* count_ptr, float count, int act, void* dy, void* dres, float* dgamma, float* dbeta, long long n8, int C, hipStream_t st) {
-#define BNS_BWD(SRC) hipLaunchKernelGGL((bn_bwd_apply8s_kernel<BNS_P, SRC>), dim3(bns_grid(n8, BNS_SLICE_BWD)), dim3(256), 0, st, (const bf16*)dout, (const bf16*)y, (const bf16*)out, ss, gamma, dstats, \
-                                        count_ptr, count, act, (bf16*)dy, (bf16*)dres, dgamma, dbeta, (unsigned)n8, C, BNS_SLICE_BWD, mask)
-  if (mask) BNS_BWD(BNS_BITS); else if (act == 2 && out) BNS_BWD(BNS_OUT); else BNS_BWD(BNS_NONE);
-#undef BNS_BWD
-  AVEC_LAUNCH_CHECK(); return 0;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void bn_apply8_kernel(const T* __restrict__ y, const float* __restrict__ ss, const T* __restrict__ res, int act,
-                                                        T* __restrict__ out, unsigned n8, int C, unsigned char* __restrict__ mask = nullptr,
-                                                        const float* __restrict__ res_ss = nullptr) {
+                                                        T* __restrict__ out, unsigned n8, int C, unsigned char* __restrict__ mask, const float* __restrict__ res_ss) {
   const unsigned C8 = (unsigned)C >> 3, stride = gridDim.x * 256, i0 = blockIdx.x * 256 + threadIdx.x;
   const int c = (int)(i0 % C8) * 8;
-  float sc[8], sh[8]; ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh);
-  float rsc[8], rsh[8];                                   // res_ss: the residual is a raw convolution output with its own BatchNorm coefficients (projection shortcut)
-  if (res_ss) { ld8<float>(res_ss + c, rsc); ld8<float>(res_ss + C + c, rsh);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sh[e] += rsh[e]; }
+  Bn8Fwd k; bn8_fwd_coeffs(k, ss, res_ss, C, c);
   for (unsigned i = i0; i < n8; i += stride * BN8_U) {
     Raw8<T> ry[BN8_U], rr[BN8_U];
 #pragma unroll
@@ -867,52 +877,36 @@ __global__ __launch_bounds__(256) void bn_apply8_kernel(const T* __restrict__ y,
 #pragma unroll
     for (int u = 0; u < BN8_U; ++u) {
       const unsigned j = i + u * stride; if (j >= n8) break;
-      float v[8]; ry[u].get(v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + sh[e];
-      if (res) { float r[8]; rr[u].get(r);
-        if (res_ss) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += r[e] * rsc[e];
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += r[e]; } }
-      if (act == 1) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = swishf_(v[e]);
-      } else if (act == 2) {
-        if (mask) {                      // one bit per element: out > 0 (what the backward pass needs of `out`)
-          unsigned b = 0;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) b |= (v[e] > 0.f ? 1u : 0u) << e;
-          mask[j] = (unsigned char)b;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
-      st8<T>(out + (long long)j * 8, v);
+      const Bn8Out o = bn8_fwd<T>(ry[u], rr[u], res != nullptr, res_ss != nullptr, k, act, mask, j);
+      st8<T>(out + (long long)j * 8, o.v);
     }
   }
+}
+// the three host ladders: the slice kernels where bns_ok, else the 8-wide grid-stride kernels, else (C % 8 != 0 or >= 2^31 chunks; never with a mask) the 4-wide ones
+static int bn_apply_fwd_impl(int dtype, const void* y, const float* ss, const void* res, const float* res_ss, int act, void* out, unsigned char* mask, long long M, int C,
+                             hipStream_t st) {
+  const long long n8 = M * C / 8;
+  if (bns_ok(dtype, M, C)) {
+    const BnsPlan p = bns_plan(0, n8, C, st);
+#define BNS_FWD(RES, MASK) hipLaunchKernelGGL((bn_apply8s_kernel<BNS_P, RES, MASK>), dim3(p.grid), dim3(256), 0, st, (const bf16*)y, ss, (const bf16*)res, act, (bf16*)out, (unsigned)n8, C, p.slice, mask, res_ss)
+    if (res) { if (mask) BNS_FWD(true, true); else BNS_FWD(true, false); } else { if (mask) BNS_FWD(false, true); else BNS_FWD(false, false); }
+#undef BNS_FWD
+  } else if (C % 8 == 0 && n8 < (1ll << 31)) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply8_kernel<T>, dim3(bn8_blocks(n8, C, BN8_CAP_FWD)), dim3(256), 0, st, (const T*)y, ss, (const T*)res, act, (T*)out, (unsigned)n8, C, mask, res_ss));
+  } else {
+    long long n4 = M * C / 4; long long nb = (n4 + 255) / 256; if (nb > 4096) nb = 4096;
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, (const T*)y, ss, (const T*)res, act, (T*)out, n4, C));
+  }
+  AVEC_LAUNCH_CHECK(); return 0;
 }
 extern "C" int avec_bn_apply_fwd_mask(int dtype, const void* y, const float* ss, const void* residual, const float* residual_ss, void* out, unsigned char* mask, long long M, int C,
                                       hipStream_t st) {
   AVEC_CHECK_ARG(y && ss && out && mask && M > 0 && C > 0 && C % 8 == 0 && M * C / 8 < (1ll << 31) && (residual || !residual_ss), "bn_apply_fwd_mask: bad arguments (C %% 8 == 0, M*C < 2^34)");
-  if (bns_ok(dtype, M, C)) return bns_apply_fwd<true>(y, ss, residual, residual_ss, 2, out, mask, M * C / 8, C, st);
-  const long long n8 = M * C / 8; const unsigned nb8 = bn8_blocks(n8, C, BN8_CAP_FWD);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply8_kernel<T>, dim3((unsigned)nb8), dim3(256), 0, st, (const T*)y, ss, (const T*)residual, 2, (T*)out, (unsigned)n8, C, mask, residual_ss));
-  AVEC_LAUNCH_CHECK(); return 0;
+  return bn_apply_fwd_impl(dtype, y, ss, residual, residual_ss, 2, out, mask, M, C, st);
 }
 extern "C" int avec_bn_apply_fwd(int dtype, const void* y, const float* ss, const void* residual, int act, void* out, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(y && ss && out && M > 0 && C > 0 && C % 4 == 0, "bn_apply_fwd: bad arguments");
-  if (bns_ok(dtype, M, C)) return bns_apply_fwd<false>(y, ss, residual, nullptr, act, out, nullptr, M * C / 8, C, st);
-  if (C % 8 == 0 && M * C / 8 < (1ll << 31)) {
-    const long long n8 = M * C / 8; const unsigned nb8 = bn8_blocks(n8, C, BN8_CAP_FWD);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply8_kernel<T>, dim3((unsigned)nb8), dim3(256), 0, st, (const T*)y, ss, (const T*)residual, act, (T*)out, (unsigned)n8, C));
-    AVEC_LAUNCH_CHECK(); return 0;
-  }
-  long long n4 = M * C / 4; long long nb = (n4 + 255) / 256; if (nb > 4096) nb = 4096;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, (const T*)y, ss, (const T*)residual, act, (T*)out, n4, C));
-  AVEC_LAUNCH_CHECK(); return 0;
+  return bn_apply_fwd_impl(dtype, y, ss, residual, nullptr, act, out, nullptr, M, C, st);
 }
 
 // dr = dout * act'(.)   (ReLU: mask from saved output `out`; Swish: from pre = y*scale+shift)
@@ -942,65 +936,55 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
 // 8-wide flat variant (C % 8 == 0): every lane busy for narrow C, 16 B accesses
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce8_kernel(const T* __restrict__ dout, const T* __restrict__ y, const T* __restrict__ out, const float* __restrict__ ss,
-                                                             int act, float* dstats, long long M, int C, ColWs ws, const unsigned char* __restrict__ mask = nullptr) {
+                                                             int act, float* dstats, long long M, int C, ColWs ws, const unsigned char* __restrict__ mask) {
   const Col8 m = col8_map(C);
   float part[2][8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) part[0][e] = part[1][e] = 0.f;
   if (m.active) {
-    const int c = m.l * 8;
-    float mu[8], rs[8], sc[8], sh[8]; ld8<float>(ss + 2 * C + c, mu); ld8<float>(ss + 3 * C + c, rs);
-    if (act == 1 || (act == 2 && !out && !mask)) { ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh); }
+    const int c = m.l * 8, src = bn8_src(act, out, mask);
+    Bn8Bwd k; bn8_bwd_coeffs(k, ss, src == BN_SRC_NONE && act != 0, C, c);
     const long long rstride = (long long)gridDim.x * m.R;
     for (long long row = (long long)blockIdx.x * m.R + m.r; row < M; row += rstride * BN8_UR) {
       Raw8<T> rd[BN8_UR], rv[BN8_UR], ro[BN8_UR]; unsigned mb[BN8_UR];
 #pragma unroll
       for (int u = 0; u < BN8_UR; ++u) { const long long r = row + u * rstride; if (r < M) { const long long off = r * C + c; rd[u].load(dout + off); rv[u].load(y + off);
-        if (mask) mb[u] = mask[off >> 3]; else if (act == 2 && out) ro[u].load(out + off); } }
+        if (src == BN_SRC_BITS) mb[u] = mask[off >> 3]; else if (src == BN_SRC_OUT) ro[u].load(out + off); } }
 #pragma unroll
       for (int u = 0; u < BN8_UR; ++u) {
         if (row + u * rstride >= M) break;
-        float d[8], v[8]; rd[u].get(d); rv[u].get(v);
-        if (mask) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) d[e] = (mb[u] >> e) & 1u ? d[e] : 0.f; }
-        else if (act == 2 && out) { float o[8]; ro[u].get(o);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) d[e] = o[e] > 0.f ? d[e] : 0.f; }
-        else if (act == 2) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) d[e] = (v[e] * sc[e] + sh[e]) > 0.f ? d[e] : 0.f; }
-        else if (act == 1) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) d[e] *= dswishf_(v[e] * sc[e] + sh[e]); }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { part[0][e] += d[e]; part[1][e] += d[e] * (v[e] - mu[e]) * rs[e]; }
+        float d[8], v[8]; bn8_bwd_d<T>(rd[u], rv[u], ro[u], mb[u], src, act, k, d, v);
+        bn8_bwd_acc(part, d, v, k);
       }
     }
   }
   float* const dst[2] = {dstats, dstats + C};
   colreduce8_atomic<2>(part, dst, m, ws);
 }
-extern "C" int avec_bn_bwd_reduce_mask(int dtype, const void* dout, const void* y, const unsigned char* mask, const float* ss, float* dstats, long long M, int C, hipStream_t st) {
-  AVEC_CHECK_ARG(dout && y && mask && ss && dstats && M > 0 && col8_ok(C), "bn_bwd_reduce_mask: bad arguments");
-  if (bns_ok(dtype, M, C)) return bns_bwd_reduce_mask(dout, y, mask, ss, dstats, M * C / 8, C, st);
-  const ColPlan plan = ColPlan::flat8<2>(M, C, st);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce8_kernel<T>, dim3(plan.nslots), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)nullptr, ss, 2, dstats, M, C, plan.ws, mask));
+// slice rung: the bit-mask variant only -- with `out` or a recomputed pre-activation the slice form measured 0-6 % slower than bn_bwd_reduce8_kernel at every stage
+static int bn_bwd_reduce_impl(int dtype, const void* dout, const void* y, const void* out, const unsigned char* mask, const float* ss, int act, float* dstats, long long M, int C,
+                              hipStream_t st) {
+  ColPlan plan;
+  if (mask && bns_ok(dtype, M, C)) {
+    const long long n8 = M * C / 8; const BnsPlan p = bns_plan(1, n8, C, st); plan = p.col;
+    hipLaunchKernelGGL((bn_bwd_reduce8s_kernel<BNS_P, BN_SRC_BITS>), dim3(p.grid), dim3(256), 0, st, (const bf16*)dout, (const bf16*)y, (const bf16*)out, ss, act, dstats, (unsigned)n8, C, p.slice, plan.ws, mask);
+  } else if (col8_ok(C)) {
+    plan = ColPlan::flat8<2>(M, C, st);
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce8_kernel<T>, dim3(plan.nslots), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, act, dstats, M, C, plan.ws, mask));
+  } else {
+    const dim3 grid = col_grid(M, C); plan = ColPlan::grid<2>(grid, C, st);
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, grid, dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, act, dstats, M, C, plan.ws));
+  }
   AVEC_LAUNCH_CHECK();
   return plan.finish({dstats, dstats + C}, C, st);
 }
+extern "C" int avec_bn_bwd_reduce_mask(int dtype, const void* dout, const void* y, const unsigned char* mask, const float* ss, float* dstats, long long M, int C, hipStream_t st) {
+  AVEC_CHECK_ARG(dout && y && mask && ss && dstats && M > 0 && col8_ok(C), "bn_bwd_reduce_mask: bad arguments");
+  return bn_bwd_reduce_impl(dtype, dout, y, nullptr, mask, ss, 2, dstats, M, C, st);
+}
 extern "C" int avec_bn_bwd_reduce(int dtype, const void* dout, const void* y, const void* out, const float* ss, int act, float* dstats, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(dout && y && ss && dstats && M > 0 && C % 4 == 0, "bn_bwd_reduce: bad arguments");
-  if (col8_ok(C)) {
-    const ColPlan plan = ColPlan::flat8<2>(M, C, st);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce8_kernel<T>, dim3(plan.nslots), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, act, dstats, M, C, plan.ws));
-    AVEC_LAUNCH_CHECK();
-    return plan.finish({dstats, dstats + C}, C, st);
-  }
-  dim3 grid = col_grid(M, C); const ColPlan plan = ColPlan::grid<2>(grid, C, st);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, grid, dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, act, dstats, M, C, plan.ws));
-  AVEC_LAUNCH_CHECK();
-  return plan.finish({dstats, dstats + C}, C, st);
+  return bn_bwd_reduce_impl(dtype, dout, y, out, nullptr, ss, act, dstats, M, C, st);
 }
 // dy = gamma*rstd*(dr - mean(dr) - yhat*mean(dr*yhat)); optional dres = dr; block 0 adds dgamma/dbeta
 template <typename T>
@@ -1023,68 +1007,57 @@ template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply8_kernel(const T* __restrict__ dout, const T* __restrict__ y, const T* __restrict__ out, const float* __restrict__ ss,
                                                             const float* __restrict__ gamma, const float* __restrict__ dstats, const float* count_ptr, float count, int act,
                                                             T* __restrict__ dy, T* __restrict__ dres, float* dgamma, float* dbeta, unsigned n8, int C,
-                                                            const unsigned char* __restrict__ mask = nullptr) {
+                                                            const unsigned char* __restrict__ mask) {
   const float inv_n = 1.f / (count_ptr ? *count_ptr : count);
   if (blockIdx.x == 0 && dgamma) for (int c = threadIdx.x; c < C; c += 256) { atomicAdd(dgamma + c, dstats[C + c]); atomicAdd(dbeta + c, dstats[c]); }
   const unsigned C8 = (unsigned)C >> 3, stride = gridDim.x * 256, i0 = blockIdx.x * 256 + threadIdx.x;
-  const int c = (int)(i0 % C8) * 8;
-  // dy = A (d - m1 - (v - mu) rstd m2)   with A = gamma rstd, m1 = mean(d), m2 = mean(d yhat)
-  float mu[8], rs[8], A[8], m1[8], m2[8], sc[8], sh[8];
-  { float g[8], s1[8], s2[8]; ld8<float>(ss + 2 * C + c, mu); ld8<float>(ss + 3 * C + c, rs); ld8<float>(gamma + c, g); ld8<float>(dstats + c, s1); ld8<float>(dstats + C + c, s2);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { A[e] = g[e] * rs[e]; m1[e] = s1[e] * inv_n; m2[e] = s2[e] * inv_n; } }
-  const bool recompute = act != 0 && !(act == 2 && (out || mask));
-  if (recompute) { ld8<float>(ss + c, sc); ld8<float>(ss + C + c, sh); }
+  const int c = (int)(i0 % C8) * 8, src = bn8_src(act, out, mask);
+  Bn8Bwd k; bn8_bwd_coeffs(k, ss, src == BN_SRC_NONE && act != 0, C, c);
+  Bn8Dy q; bn8_dy_coeffs(q, k, gamma, dstats, inv_n, C, c);
   for (unsigned i = i0; i < n8; i += stride * BN8_U) {
     Raw8<T> rd[BN8_U], rv[BN8_U], ro[BN8_U]; unsigned mb[BN8_U];
 #pragma unroll
     for (int u = 0; u < BN8_U; ++u) { const unsigned j = i + u * stride; if (j < n8) { const long long off = (long long)j * 8; rd[u].load(dout + off); rv[u].load(y + off);
-      if (mask) mb[u] = mask[j]; else if (act == 2 && out) ro[u].load(out + off); } }
+      if (src == BN_SRC_BITS) mb[u] = mask[j]; else if (src == BN_SRC_OUT) ro[u].load(out + off); } }
 #pragma unroll
     for (int u = 0; u < BN8_U; ++u) {
       const unsigned j = i + u * stride; if (j >= n8) break;
       const long long off = (long long)j * 8;
-      float d[8], v[8], o[8]; rd[u].get(d); rv[u].get(v);
-      if (mask) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) d[e] = (mb[u] >> e) & 1u ? d[e] : 0.f;
-      } else if (act == 2 && out) { float q[8]; ro[u].get(q);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) d[e] = q[e] > 0.f ? d[e] : 0.f;
-      } else if (act != 0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float pre = v[e] * sc[e] + sh[e]; d[e] = act == 1 ? d[e] * dswishf_(pre) : (pre > 0.f ? d[e] : 0.f); }
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = A[e] * (d[e] - m1[e] - (v[e] - mu[e]) * rs[e] * m2[e]);
+      float d[8], v[8], o[8]; bn8_bwd_d<T>(rd[u], rv[u], ro[u], mb[u], src, act, k, d, v);
+      bn8_dy(d, v, k, q, o);
       st8<T>(dy + off, o);
       if (dres) st8<T>(dres + off, d);
     }
   }
 }
+static int bn_bwd_apply_impl(int dtype, const void* dout, const void* y, const void* out, const unsigned char* mask, const float* ss, const float* gamma, const float* dstats,
+                             const float* count_ptr, float count, int act, void* dy, void* dres, float* dgamma, float* dbeta, long long M, int C, hipStream_t st) {
+  const long long n8 = M * C / 8;
+  if (bns_ok(dtype, M, C)) {
+    const BnsPlan p = bns_plan(2, n8, C, st);
+#define BNS_BWD(SRC) hipLaunchKernelGGL((bn_bwd_apply8s_kernel<BNS_P, SRC>), dim3(p.grid), dim3(256), 0, st, (const bf16*)dout, (const bf16*)y, (const bf16*)out, ss, gamma, dstats, \
+                                        count_ptr, count, act, (bf16*)dy, (bf16*)dres, dgamma, dbeta, (unsigned)n8, C, p.slice, mask)
+    if (mask) BNS_BWD(BN_SRC_BITS); else if (act == 2 && out) BNS_BWD(BN_SRC_OUT); else BNS_BWD(BN_SRC_NONE);
+#undef BNS_BWD
+  } else if (C % 8 == 0 && n8 < (1ll << 31)) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply8_kernel<T>, dim3(bn8_blocks(n8, C, BN8_CAP_BWD)), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, gamma, dstats,
+                                         count_ptr, count, act, (T*)dy, (T*)dres, dgamma, dbeta, (unsigned)n8, C, mask));
+  } else {
+    long long n4 = M * C / 4; long long nb = (n4 + 255) / 256; if (nb > 4096) nb = 4096;
+    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, gamma, dstats,
+                                         count_ptr, count, act, (T*)dy, (T*)dres, dgamma, dbeta, n4, C));
+  }
+  AVEC_LAUNCH_CHECK(); return 0;
+}
 extern "C" int avec_bn_bwd_apply_mask(int dtype, const void* dout, const void* y, const unsigned char* mask, const float* ss, const float* gamma, const float* dstats,
                                       const float* count_ptr, float count, void* dy, void* dres, float* dgamma, float* dbeta, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(dout && y && mask && ss && gamma && dstats && dy && M > 0 && C % 8 == 0 && M * C / 8 < (1ll << 31), "bn_bwd_apply_mask: bad arguments");
-  if (bns_ok(dtype, M, C)) return bns_bwd_apply(dout, y, nullptr, mask, ss, gamma, dstats, count_ptr, count, 2, dy, dres, dgamma, dbeta, M * C / 8, C, st);
-  const long long n8 = M * C / 8; const unsigned nb8 = bn8_blocks(n8, C, BN8_CAP_BWD);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply8_kernel<T>, dim3((unsigned)nb8), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)nullptr, ss, gamma, dstats,
-                                       count_ptr, count, 2, (T*)dy, (T*)dres, dgamma, dbeta, (unsigned)n8, C, mask));
-  AVEC_LAUNCH_CHECK(); return 0;
+  return bn_bwd_apply_impl(dtype, dout, y, nullptr, mask, ss, gamma, dstats, count_ptr, count, 2, dy, dres, dgamma, dbeta, M, C, st);
 }
 extern "C" int avec_bn_bwd_apply(int dtype, const void* dout, const void* y, const void* out, const float* ss, const float* gamma, const float* dstats,
                                  const float* count_ptr, float count, int act, void* dy, void* dres, float* dgamma, float* dbeta, long long M, int C, hipStream_t st) {
   AVEC_CHECK_ARG(dout && y && ss && gamma && dstats && dy && M > 0 && C % 4 == 0, "bn_bwd_apply: bad arguments");
-  if (bns_ok(dtype, M, C)) return bns_bwd_apply(dout, y, out, nullptr, ss, gamma, dstats, count_ptr, count, act, dy, dres, dgamma, dbeta, M * C / 8, C, st);
-  if (C % 8 == 0 && M * C / 8 < (1ll << 31)) {
-    const long long n8 = M * C / 8; const unsigned nb8 = bn8_blocks(n8, C, BN8_CAP_BWD);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply8_kernel<T>, dim3((unsigned)nb8), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, gamma, dstats,
-                                         count_ptr, count, act, (T*)dy, (T*)dres, dgamma, dbeta, (unsigned)n8, C));
-    AVEC_LAUNCH_CHECK(); return 0;
-  }
-  long long n4 = M * C / 4; long long nb = (n4 + 255) / 256; if (nb > 4096) nb = 4096;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3((unsigned)nb), dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)out, ss, gamma, dstats,
-                                       count_ptr, count, act, (T*)dy, (T*)dres, dgamma, dbeta, n4, C));
-  AVEC_LAUNCH_CHECK(); return 0;
+  return bn_bwd_apply_impl(dtype, dout, y, out, nullptr, ss, gamma, dstats, count_ptr, count, act, dy, dres, dgamma, dbeta, M, C, st);
 }
 // what the slice-streaming path does with an (M, C) bf16 tensor, for tests and tools: pass 0 = forward apply, 1 = backward reduce by the bit mask, 2 = backward apply.
 // Returns 1 when such a launch takes the slice path (0: the grid-stride kernels) and stores the pieces per thread and unit, the workgroups and the chunks per
@@ -1093,12 +1066,9 @@ extern "C" int avec_bn_slice_mode(int mode) { const int old = bns_mode(); if (mo
 extern "C" int avec_bn_slice_plan(int pass, long long M, int C, int* P, unsigned* grid, unsigned* slice, hipStream_t st) {
   if (P) *P = BNS_P;
   if (M <= 0 || C <= 0 || C % 8 != 0 || pass < 0 || pass > 2 || !bns_ok(AVEC_BF16, M, C)) return 0;
-  const long long n8 = M * C / 8;
-  unsigned g, sl;
-  if (pass == 1) { g = ColPlan::flat<2>(bns_red_grid(n8), C, st).cap_without_ws(256).nslots; sl = bns_slice(n8, g); }
-  else { sl = pass == 0 ? BNS_SLICE_FWD : BNS_SLICE_BWD; g = bns_grid(n8, sl); }
-  if (grid) *grid = g;
-  if (slice) *slice = sl;
+  const BnsPlan p = bns_plan(pass, M * C / 8, C, st);
+  if (grid) *grid = p.grid;
+  if (slice) *slice = p.slice;
   return 1;
 }
 
