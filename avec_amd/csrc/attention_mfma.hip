@@ -12,28 +12,16 @@
 // bijection of the row bits chosen so that BOTH the ds_read_b128 operand reads (lanes = rows) and the transposed reads (4 rows x 32 B
 // blocks) are bank-conflict free:  pitch 128: chunk ^= ((row>>1)&1)<<2 | (row>>2)&3;   pitch 256: chunk ^= (row&3)<<2 | (row>>2)&3.
 #include "attention.h"
+#include "wave_prims.h"
 #ifndef AVEC_ATTN_ABL
 #define AVEC_ATTN_ABL 0
 #endif
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef short v4s_t __attribute__((ext_vector_type(4)));
 
 static constexpr int NTMAX = 12;     // key tiles of 32 held in registers: kernels are instantiated for NTM = 7 (T <= 224, two workgroups per CU) and 12 (T <= 384)
 static constexpr int CTMAX = 3;      // channel tiles of 32 (d <= 96)
 
 template <int PITCH> __device__ __forceinline__ int aswz(int row) {
   return PITCH == 128 ? ((((row >> 1) & 1) << 2) | ((row >> 2) & 3)) : (((row & 3) << 2) | ((row >> 2) & 3));
-}
-__device__ __forceinline__ f32x16 mma(const chunk16& a, const chunk16& b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ chunk16 tr8(const char* p0, const char* p1) {
-  typedef __attribute__((address_space(3))) v4s_t* lp_t;
-  const v4s_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p0), b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p1);
-  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
-  chunk16 f; f.w[0] = ua.x; f.w[1] = ua.y; f.w[2] = ub.x; f.w[3] = ub.y; return f;
 }
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f32x2_to_bf16x2(lo, hi); }
 
@@ -60,7 +48,7 @@ __device__ __forceinline__ void stage_rows(char* dst, const bf16* src, long long
   }
 }
 
-// The same image by LDS-DMA (global_load_lds_dwordx4: 16 B per lane, no VGPR round trip, every instruction of a wave in flight at once).  Round 4: the register
+// The same image by LDS-DMA (glds16, wave_prims.h: 16 B per lane, no VGPR round trip, every instruction of a wave in flight at once).  Round 4: the register
 // path above was 8-15 us of a 18-22 us forward launch -- two waves per workgroup, one per SIMD, a load -> wait -> store round trip per 16 bytes.  An instruction
 // writes 64 consecutive 16-byte slots = 8 (pitch 128) or 4 (pitch 256) image rows; lane l owns slot l, i.e. (row l / SLOTS, position l % SLOTS), and fetches the
 // logical chunk that the swizzle puts there.  The DMA has no fill value, so:
@@ -69,12 +57,7 @@ __device__ __forceinline__ void stage_rows(char* dst, const bf16* src, long long
 //   * channels d .. dpad-1 of a row hold whatever follows the head in memory; the caller zeroes them in the Q / dO tiles only (zero_pad_channels) -- K, V and E
 //     meet them only in products contracted over the channels with Q or dO, or in output channels that are never stored;
 //   * the one 16-byte read that would run past the END of the tensor (last row, last head, d % 8 != 0) is replaced by a zero chunk + element loads.
-// Source addresses need 2-byte alignment only (tools/glds_align_probe.hip: any even offset copies right).
-__device__ __forceinline__ void attn_glds16(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-__device__ __attribute__((aligned(64))) unsigned char attn_zero16[64];
+// Source addresses need 2-byte alignment only (rows of odd heads start at any even offset).
 
 // rows [row0, row0 + nrows) of `src` (row stride ld elements, `last_row` = last row of the whole tensor, rowbytes = bytes of a tensor row counted from src's column)
 // -> image at LDS byte address lds_img; nrows is a multiple of 8; wave w of NW issues instructions w, w + NW, ...
@@ -122,7 +105,7 @@ __device__ __forceinline__ void stage_rows_dma(unsigned lds_img, char* img, cons
         int gr = row0 + k * RPI + rg; gr = gr < 0 ? 0 : (gr >= limit ? limit - 1 : gr);
         const char* p = (const char*)src + ((unsigned)gr * ldb + coff[v]);
         const bool past = gr == lastr && cpast[v];
-        attn_glds16(past ? (const void*)attn_zero16 : (const void*)p, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_img + k * 1024)));
+        glds16(past ? (const void*)avec_zero16 : (const void*)p, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_img + k * 1024)));
       }
     }
   }
@@ -188,7 +171,7 @@ __device__ __forceinline__ float scores(f32x16 (&S)[NTM], const char* Ks, const 
     for (int kk = 0; kk < dks; ++kk) {
       const chunk16 fa = *(const chunk16*)(erow + (((2 * kk + hf) ^ swr) << 4));
       const chunk16 fb = *(const chunk16*)(qrow + (((2 * kk + hf) ^ swr) << 4));
-      R = mma(fa, fb, R);
+      R = mma16(fa, fb, R);
     }
     float* slot = ring + (et & 1) * 1024;
 #pragma unroll
@@ -203,7 +186,7 @@ __device__ __forceinline__ float scores(f32x16 (&S)[NTM], const char* Ks, const 
       for (int kk = 0; kk < dks; ++kk) {
         const chunk16 fa = *(const chunk16*)(krow + (((2 * kk + hf) ^ swr) << 4));
         const chunk16 fb = *(const chunk16*)(qrow + (((2 * kk + hf) ^ swr) << 4));
-        S[jt] = mma(fa, fb, S[jt]);
+        S[jt] = mma16(fa, fb, S[jt]);
       }
       rel_tile(jt + 1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // LDS is in-order per wave: the ring writes above are visible to the reads below
@@ -291,7 +274,6 @@ __global__ __launch_bounds__(ALIAS ? 128 : 256) void attn_mfma_fwd_kernel(AttnAr
   const bf16* vp = (const bf16*)a.v + (long long)b * Tn * a.ld + h * d;
   const bf16* ep = (const bf16*)a.e + h * d;
   {
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)sm;
     const int wv = __builtin_amdgcn_readfirstlane(w);
     const long long lastq = (long long)(a.B - 1 - b) * Tn + Tn - 1;      // last row of the q / k / v tensors, counted from this batch element's first row
@@ -351,7 +333,7 @@ __global__ __launch_bounds__(ALIAS ? 128 : 256) void attn_mfma_fwd_kernel(AttnAr
         for (int e = 0; e < 4; ++e) pb.w[e] = pack2(S[jt][8 * s + 2 * e], S[jt][8 * s + 2 * e + 1]);
         const char* vb = Vs + (32 * jt + 16 * s) * PITCH;
 #pragma unroll
-        for (int ct = 0; ct < CTMAX; ++ct) if (ct < G.CT) O[ct] = mma(tr8(vb + offv[ct][0], vb + offv[ct][1]), pb, O[ct]);
+        for (int ct = 0; ct < CTMAX; ++ct) if (ct < G.CT) O[ct] = mma16(lds_tr8(vb + offv[ct][0], vb + offv[ct][1]), pb, O[ct]);
       }
     }
   }
@@ -378,7 +360,6 @@ __global__ __launch_bounds__(ALIAS ? 128 : 256) void attn_mfma_bwd_kernel(AttnAr
   const bf16* ep = (const bf16*)a.e + h * d;
   const bf16* gp = (const bf16*)a.dout + (long long)b * Tn * a.ldo + h * d;
   {
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)sm;
     const int wv = __builtin_amdgcn_readfirstlane(w);
     const long long lastq = (long long)(a.B - 1 - b) * Tn + Tn - 1;
@@ -439,7 +420,7 @@ __global__ __launch_bounds__(ALIAS ? 128 : 256) void attn_mfma_bwd_kernel(AttnAr
       for (int kk = 0; kk < (DKS ? DKS : G.DKS); ++kk) {
         const chunk16 fa = *(const chunk16*)(vrow + (((2 * kk + hf) ^ swr) << 4));
         const chunk16 fb = *(const chunk16*)(grow + (((2 * kk + hf) ^ swr) << 4));
-        dP = mma(fa, fb, dP);
+        dP = mma16(fa, fb, dP);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -493,7 +474,7 @@ __global__ __launch_bounds__(ALIAS ? 128 : 256) void attn_mfma_bwd_kernel(AttnAr
         for (int e = 0; e < 4; ++e) pb.w[e] = pack2(S[jt][8 * s + 2 * e], S[jt][8 * s + 2 * e + 1]);
         const char* kb = Ks + (32 * jt + 16 * s) * PITCH;
 #pragma unroll
-        for (int ct = 0; ct < CTMAX; ++ct) if (ct < G.CT) DQ[ct] = mma(tr8(kb + offt[ct][0], kb + offt[ct][1]), pb, DQ[ct]);
+        for (int ct = 0; ct < CTMAX; ++ct) if (ct < G.CT) DQ[ct] = mma16(lds_tr8(kb + offt[ct][0], kb + offt[ct][1]), pb, DQ[ct]);
       }
     }
   }
@@ -527,7 +508,7 @@ __global__ __launch_bounds__(ALIAS ? 128 : 256) void attn_mfma_bwd_kernel(AttnAr
         for (int e = 0; e < 4; ++e) pb.w[e] = pack2(rs[8 * s + 2 * e], rs[8 * s + 2 * e + 1]);
         const char* eb = Es + (32 * et + 32 * (1 - w) + 16 * s) * PITCH;
 #pragma unroll
-        for (int ct = 0; ct < CTMAX; ++ct) if (ct < G.CT) DQ[ct] = mma(tr8(eb + offt[ct][0], eb + offt[ct][1]), pb, DQ[ct]);
+        for (int ct = 0; ct < CTMAX; ++ct) if (ct < G.CT) DQ[ct] = mma16(lds_tr8(eb + offt[ct][0], eb + offt[ct][1]), pb, DQ[ct]);
       }
     }
   }

@@ -16,20 +16,14 @@
 // registers -- which is where the 36 prefetch registers come from.
 // forward:   y[p][co]  = sum_{tap,ci} x[p + tap - 1][ci] * Wf[co][tap][ci]          (flip = 0, weight = forward shadow  [Cout][9][Cin])
 // backward:  dx[p][ci] = sum_{tap,co} dy[p - tap + 1][co] * Wb[ci][tap][co] (+ res)  (flip = 1, weight = backward shadow [Cin][9][Cout])
-#include "common.h"
+#include "wave_prims.h"
 #include "vec.h"
 #include "avec_hip.h"
-
-typedef __attribute__((ext_vector_type(16))) float c3_f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 c3_bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned c3_u32x4;
 
 #define C3_WPITCH 1280                      // bytes per weight row in LDS: 72 data chunks in 80 slots (5 groups of 16)
 #define C3_WBYTES (64 * C3_WPITCH)          // 81 920
 #define C3_MAXPIX 576                       // slab pixels ((H+2)*(W+2), even)
 #define C3_SBYTES (C3_MAXPIX * 128)         // 73 728
-
-__device__ __attribute__((aligned(64))) unsigned char c3_zero16[64];     // source of the zero border (LDS-DMA has no immediate fill)
 
 struct C3Args { const bf16* x; const bf16* w; bf16* y; const bf16* res; float* stats; int N, H, W, flip; const unsigned char* rmask; };      // rmask: one bit per element of res (added where set)
 
@@ -51,8 +45,6 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(C3Args a) {
   char* Ws = smem; char* Sl = smem + C3_WBYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int H = a.H, W = a.W, PW = W + 1, HW = H * W, NPIX = (H + 2) * PW + 1;
-  typedef __attribute__((address_space(1))) const void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
 
   // ---- weights -> LDS once (plain loads + ds_write: 9 chunks per thread) ----
   for (int q = tid; q < 64 * 72; q += 512) {
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(C3Args a) {
       for (int r = 0; r < 16; ++r) { ssum[j][r] = 0.f; ssq[j][r] = 0.f; }
   }
 
-  c3_f32x16 acc[2][2];                       // [n-tile j][m-tile i], C^T layout: column = pixel (lane & 31), rows = channels (r&3) + 8*(r>>2) + 4*(lane>>5)
+  f32x16 acc[2][2];                       // [n-tile j][m-tile i], C^T layout: column = pixel (lane & 31), rows = channels (r&3) + 8*(r>>2) + 4*(lane>>5)
   // Results leave in two steps so that nobody waits for a store: right after the MFMAs of image n the accumulators are folded into the statistics, added to the
   // residual and packed to bf16 (32 registers); those 8-byte pieces are stored at the START of image n+1's MFMA phase, after the wait for its slab, and
   // complete under that phase.  The residual pieces of image n are requested at the start of its own MFMA phase and consumed after it.
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(C3Args a) {
   // cycles per image in that wait and 2.5 more where two 1 KB stores per tap throttled taps 1-4.  Issue order per image and wave (all 16-byte pieces per lane):
   //   tap t = 0..3: next image's pieces 2t, 2t+1 | residual pieces 2t, 2t+1 (backward) | store t of the previous image;  tap 4: piece 8, store 4;  taps 5-7: stores 5-7
   // so after tap 8 `s_waitcnt vmcnt(3)` covers every load and leaves the three youngest stores in flight (vmcnt counts in issue order; no stores in the first image: 0).
-  c3_u32x4 outp[2][2][2], resp[RES ? 2 : 1][2][2];
+  u32x4 outp[2][2][2], resp[RES ? 2 : 1][2][2];
   long long prev = -1;                       // image whose packed results are still in outp
   auto swap_pair = [&](uint2& x, uint2& y) {   // (X, Y) = (group 2k, group 2k+1) <-> (channels 0-7 | 8-15 of the 16-block): an involution
     auto r0 = __builtin_amdgcn_permlane32_swap(x.x, y.x, false, false); x.x = r0[0]; y.x = r0[1];
@@ -129,20 +121,20 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(C3Args a) {
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int k = 0; k < 2; ++k) *(c3_u32x4*)(yo + (long long)pm[i] * 64 + j * 32 + k * 16 + chq) = outp[j][i][k];
+        for (int k = 0; k < 2; ++k) *(u32x4*)(yo + (long long)pm[i] * 64 + j * 32 + k * 16 + chq) = outp[j][i][k];
     }
   };
 
-  c3_u32x4 pf[9];
+  u32x4 pf[9];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) pf[i] = c3_u32x4{0u, 0u, 0u, 0u};
+  for (int i = 0; i < 9; ++i) pf[i] = u32x4{0u, 0u, 0u, 0u};
   if (RES) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int k = 0; k < 2; ++k) resp[RES ? j : 0][i][k] = c3_u32x4{0u, 0u, 0u, 0u};
+        for (int k = 0; k < 2; ++k) resp[RES ? j : 0][i][k] = u32x4{0u, 0u, 0u, 0u};
   }
   if ((long long)blockIdx.x < a.N && !(C3S_ABL & 2)) {
     const bf16* x0 = a.x + (long long)blockIdx.x * HW * 64;
@@ -169,9 +161,9 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(C3Args a) {
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
       if (C3S_ABL & 2) break;
-      c3_u32x4 v = pf[i];
-      if (zmask & (1u << i)) v = c3_u32x4{0u, 0u, 0u, 0u};
-      *(c3_u32x4*)(Sl + ((wave + 8 * i) * 64 + lane) * 16) = v;
+      u32x4 v = pf[i];
+      if (zmask & (1u << i)) v = u32x4{0u, 0u, 0u, 0u};
+      *(u32x4*)(Sl + ((wave + 8 * i) * 64 + lane) * 16) = v;
     }
     __syncthreads();
     C3S_STAMP(1);
@@ -215,10 +207,11 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(C3Args a) {
         chunk16 cx0, cx1, cw0, cw1;
         load4(ax0, ax1, aw0, aw1, z0, z1, q, cx0, cx1, cw0, cw1);
         if (C3S_ABL & 1) { asm volatile("" :: "v"(cx0.w[0]), "v"(cx0.w[3]), "v"(cx1.w[0]), "v"(cx1.w[3]), "v"(cw0.w[0]), "v"(cw0.w[3]), "v"(cw1.w[0]), "v"(cw1.w[3])); continue; }
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, cw0), __builtin_bit_cast(c3_bf16x8, cx0), acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, cw0), __builtin_bit_cast(c3_bf16x8, cx1), acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, cw1), __builtin_bit_cast(c3_bf16x8, cx0), acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, cw1), __builtin_bit_cast(c3_bf16x8, cx1), acc[1][1], 0, 0, 0);
+        // (mma16 written out: through the wrapper, by reference or by value, the <STATS, no RES> instance gets another register allocation -- tools/isa_diff.py)
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, cw0), __builtin_bit_cast(bf16x8_t, cx0), acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, cw0), __builtin_bit_cast(bf16x8_t, cx1), acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, cw1), __builtin_bit_cast(bf16x8_t, cx0), acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, cw1), __builtin_bit_cast(bf16x8_t, cx1), acc[1][1], 0, 0, 0);
       }
     };
     // piece k of a pixel tile: k = 4 i + 2 j + kk  ->  outp / resp [j][i][kk] at byte offset 64 j + 32 kk of the lane's row piece
@@ -271,7 +264,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(C3Args a) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           uint2 rx = make_uint2(0u, 0u), ry = make_uint2(0u, 0u);
-          if (RES) { const c3_u32x4 rr = resp[RES ? j : 0][i][k]; rx = make_uint2(rr[0], rr[1]); ry = make_uint2(rr[2], rr[3]); swap_pair(rx, ry); }   // back to (group 2k, group 2k+1)
+          if (RES) { const u32x4 rr = resp[RES ? j : 0][i][k]; rx = make_uint2(rr[0], rr[1]); ry = make_uint2(rr[2], rr[3]); swap_pair(rx, ry); }   // back to (group 2k, group 2k+1)
           uint2 o[2];
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
@@ -288,7 +281,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(C3Args a) {
             o[e] = make_uint2(f32x2_to_bf16x2(v[0], v[1]), f32x2_to_bf16x2(v[2], v[3]));
           }
           swap_pair(o[0], o[1]);
-          outp[j][i][k] = c3_u32x4{o[0].x, o[0].y, o[1].x, o[1].y};
+          outp[j][i][k] = u32x4{o[0].x, o[0].y, o[1].x, o[1].y};
         }
     prev = n;
     C3S_STAMP(4);
@@ -335,8 +328,6 @@ __global__ __launch_bounds__(512) void conv3x3_c64_res_kernel(C3Args a) {
   char* Ws = smem; char* Sl = smem + C3_WBYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int H = a.H, W = a.W, PW = W + 1, HW = H * W, NPIX = (H + 2) * PW + 1;
-  typedef __attribute__((address_space(1))) const void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
 
   // ---- weights -> LDS once (plain loads + ds_write: 9 chunks per thread) ----
   for (int q = tid; q < 64 * 72; q += 512) {
@@ -369,7 +360,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_res_kernel(C3Args a) {
   const int wkey = lane & 15;                // (n & 15) for both n-tiles
 
 
-  c3_f32x16 acc[2][2];                       // [n-tile j][m-tile i], C^T layout: column = pixel (lane & 31), rows = channels (r&3) + 8*(r>>2) + 4*(lane>>5)
+  f32x16 acc[2][2];                       // [n-tile j][m-tile i], C^T layout: column = pixel (lane & 31), rows = channels (r&3) + 8*(r>>2) + 4*(lane>>5)
   // Results leave in two steps so that nobody waits for a store: right after the MFMAs of image n the accumulators are folded into the statistics, added to the
   // residual and packed to bf16 (32 registers); those 8-byte pieces are stored at the START of image n+1's MFMA phase, after the wait for its slab, and
   // complete under that phase.  The residual pieces of image n are requested at the start of its own MFMA phase and consumed after it.
@@ -449,10 +440,10 @@ __global__ __launch_bounds__(512) void conv3x3_c64_res_kernel(C3Args a) {
       for (int q = 0; q < 4; ++q) {
         chunk16 cx0, cx1, cw0, cw1;
         load4(ax0, ax1, aw0, aw1, z0, z1, q, cx0, cx1, cw0, cw1);
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, cw0), __builtin_bit_cast(c3_bf16x8, cx0), acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, cw0), __builtin_bit_cast(c3_bf16x8, cx1), acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, cw1), __builtin_bit_cast(c3_bf16x8, cx0), acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, cw1), __builtin_bit_cast(c3_bf16x8, cx1), acc[1][1], 0, 0, 0);
+        acc[0][0] = mma16(cw0, cx0, acc[0][0]);
+        acc[0][1] = mma16(cw0, cx1, acc[0][1]);
+        acc[1][0] = mma16(cw1, cx0, acc[1][0]);
+        acc[1][1] = mma16(cw1, cx1, acc[1][1]);
       }
     };
 #define C3_ST(I, J, K) if (pvalid[I]) *(uint4*)(yprev + (long long)pm[I] * 64 + J * 32 + K * 16 + chq) = outp[J][I][K]
@@ -537,19 +528,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_res_kernel(C3Args a) {
 // dh*(W+1) + dw into the slab.  Both MFMA operands are [k'][channel] arrays read with ds_read_b64_tr_b16 (the transposing read of gemm_tn_tr_kernel);
 // every input byte crosses L2 -> LDS once.  One atomic add per result element per workgroup at the end.
 // ------------------------------------------------------------------------------------------------
-typedef short c3_v4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ chunk16 c3_tr_read8(const char* p0, const char* p1) {
-  typedef __attribute__((address_space(3))) c3_v4s* lp_t;
-  const c3_v4s a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p0), b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p1);
-  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
-  chunk16 f; f.w[0] = ua.x; f.w[1] = ua.y; f.w[2] = ub.x; f.w[3] = ub.y; return f;
-}
-__device__ __forceinline__ void c3_glds16(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-typedef __attribute__((ext_vector_type(2))) unsigned c3_u32x2;
-__device__ __forceinline__ c3_u32x2 c3_lds_tr(unsigned lds_addr) { c3_u32x2 v; asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory"); return v; }
+__device__ __forceinline__ uint2 c3_lds_tr(unsigned lds_addr) { uint2 v; asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory"); return v; }
 #ifndef C3W_ABL
 #define C3W_ABL 0         // timing experiment on the 64-channel weight gradient (tools/build_abl_c3w.sh): 64 in-kernel cycle counters
 #endif
@@ -579,7 +558,6 @@ __device__ __forceinline__ void c3w_roll_body(const C3WArgs& a, const int bid, c
   char* Xs = smem; char* Ds = smem + C3_SBYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, W = a.W, PW = W + 1, HW = H * W, NPIX = (H + 2) * PW + 1;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   int xoff[9], doff[8];
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
@@ -610,7 +588,7 @@ __device__ __forceinline__ void c3w_roll_body(const C3WArgs& a, const int bid, c
       offb[j][h] = rowd * 128 + ((((cbB >> 3) + ((t & 3) >> 1)) ^ (4 * ((rowd >> 1) & 1))) << 4) + (t & 1) * 8;
     }
   }
-  c3_f32x16 acc[5];
+  f32x16 acc[5];
 #pragma unroll
   for (int j = 0; j < 5; ++j)
 #pragma unroll
@@ -621,24 +599,24 @@ __device__ __forceinline__ void c3w_roll_body(const C3WArgs& a, const int bid, c
     constexpr int G = decltype(gc)::value;
     const bf16* xi = a.x + n * HW * 64; const bf16* di = a.dy + n * HW * 64;
 #pragma unroll
-    for (int i = 2 * G; i < (G == 3 ? 9 : 2 * G + 2); ++i) c3_glds16(xoff[i] >= 0 ? (const void*)(xi + xoff[i]) : (const void*)c3_zero16, xs0 + (wave + 8 * i) * 1024);
+    for (int i = 2 * G; i < (G == 3 ? 9 : 2 * G + 2); ++i) glds16(xoff[i] >= 0 ? (const void*)(xi + xoff[i]) : (const void*)avec_zero16, xs0 + (wave + 8 * i) * 1024);
 #pragma unroll
-    for (int i = 2 * G; i < 2 * G + 2; ++i) c3_glds16(doff[i] >= 0 ? (const void*)(di + doff[i]) : (const void*)c3_zero16, ds0 + (wave + 8 * i) * 1024);
+    for (int i = 2 * G; i < 2 * G + 2; ++i) glds16(doff[i] >= 0 ? (const void*)(di + doff[i]) : (const void*)avec_zero16, ds0 + (wave + 8 * i) * 1024);
   };
   auto group = [&](auto gc) {                              // k-steps [8G, 8G + 8)
     constexpr int G = decltype(gc)::value;
 #pragma unroll 2
     for (int s = 8 * G; s < 8 * G + 8; ++s) {
       const int so = s * 2048;
-      const chunk16 fa = c3_tr_read8(Ds + offa[0] + so, Ds + offa[1] + so);
+      const chunk16 fa = lds_tr8(Ds + offa[0] + so, Ds + offa[1] + so);
       chunk16 fb[5];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = c3_tr_read8(Xs + offb[j][0] + so, Xs + offb[j][1] + so);
-      if (five) fb[4] = c3_tr_read8(Xs + offb[4][0] + so, Xs + offb[4][1] + so);
+      for (int j = 0; j < 4; ++j) fb[j] = lds_tr8(Xs + offb[j][0] + so, Xs + offb[j][1] + so);
+      if (five) fb[4] = lds_tr8(Xs + offb[4][0] + so, Xs + offb[4][1] + so);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, fa), __builtin_bit_cast(c3_bf16x8, fb[j]), acc[j], 0, 0, 0);
-      if (five) acc[4] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, fa), __builtin_bit_cast(c3_bf16x8, fb[4]), acc[4], 0, 0, 0);
+        acc[j] = mma16(fa, fb[j], acc[j]);
+      if (five) acc[4] = mma16(fa, fb[4], acc[4]);
     }
   };
   long long n = bid;
@@ -721,7 +699,6 @@ __device__ __forceinline__ void c3ww_body(const C3WWArgs& a, const int bid, cons
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, W = a.W, C = a.C, PW = W + 1, HW = H * W, NPIX = (H + 2) * PW + 1;
   const int nci = C >> 7, kinds = (C >> 6) * nci, kind = bid % kinds, cog = kind / nci, cig = kind - cog * nci;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const unsigned xs0 = (unsigned)(uintptr_t)(lptr_t)Xs, ds0 = (unsigned)(uintptr_t)(lptr_t)Ds;
   const int xhalf = a.IT * a.RS * 256, dhalf = a.IT * a.KP * 128;          // bytes of one half (multiples of 4096 / 2048: whole DMA passes)
   const int xpasses = xhalf >> 10, dpasses = dhalf >> 10;                   // 1 KB = one DMA instruction of a wave
@@ -756,7 +733,7 @@ __device__ __forceinline__ void c3ww_body(const C3WWArgs& a, const int bid, cons
       adb0[j][h] = xs0 + rowd * 256 + ((((cbB >> 3) + ((t & 3) >> 1)) ^ (4 * (rowd & 3))) << 4) + (t & 1) * 8;
     }
   }
-  c3_f32x16 acc[9];
+  f32x16 acc[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j)
 #pragma unroll
@@ -774,15 +751,15 @@ __device__ __forceinline__ void c3ww_body(const C3WWArgs& a, const int bid, cons
     for (int k = 0; k < C3X_XPL; ++k) {
       if (wave + 8 * k >= xpasses) break;                                     // wave-uniform
       const int e = xpl[k]; const long long img = img0 + (e >> 24);
-      const void* src = (e >= 0 && img < a.N) ? (const void*)(a.x + img * HW * C + (e & 0xffffff)) : (const void*)c3_zero16;
-      c3_glds16(src, xs0 + par * xhalf + (wave + 8 * k) * 1024);
+      const void* src = (e >= 0 && img < a.N) ? (const void*)(a.x + img * HW * C + (e & 0xffffff)) : (const void*)avec_zero16;
+      glds16(src, xs0 + par * xhalf + (wave + 8 * k) * 1024);
     }
 #pragma unroll
     for (int k = 0; k < C3X_DPL; ++k) {
       if (wave + 8 * k >= dpasses) break;
       const int e = dpl[k]; const long long img = img0 + (e >> 24);
-      const void* src = (e >= 0 && img < a.N) ? (const void*)(a.dy + img * HW * C + (e & 0xffffff)) : (const void*)c3_zero16;
-      c3_glds16(src, ds0 + par * dhalf + (wave + 8 * k) * 1024);
+      const void* src = (e >= 0 && img < a.N) ? (const void*)(a.dy + img * HW * C + (e & 0xffffff)) : (const void*)avec_zero16;
+      glds16(src, ds0 + par * dhalf + (wave + 8 * k) * 1024);
     }
   };
   long long q = bid / kinds;
@@ -801,13 +778,13 @@ __device__ __forceinline__ void c3ww_body(const C3WWArgs& a, const int bid, cons
     int s = 0;
 #pragma unroll 1
     for (int u = a.IT * nsteps; u > 0; --u) {
-      c3_u32x2 ra[2], rb[9][2];
+      uint2 ra[2], rb[9][2];
 #pragma unroll
-      for (int h = 0; h < 2; ++h) ra[h] = (C3_ABL & 4) ? c3_u32x2{(unsigned)u, 1u} : c3_lds_tr(ada[h]);
+      for (int h = 0; h < 2; ++h) ra[h] = (C3_ABL & 4) ? uint2{(unsigned)u, 1u} : c3_lds_tr(ada[h]);
 #pragma unroll
       for (int j = 0; j < 9; ++j)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) rb[j][h] = (C3_ABL & 4) ? c3_u32x2{(unsigned)u, 2u} : c3_lds_tr(adb[j][h]);
+        for (int h = 0; h < 2; ++h) rb[j][h] = (C3_ABL & 4) ? uint2{(unsigned)u, 2u} : c3_lds_tr(adb[j][h]);
       const bool wrap = ++s == nsteps; if (wrap) s = 0;
       const int dx = wrap ? xjump : 4096, dd = wrap ? djump : 2048;
 #pragma unroll
@@ -817,7 +794,7 @@ __device__ __forceinline__ void c3ww_body(const C3WWArgs& a, const int bid, cons
 #define C3_STEP(j) do { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"((j) == 0 ? 15 : 2 * (8 - (j))) : "memory"); if ((j) == 0) asm volatile("" : "+v"(ra[0]), "+v"(ra[1])); asm volatile("" : "+v"(rb[j][0]), "+v"(rb[j][1])); \
         chunk16 fa, fb; fa.w[0] = ra[0].x; fa.w[1] = ra[0].y; fa.w[2] = ra[1].x; fa.w[3] = ra[1].y; fb.w[0] = rb[j][0].x; fb.w[1] = rb[j][0].y; fb.w[2] = rb[j][1].x; fb.w[3] = rb[j][1].y; \
         if (C3_ABL & 1) asm volatile("" :: "v"(fa.w[0]), "v"(fa.w[1]), "v"(fa.w[2]), "v"(fa.w[3]), "v"(fb.w[0]), "v"(fb.w[1]), "v"(fb.w[2]), "v"(fb.w[3])); else \
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(c3_bf16x8, fa), __builtin_bit_cast(c3_bf16x8, fb), acc[j], 0, 0, 0); } while (0)
+        acc[j] = mma16(fa, fb, acc[j]); } while (0)
       C3_STEP(0); C3_STEP(1); C3_STEP(2); C3_STEP(3); C3_STEP(4); C3_STEP(5); C3_STEP(6); C3_STEP(7); C3_STEP(8);
 #undef C3_STEP
       __builtin_amdgcn_sched_barrier(0);

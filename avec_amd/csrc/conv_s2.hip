@@ -20,12 +20,6 @@ namespace {
 
 constexpr int S2_HALO = 16;
 
-// LDS-DMA of one 16-byte piece per lane (lanes outside `on` idle): wave-uniform LDS base through M0
-__device__ __forceinline__ void s2_glds16(const void* sbase, unsigned voff, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst_uniform) : "memory");
-}
-
 // MODE_CONV_FWD: CLS unused.  MODE_CONV_BWD: CLS = pr * 2 + pc of the fine pixels this workgroup produces.  EVEN: H and W even (no class plane is short of a row / column).
 // (bx, by): tile coordinates (the caller maps workgroup ids XCD-aware)
 template <int BM, int BN, int MODE, int CLS, bool EVEN>
@@ -45,7 +39,6 @@ __device__ __forceinline__ void conv_s2_body(const GemmArgs& g, char* smem, cons
   const int H = g.a.H, Wd = g.a.W, OH = g.a.OH, OW = g.a.OW, C = g.a.C;
   const unsigned P = (unsigned)(FWD ? g.M : g.M / ((long long)H * Wd) * OH * OW);       // coarse pixels (host: < 2^31)
   const unsigned m0 = (unsigned)bx * BM; const int n0 = by * BN;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const unsigned bring0 = (unsigned)(uintptr_t)(lptr_t)Bring, awin0 = (unsigned)(uintptr_t)(lptr_t)Awin;
   const unsigned wslot = (unsigned)wave * 1024u;
 
@@ -145,14 +138,13 @@ __device__ __forceinline__ void conv_s2_body(const GemmArgs& g, char* smem, cons
 #pragma unroll
     for (int i = 0; i < NAF; ++i) { const unsigned o = aoff[i] + delta; v[i] = (FWD && GI != 1) ? (o < amax ? o : amax) : o; }
     glds16_group<NAF>(v, src, awin0 + WB * AWIN + wslot);
-    if (lane < 16) { const unsigned o = aoff[NAF] + delta; s2_glds16(src, (FWD && GI != 1) ? (o < amax ? o : amax) : o, awin0 + WB * AWIN + NAF * 4096u + (unsigned)wave * 256u); }
+    if (lane < 16) { const unsigned o = aoff[NAF] + delta; glds16_s(src, (FWD && GI != 1) ? (o < amax ? o : amax) : o, awin0 + WB * AWIN + NAF * 4096u + (unsigned)wave * 256u); }
   };
   auto issue_b = [&](const int cc, const int tap, auto stc) {
     constexpr int ST = decltype(stc)::value;
     glds16_group<NCB>(boff, Wb + (long long)tap * C2 + (long long)cc * (KE * 2), bring0 + ST * BTILE + wslot);
   };
 
-#define S2_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
   // prologue: W(0), W(1), B(0), B(1)
   issue_window(0, IntC<0>{}, IntC<Plan::wbuf(0, 0)>{});
   if (FWD) issue_window(0, IntC<1 % NG>{}, IntC<Plan::wbuf(0, 1 % NG)>{});
@@ -173,8 +165,8 @@ __device__ __forceinline__ void conv_s2_body(const GemmArgs& g, char* smem, cons
     bool prev_w;
     if (K_ > 0) prev_w = Plan::first(K_ > 0 ? K_ - 1 : 0) && (FWD ? (Plan::group(K_ > 0 ? K_ - 1 : 0) + 2 < NG || more) : (cc + 2 < NC));
     else prev_w = (NTAPS == 1) && cc > 0 && more;               // (one-tap class: the previous chunk's only step asked for chunk cc + 1)
-    if (prev_w) { if (next_b) S2_WAIT_VM(NCB + NAF + 1); else S2_WAIT_VM(NAF + 1); }
-    else { if (next_b) S2_WAIT_VM(NCB); else S2_WAIT_VM(0); }
+    if (prev_w) { if (next_b) AVEC_WAIT_VM(NCB + NAF + 1); else AVEC_WAIT_VM(NAF + 1); }
+    else { if (next_b) AVEC_WAIT_VM(NCB); else AVEC_WAIT_VM(0); }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     u32x4 fa[2][MT], fb[2][NT];
@@ -218,7 +210,7 @@ __device__ __forceinline__ void conv_s2_body(const GemmArgs& g, char* smem, cons
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fb[q][j]), __builtin_bit_cast(bf16x8_t, fa[q][i]), acc[i][j], 0, 0, 0);
+          acc[i][j] = mma16(fb[q][j], fa[q][i], acc[i][j]);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -234,7 +226,6 @@ __device__ __forceinline__ void conv_s2_body(const GemmArgs& g, char* smem, cons
     if (cc + 1 < NC) chunk(IntC<1>{}, cc + 1);
     if (cc + 2 < NC) chunk(IntC<2>{}, cc + 2);
   }
-#undef S2_WAIT_VM
   __syncthreads();
   // ---- epilogue rows: forward the coarse pixel itself; backward its fine pixel of this class (none for odd sizes at the last row / column)
   const bool use_res = g.e.res != nullptr && (!g.e.res_cls0 || (!FWD && CLS == 0));

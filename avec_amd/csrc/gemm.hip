@@ -78,8 +78,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs g) {
 // (conflict-free for ds_read_b128's 16-lane groups).  Invalid rows / taps / K-tails fetch 16 zero bytes from `avec_zero16`.
 // Requires every chunk address 16-byte aligned and K % VEC == 0 (host-checked: the A16 case).
 // ------------------------------------------------------------------------------------------------
-__device__ __attribute__((aligned(64))) unsigned char avec_zero16[64];
-
 
 // RB: bytes of K per LDS row (128: 8 chunks, swizzle (row>>1)&7;  64: 4 chunks, swizzle (row>>2)&3 -- half the ring, twice the resident workgroups)
 template <typename T, int BM, int BN, int MODE, int STAGES, bool FASTC = false, int RB = 128>
@@ -146,8 +144,6 @@ __global__ __launch_bounds__(256, (BM * BN > 128 * 256) ? 1 : 2) void gemm_nt_gl
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  typedef __attribute__((address_space(1))) const void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   int KT = (g.K + KE - 1) / KE;
   int f_tap = 0, f_kh = 0, f_kw = 0, f_c0 = 0;       // fast path: running (tap, kh, kw, channel offset) of the next K-step to be issued (issue() is called with kt = 0, 1, 2, ...)
   unsigned tapmask = 0xffffffffu;                    // parity classes: the taps this tile's class can reach (wave-uniform); the others are skipped
@@ -221,7 +217,6 @@ __global__ __launch_bounds__(256, (BM * BN > 128 * 256) ? 1 : 2) void gemm_nt_gl
   //   wait(tile kt landed: only the newer S-2 tiles may still be outstanding) -> barrier -> issue tile kt+S-1 into the buffer everybody
   //   finished reading before this barrier -> MFMAs on tile kt.
   constexpr int LPT = NCA + NCB;             // DMA instructions per thread per tile
-#define AVEC_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 #pragma unroll
   for (int st = 0; st < STAGES - 1; ++st) if (st < KT) issue(st, st);
   for (int kt = 0; kt < KT; ++kt) {
@@ -285,7 +280,6 @@ __global__ __launch_bounds__(256, (BM * BN > 128 * 256) ? 1 : 2) void gemm_nt_gl
           }
     }
   }
-#undef AVEC_WAIT_VM
   __syncthreads();                            // every wave is done with the ring before the epilogue reuses the LDS
   nt_epilogue<T, BM, BN, MT, NT>(g, acc, smem, m0, n0, tid, lane, wm, wn, cls);
 }
@@ -333,7 +327,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_shift_kernel(GemmArgs g) {
   }
   const long long m0 = (long long)bx * BM; const int n0 = by * BN;
   const int Wd = g.a.W, H = g.a.H, C = g.a.C, halo = Wd + 1;
-  typedef __attribute__((address_space(3))) void* lptr_t;
 
   // DMA plan: window row wr = i*64 + tid/4 holds source pixel m0 - halo + wr (clamped into the tensor); physical slot tid%4 carries logical chunk slot ^ swz(row)
   unsigned aoff[NA], boff[NCB];
@@ -398,7 +391,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_shift_kernel(GemmArgs g) {
 
   const int NC = C / KE;
   const char* const Ab = (const char*)g.a.ptr; const char* const Wb = (const char*)g.W;
-#define AVEC_WAIT_VM(n) do { if (!(AVEC_ABL & 16)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory"); } while (0)
+#define SHIFT_WAIT_VM(n) do { if (!(AVEC_ABL & 16)) AVEC_WAIT_VM(n); } while (0)      // (ablation 16 also drops the waits)
   // issue order: A(0), B(0), B(1); then in step ks (after its barrier): [A(cc+1) when t == 0], B(ks+2)
   if (!(AVEC_ABL & (2 | 64))) glds16_group<NA>(aoff, Ab, awin0 + wslot);
   if (!(AVEC_ABL & (2 | 128))) { glds16_group<NCB>(boff, Wb, bring0 + wslot); glds16_group<NCB>(boff, Wb + C2, bring0 + BTILE + wslot); }
@@ -407,9 +400,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_shift_kernel(GemmArgs g) {
   auto step = [&](auto tapc, auto parc, const int cc) {
     constexpr int TAP = decltype(tapc)::value, PAR = decltype(parc)::value;
     const bool last_chunk = cc + 1 >= NC;
-    if (TAP == 8) { if (last_chunk) AVEC_WAIT_VM(0); else AVEC_WAIT_VM(NCB); }
-    else if (TAP == 1) { if (last_chunk) AVEC_WAIT_VM(NCB); else AVEC_WAIT_VM(NCB + NA); }       // the window of the next chunk went out in the previous step (newer than B(ks))
-    else AVEC_WAIT_VM(NCB);
+    if (TAP == 8) { if (last_chunk) SHIFT_WAIT_VM(0); else SHIFT_WAIT_VM(NCB); }
+    else if (TAP == 1) { if (last_chunk) SHIFT_WAIT_VM(NCB); else SHIFT_WAIT_VM(NCB + NA); }       // the window of the next chunk went out in the previous step (newer than B(ks))
+    else SHIFT_WAIT_VM(NCB);
     if (!(AVEC_ABL & 8)) __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     // all fragment reads of the step are requested at once (inline asm: in-order returns, counted waits); the first MFMA group
@@ -447,8 +440,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_shift_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < NT; ++j)
           if (AVEC_ABL & 1) asm volatile("" :: "v"(fa[q][i]), "v"(fb[q][j])); else
-          if (TR) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fb[q][j]), __builtin_bit_cast(bf16x8_t, fa[q][i]), acc[i][j], 0, 0, 0);
-          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fa[q][i]), __builtin_bit_cast(bf16x8_t, fb[q][j]), acc[i][j], 0, 0, 0);
+          if (TR) acc[i][j] = mma16(fb[q][j], fa[q][i], acc[i][j]);
+          else acc[i][j] = mma16(fa[q][i], fb[q][j], acc[i][j]);
       }
       __builtin_amdgcn_sched_barrier(0);          // (keeps this group's MFMAs above the next group's wait)
     }
@@ -462,7 +455,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_shift_kernel(GemmArgs g) {
     chunk(IntC<0>{}, cc);
     if (cc + 1 < NC) chunk(IntC<1>{}, cc + 1);
   }
-#undef AVEC_WAIT_VM
+#undef SHIFT_WAIT_VM
   __syncthreads();
   if (TR) {
     long long row[MT]; bool valid[MT];
@@ -481,10 +474,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_shift_kernel(GemmArgs g) {
 // entry; only the last, partial K tile takes per-lane selects (K % 8 == 0: a 16-byte chunk is inside K or not at all).  Rows beyond M / N are clamped (their
 // results are not stored).  Same LDS image, swizzle and epilogue as gemm_nt_glds_kernel<bf16, BM, 64, MODE_PLAIN, 4, false, 128>.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void glds16_v64(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
 // STAGES = 4: all of K <= 256 in flight, two workgroups per CU (64 KB).  STAGES = 2: 32 KB, four workgroups per CU -- for products whose 64 x 64 tiling
 // exceeds the 512 slots of the deep ring (3200 x 1024 x 256: 800 tiles) one round of workgroups that hide each other's DMA latency instead of two rounds.
 template <int BM, int BN, int STAGES = 4, bool TR = false>      // TR: transposed product + register-direct epilogue (plain_epilogue_tr)
@@ -510,7 +499,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_plain_kernel(const void* pa_pt
 #else
   const long long m0 = (long long)blockIdx.x * BM; const int n0 = blockIdx.y * BN;
 #endif
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)smem, wslot = (unsigned)wave * 1024u;
   const int K = pa_K, KT = (K + KE - 1) / KE, KF = K / KE;
   // DMA plan: pass i, thread tid -> tile row tid/8 + 32 i, physical slot tid%8 carrying logical K-chunk (tid%8) ^ swz(row)
@@ -545,12 +533,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_plain_kernel(const void* pa_pt
 #pragma unroll
       for (int i = 0; i < NCA; ++i) {
         const int k0 = kt * KE + kca * 8; const long long early = (ktail && k0 + 8 > K && ((lastrow >> i) & 1u)) ? 8 : 0;
-        glds16_v64(k0 < K ? (const void*)(Ab + aoff[i] + (long long)kt * (KE * 2) - early) : (const void*)avec_zero16, la + i * 4096);
+        glds16(k0 < K ? (const void*)(Ab + aoff[i] + (long long)kt * (KE * 2) - early) : (const void*)avec_zero16, la + i * 4096);
       }
 #pragma unroll
       for (int i = 0; i < NCB; ++i) {
         const int k0 = kt * KE + kcb[i] * 8; const long long early = (ktail && k0 + 8 > K && ((lastrow >> (8 + i)) & 1u)) ? 8 : 0;
-        glds16_v64(k0 < K ? (const void*)(Wb + boff[i] + (long long)kt * (KE * 2) - early) : (const void*)avec_zero16, lb + i * 4096);
+        glds16(k0 < K ? (const void*)(Wb + boff[i] + (long long)kt * (KE * 2) - early) : (const void*)avec_zero16, lb + i * 4096);
       }
     }
   };
@@ -570,7 +558,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_plain_kernel(const void* pa_pt
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
 
-#define AVEC_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
   issue(0, IntC<0>{});
   if (STAGES > 2 && KT > 1) issue(1, IntC<1 % STAGES>{});
   if (STAGES > 2 && KT > 2) issue(2, IntC<2 % STAGES>{});
@@ -628,8 +615,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_plain_kernel(const void* pa_pt
 #pragma unroll
       for (int i = 0; i < MT; ++i)
         if (AVEC_ABL & 1) asm volatile("" :: "v"(fa[q][i]), "v"(fb[q])); else
-        if (TR) acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fb[q]), __builtin_bit_cast(bf16x8_t, fa[q][i]), acc[i][0], 0, 0, 0); else
-        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fa[q][i]), __builtin_bit_cast(bf16x8_t, fb[q]), acc[i][0], 0, 0, 0);
+        if (TR) acc[i][0] = mma16(fb[q], fa[q][i], acc[i][0]); else
+        acc[i][0] = mma16(fa[q][i], fb[q], acc[i][0]);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -640,7 +627,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_plain_kernel(const void* pa_pt
     if (STAGES > 2 && kt + 2 < KT) step(kt + 2, IntC<2 % STAGES>{});
     if (STAGES > 2 && kt + 3 < KT) step(kt + 3, IntC<3 % STAGES>{});
   }
-#undef AVEC_WAIT_VM
   if constexpr (TR) {
     static_assert(BM == 64 && BN == 64, "register-direct epilogue: 64 x 64 tiles");
     plain_epilogue_tr(g, acc[0][0], m0, n0, lane, wm, wn);
@@ -672,7 +658,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_conv_lean_kernel(GemmArgs g) {
   const int cls = perm ? ((int)blockIdx.x >= g.pTs[2] ? ((int)blockIdx.x >= g.pTs[3] ? 3 : 2) : ((int)blockIdx.x >= g.pTs[1] ? 1 : 0)) : 0;
   const long long m0 = perm ? (long long)((int)blockIdx.x - g.pTs[cls]) * BM : (long long)blockIdx.x * BM; const int n0 = blockIdx.y * BN;
   const long long pMc = perm ? perm2_count(g.a, cls, g.pImgs) : 0;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)smem, wslot = (unsigned)wave * 1024u;
   const int IW = MODE == MODE_CONV_FWD ? g.a.W : g.a.OW;      // row pitch of the source image
   const int sh = (MODE == MODE_CONV_BWD && g.a.stride == 2) ? 1 : 0;
@@ -723,7 +708,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_conv_lean_kernel(GemmArgs g) {
 #pragma unroll
     for (int i = 0; i < NCA; ++i) {
       const void* src = ((rmask[i] >> f_tap) & 1u) ? (const void*)(aptr[i] + tapoff) : (const void*)avec_zero16;
-      glds16_v64(src, la + i * 4096);
+      glds16(src, la + i * 4096);
     }
     glds16_group<NCB>(boff, Wb + (long long)(f_tap * g.a.C + f_c0) * 2, lb);
     f_c0 += KE;
@@ -747,7 +732,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_conv_lean_kernel(GemmArgs g) {
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#define AVEC_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
   issue(IntC<0>{});
   if (KT > 1) issue(IntC<1>{});
   auto step = [&](const int kt, auto stagec) {
@@ -774,8 +758,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_conv_lean_kernel(GemmArgs g) {
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
-          if (TR) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fb[q][j]), __builtin_bit_cast(bf16x8_t, fa[q][i]), acc[i][j], 0, 0, 0);
-          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fa[q][i]), __builtin_bit_cast(bf16x8_t, fb[q][j]), acc[i][j], 0, 0, 0);
+          if (TR) acc[i][j] = mma16(fb[q][j], fa[q][i], acc[i][j]);
+          else acc[i][j] = mma16(fa[q][i], fb[q][j], acc[i][j]);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -785,7 +769,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_conv_lean_kernel(GemmArgs g) {
     if (kt + 1 < KT) step(kt + 1, IntC<1>{});
     if (kt + 2 < KT) step(kt + 2, IntC<2>{});
   }
-#undef AVEC_WAIT_VM
   __syncthreads();
   if (TR) {
     // parity-class order: the tile's rows are class-local indices; the output row is the pixel's; a class-0-only residual (res_cls0) is indexed class-locally
@@ -824,8 +807,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_fp8_kernel(GemmArgs g, const f
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const long long m0 = (long long)blockIdx.x * BM; const int n0 = blockIdx.y * BN;
-  typedef __attribute__((address_space(1))) const void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   long long aoff[NCA], boff[NCB]; int ka[NCA], kb[NCB];
 #pragma unroll
   for (int i = 0; i < NCA; ++i) { const int row = (tid >> 3) + i * 32; aoff[i] = (m0 + row < g.M) ? (m0 + row) * g.a.ld : -1; ka[i] = ((tid & 7) ^ glds_swz<RB>(row)) * 16; }
@@ -861,7 +842,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_fp8_kernel(GemmArgs g, const f
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
   const int KT = (g.K + KE - 1) / KE;
   constexpr int LPT = NCA + NCB;
-#define AVEC_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 #pragma unroll
   for (int st = 0; st < STAGES - 1; ++st) if (st < KT) issue(st, st);
   for (int kt = 0; kt < KT; ++kt) {
@@ -896,7 +876,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_fp8_kernel(GemmArgs g, const f
       }
     }
   }
-#undef AVEC_WAIT_VM
   const float sc = (fmaxf(*amax_a, 1e-20f) * (1.0f / 448.0f)) * (fmaxf(*amax_w, 1e-20f) * (1.0f / 448.0f));
 #pragma unroll
   for (int i = 0; i < MT; ++i)
@@ -1085,13 +1064,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_multi_kernel(TnMulti m) {
 // (source side: lane L of a DMA fetches the logical chunk that belongs in physical slot L) so that the 4 rows of a block fall on
 // distinct banks: chunk ^= 4*(row & 3) for 256-byte rows, ^= 4*((row >> 1) & 1) for 128-byte rows.
 // ------------------------------------------------------------------------------------------------
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ chunk16 tr_read8(const char* p0, const char* p1) {
-  typedef __attribute__((address_space(3))) v4s_t* lp_t;
-  const v4s_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p0), b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p1);
-  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
-  chunk16 f; f.w[0] = ua.x; f.w[1] = ua.y; f.w[2] = ub.x; f.w[3] = ub.y; return f;
-}
 template <int BC> __device__ __forceinline__ int tr_swz(int row) { return BC == 128 ? 4 * (row & 3) : 4 * ((row >> 1) & 1); }
 
 template <int BI, int BJ, int MODE, int STAGES, bool Q32 = false, int KT = 64>      // Q32: the im2col source has < 2^31 elements: 32-bit offsets; KT: reduction rows per tile
@@ -1139,14 +1111,12 @@ __device__ __forceinline__ void tn_tr_body(const TnArgs& g, const int bx, const 
       const long long m = mb + qrow0 + u * RJ; const long long im = m / g.q_ohw; qpx[u] = (int)(m - im * g.q_ohw); qimg[u] = im * (long long)q_hwc;
     }
   }
-  typedef __attribute__((address_space(1))) const void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   // The DMA goes out through inline asm: behind the builtin the compiler drains the queue (s_waitcnt vmcnt(0), visible in the ISA of this loop) in front of the first
   // transposed read it cannot prove disjoint, i.e. right behind the prefetch of the next tile (DESIGN.md 17.2 rule 3); completion is counted by hand below (AVEC_WAIT_VM).
   // (The gathered operand only gained from it once its per-tile address arithmetic had been cut down -- with the old carry chain the asm form was 5-25 % slower.)
   const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)smem;
   auto tn_dma = [&](const void* src, unsigned off) {
-    if ((!Q_CONV || AVEC_TN_CONV_ASM) && !(AVEC_TN_BUILTIN_DMA)) glds16_v64(src, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + off)));
+    if ((!Q_CONV || AVEC_TN_CONV_ASM) && !(AVEC_TN_BUILTIN_DMA)) glds16(src, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + off)));
     else __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + off), 16, 0, 0);
   };
   // plain products, whole tiles: scalar base (first row of the tile) + per-lane 32-bit offsets fixed at entry, one M0 save / restore per operand (glds16_group) --
@@ -1217,7 +1187,6 @@ __device__ __forceinline__ void tn_tr_body(const TnArgs& g, const int bx, const 
   const int cs_pc = lane % CPI, cs_r4 = (lane / CPI) & 3, cs_rs = lane / (CPI * 4);
   float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   constexpr int LPT = NLI + NLJ;
-#define AVEC_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
   const int KTN = (int)((me - mb + KT - 1) / KT);
 #pragma unroll
   for (int st = 0; st < STAGES - 1; ++st) if (st < KTN) issue(mb + (long long)st * KT, st);
@@ -1243,16 +1212,15 @@ __device__ __forceinline__ void tn_tr_body(const TnArgs& g, const int bx, const 
     for (int kk = 0; kk < KT / 16; ++kk) {
       chunk16 fa[MTI], fb[MTJ];
 #pragma unroll
-      for (int i = 0; i < MTI; ++i) fa[i] = tr_read8(S + offa[i][0] + kk * 16 * BI * 2, S + offa[i][1] + kk * 16 * BI * 2);
+      for (int i = 0; i < MTI; ++i) fa[i] = lds_tr8(S + offa[i][0] + kk * 16 * BI * 2, S + offa[i][1] + kk * 16 * BI * 2);
 #pragma unroll
-      for (int j = 0; j < MTJ; ++j) fb[j] = tr_read8(S + offb[j][0] + kk * 16 * BJ * 2, S + offb[j][1] + kk * 16 * BJ * 2);
+      for (int j = 0; j < MTJ; ++j) fb[j] = lds_tr8(S + offb[j][0] + kk * 16 * BJ * 2, S + offb[j][1] + kk * 16 * BJ * 2);
 #pragma unroll
       for (int i = 0; i < MTI; ++i)
 #pragma unroll
         for (int j = 0; j < MTJ; ++j) Mma<T>::run(fa[i], fb[j], acc[i][j]);
     }
   }
-#undef AVEC_WAIT_VM
   if (do_cs) {                                           // workgroup-uniform: reduce the 16 partials per column in LDS, then one global atomic per column
     float* red = (float*)smem;
     __syncthreads();                                     // the ring is free

@@ -1,5 +1,5 @@
 // Device-side pieces shared by the MFMA product / convolution kernels (gemm.hip, conv_s2.hip): operand row maps, the argument block, the staged and the
-// register-direct epilogues, LDS-DMA helpers.  Split out of gemm.hip in round 6 so that a new kernel family compiles as its own translation unit.
+// register-direct epilogues (the wave-level MFMA / LDS-DMA primitives are in wave_prims.h).  Split out of gemm.hip in round 6 so that a new kernel family compiles as its own translation unit.
 #pragma once
 // MFMA GEMM family for gfx950 (CDNA4, wave64).
 //
@@ -17,9 +17,7 @@
 // MFMA: v_mfma_f32_32x32x16_bf16 (bf16) / v_mfma_f32_32x32x2_f32 (fp32, exact fp32 for the parity tests).
 #include "vec.h"
 #include "avec_hip.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "wave_prims.h"
 
 // kernel ablation builds (tools/build_abl.sh): bit 1 no MFMA, 2 no LDS-DMA, 4 no fragment reads, 8 no barrier, 16 no global stores, 32 no epilogue,
 // 64 / 128 no A / B DMA of the shifted-window kernel.  0 in the product.
@@ -189,7 +187,7 @@ int avec_launch_conv_s2(const GemmArgs& g, int mode, hipStream_t st);
 template <typename T> struct Mma;
 template <> struct Mma<bf16> {
   __device__ static __forceinline__ void run(const chunk16& a, const chunk16& b, f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+    c = mma16(a, b, c);
   }
 };
 template <> struct Mma<float> {
@@ -656,26 +654,6 @@ __device__ __forceinline__ void plain_epilogue_tr(const GemmArgs& g, const f32x1
 
 template <int RB> __device__ __forceinline__ int glds_swz(int row) { return RB == 256 ? (row & 15) : RB == 128 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 __device__ __forceinline__ u32x4 lds_read128(unsigned lds_addr) { u32x4 v; asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory"); return v; }
 template <int OFF> __device__ __forceinline__ u32x4 lds_read128o(unsigned lds_addr) { u32x4 v; asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "n"(OFF) : "memory"); return v; }
-// LDS-DMA of N x 16 B per lane as one group: scalar base + per-lane 32-bit byte offsets (no VALU on the issue path); LDS destinations lds0 + 4096 i (wave-uniform)
-// go through M0, saved and restored once per group
-#define AVEC_GLDS_HEAD "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-#define AVEC_GLDS_NEXT(k) "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %" #k ", %2\n\t"
-#define AVEC_GLDS_TAIL "s_mov_b32 m0, %0"
-template <int N> __device__ __forceinline__ void glds16_group(const unsigned (&v)[N], const void* sbase, unsigned lds0) {
-  static_assert(N >= 1 && N <= 5, "group size");
-  unsigned keep;
-  if constexpr (N == 1) asm volatile(AVEC_GLDS_HEAD AVEC_GLDS_TAIL : "=&s"(keep) : "v"(v[0]), "s"(sbase), "s"(lds0) : "memory", "scc");
-  if constexpr (N == 2) asm volatile(AVEC_GLDS_HEAD AVEC_GLDS_NEXT(4) AVEC_GLDS_TAIL : "=&s"(keep) : "v"(v[0]), "s"(sbase), "s"(lds0), "v"(v[1]) : "memory", "scc");
-  if constexpr (N == 3) asm volatile(AVEC_GLDS_HEAD AVEC_GLDS_NEXT(4) AVEC_GLDS_NEXT(5) AVEC_GLDS_TAIL : "=&s"(keep) : "v"(v[0]), "s"(sbase), "s"(lds0), "v"(v[1]), "v"(v[2]) : "memory", "scc");
-  if constexpr (N == 4) asm volatile(AVEC_GLDS_HEAD AVEC_GLDS_NEXT(4) AVEC_GLDS_NEXT(5) AVEC_GLDS_NEXT(6) AVEC_GLDS_TAIL
-                                     : "=&s"(keep) : "v"(v[0]), "s"(sbase), "s"(lds0), "v"(v[1]), "v"(v[2]), "v"(v[3]) : "memory", "scc");
-  if constexpr (N == 5) asm volatile(AVEC_GLDS_HEAD AVEC_GLDS_NEXT(4) AVEC_GLDS_NEXT(5) AVEC_GLDS_NEXT(6) AVEC_GLDS_NEXT(7) AVEC_GLDS_TAIL
-                                     : "=&s"(keep) : "v"(v[0]), "s"(sbase), "s"(lds0), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]) : "memory", "scc");
-}
-#undef AVEC_GLDS_HEAD
-#undef AVEC_GLDS_NEXT
-#undef AVEC_GLDS_TAIL
 template <int V> struct IntC { static constexpr int value = V; };

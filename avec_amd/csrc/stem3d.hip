@@ -8,26 +8,13 @@
 // k = (kd*7 + kh)*7 + kw.  BatchNorm statistics of y are accumulated per workgroup and leave through the two-pass reduction workspace.
 #include "vec.h"
 #include "avec_hip.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef short v4s_t __attribute__((ext_vector_type(4)));
+#include "wave_prims.h"
 
 static constexpr int S3_HALVES = 2;      // an output frame is processed as two bands of rows
 static constexpr int S3_C = 64;          // output channels
 static constexpr int S3_K = 245;         // taps
 
 struct Stem3 { int T3, H, W, OH, OW, ohn, SH, WP; long long items; };     // ohn: output rows per band; SH: staged input rows per frame; WP: staged row pitch
-
-__device__ __forceinline__ f32x16 mma16(const chunk16& a, const chunk16& b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ chunk16 tr8s(const char* p0, const char* p1) {
-  typedef __attribute__((address_space(3))) v4s_t* lp_t;
-  const v4s_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p0), b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p1);
-  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
-  chunk16 f; f.w[0] = ua.x; f.w[1] = ua.y; f.w[2] = ub.x; f.w[3] = ub.y; return f;
-}
 
 // stage the band's input: slab[kd][r][x] (bf16) = video[clip][fr + kd - 2][2*oh0 - 3 + r][x - 3], zero outside the clip / frame.
 // Loads are issued in batches of 8 independent (clamped, unconditional) accesses per thread before any is consumed: a load-store loop
@@ -228,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void stem3_wgrad_kernel(const float* __rest
         }
         ow0 += 16; if (ow0 >= G.OW) { ow0 -= G.OW; ++ohl0; }
         const char* db = dyt + (16 * s) * 128;
-        const chunk16 fb0 = tr8s(db + offb[0][0], db + offb[0][1]), fb1 = tr8s(db + offb[1][0], db + offb[1][1]);
+        const chunk16 fb0 = lds_tr8(db + offb[0][0], db + offb[0][1]), fb1 = lds_tr8(db + offb[1][0], db + offb[1][1]);
 #pragma unroll
         for (int i = 0; i < 2; ++i) { acc[i][0] = mma16(fa[i], fb0, acc[i][0]); acc[i][1] = mma16(fa[i], fb1, acc[i][1]); }
       }

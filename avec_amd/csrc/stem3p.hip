@@ -16,12 +16,10 @@
 #include <type_traits>
 #include "vec.h"
 #include "avec_hip.h"
+#include "wave_prims.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
+// this file's own zero page (see avec_zero16 in wave_prims.h): static, named inside lambdas, hence reached through the GOT; the shared inline page would change
+// the address arithmetic and with it the schedule of every kernel below
 static __device__ __attribute__((aligned(64))) unsigned char s3p_zero16[64];
 
 static constexpr int S3P_C = 64;
@@ -38,10 +36,6 @@ struct S3P {
   int RING;                // forward: pixels of the conv-output ring (3 rows + one 128-pixel tile)
   long long items;         // clips * T3 * NB
 };
-
-__device__ __forceinline__ f32x16 s3p_mma(const chunk16& a, const chunk16& b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
 
 // LDS-DMA of the band's input: slab[(kd * SH + r) * pitch + 16 * j] <- chunk j of input row ir0 + r of frame fr + kd - 2 (zero page outside the clip / frame, and
 // for the two padding chunks).  Every lane issues slab_bytes / 4096 unconditional loads.
@@ -78,8 +72,8 @@ __device__ __forceinline__ void s3p_conv_tile(const char* slab, int ohl, int ow,
   for (int s = 0; s < 18; ++s) {
     if (s + 3 < 18) fa[s + 3] = ldfrag(s + 3);
     asm volatile("" ::: "memory");
-    acc[0] = s3p_mma(fa[s], wf[s][0], acc[0]);
-    acc[1] = s3p_mma(fa[s], wf[s][1], acc[1]);
+    acc[0] = mma16(fa[s], wf[s][0], acc[0]);
+    acc[1] = mma16(fa[s], wf[s][1], acc[1]);
   }
 }
 
@@ -279,8 +273,8 @@ __device__ __forceinline__ void s3p_conv_tile_t(const char* slab, int ohl, int o
   for (int s = 0; s < 18; ++s) {
     if (s + 3 < 18) fa[s + 3] = ldfrag(s + 3);
     asm volatile("" ::: "memory");
-    acc[0] = s3p_mma(wf[s][0], fa[s], acc[0]);
-    acc[1] = s3p_mma(wf[s][1], fa[s], acc[1]);
+    acc[0] = mma16(wf[s][0], fa[s], acc[0]);
+    acc[1] = mma16(wf[s][1], fa[s], acc[1]);
   }
 }
 
@@ -380,20 +374,7 @@ struct S3W { int SLOT, DPB, IXB, CH, NCH; long long units; };      // bytes of a
 
 #define S3P_BAR() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
 
-__device__ __forceinline__ chunk16 s3p_tr8(const char* p0, const char* p1) {
-  typedef short v4s_t __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) v4s_t* lp_t;
-  const v4s_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p0), b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p1);
-  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
-  chunk16 f; f.w[0] = ua.x; f.w[1] = ua.y; f.w[2] = ub.x; f.w[3] = ub.y; return f;
-}
-
-// LDS-DMA hidden from hipcc (cdna_hip_programming.md 5.7): the compiler otherwise drains the queue (s_waitcnt vmcnt(0)) in front of the next LDS access it cannot
-// prove disjoint from the DMA target, i.e. right behind the prefetch.  Completion is counted by hand: one vmcnt(0) + barrier at the end of a frame.
-__device__ __forceinline__ void s3p_glds16(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
+// The DMA goes through glds16 (wave_prims.h), hidden from hipcc; completion is counted by hand: one vmcnt(0) + barrier at the end of a frame.
 
 // Pixel order inside a band (all three parts agree on it): a STEP is 16 pixels = 4 rows x 4 columns of the conv output, k = 4 rho + kappa; step S covers rows 4 R .. 4 R + 3 and
 // columns 4 Cg .. 4 Cg + 3, (R, Cg) = (S / ncg, S % ncg), ncg = OW / 4; a tile is 8 steps (tile row m = 16 s + k).  With this order the gather address of a lane's 8 pixels of a
@@ -483,7 +464,7 @@ __global__ __launch_bounds__(512) void stem3p_wgrad_roles_kernel(const bf16* __r
     const int row = tid / G.CPR, j = tid - row * G.CPR; const int ih = ir0 + row;
     const bool ok = row < G.SH && itf >= 0 && itf < G.T3 && ih >= 0 && ih < G.H && j >= 1 && j <= G.CPR - 2;
     const void* sp = ok ? (const void*)(vb + ((clip * G.T3 + itf) * (long long)G.H + ih) * G.W + (j - 1) * 8) : (const void*)s3p_zero16;
-    s3p_glds16(sp, lds0 + slot * Q.SLOT + wave * 1024);
+    glds16(sp, lds0 + slot * Q.SLOT + wave * 1024);
   };
   // the band's pooled rows ph0 .. ph0 + pn of frame cf: contiguous in memory; rows beyond PH come from the zero page
   auto dma_pooled = [&](long long cf, int ph0, int buf) {
@@ -493,12 +474,12 @@ __global__ __launch_bounds__(512) void stem3p_wgrad_roles_kernel(const bf16* __r
     for (int q0 = wave * 64; q0 < Q.DPB / 16; q0 += 512) {          // 8 chunks of 16 B per pooled pixel
       const int q = q0 + lane;
       const void* sp = (q >> 3) < valid_px ? (const void*)(dpm + dp0 + (long long)q * 8) : (const void*)s3p_zero16;
-      s3p_glds16(sp, lds0 + 6 * Q.SLOT + buf * Q.DPB + q0 * 16);
+      glds16(sp, lds0 + 6 * Q.SLOT + buf * Q.DPB + q0 * 16);
     }
     for (int q0 = wave * 64; q0 < Q.IXB / 16; q0 += 512) {          // 4 chunks per pooled pixel
       const int q = q0 + lane;
       const void* sp = (q >> 2) < valid_px ? (const void*)(idx + dp0 + (long long)q * 16) : (const void*)s3p_zero16;
-      s3p_glds16(sp, lds0 + 6 * Q.SLOT + 2 * Q.DPB + buf * Q.IXB + q0 * 16);
+      glds16(sp, lds0 + 6 * Q.SLOT + 2 * Q.DPB + buf * Q.IXB + q0 * 16);
     }
   };
 
@@ -545,8 +526,8 @@ __global__ __launch_bounds__(512) void stem3p_wgrad_roles_kernel(const bf16* __r
           if (s + 4 < 18) fa[s + 4] = ldfrag(s + 4);
           asm volatile("" ::: "memory");
           asm volatile("" : "+v"(fa[s].w[0]), "+v"(fa[s].w[1]), "+v"(fa[s].w[2]), "+v"(fa[s].w[3]));      // (the use stays below the requests of step s + 4)
-          z[0] = s3p_mma(wf[s][0], fa[s], z[0]);
-          z[1] = s3p_mma(wf[s][1], fa[s], z[1]);
+          z[0] = mma16(wf[s][0], fa[s], z[0]);
+          z[1] = mma16(wf[s][1], fa[s], z[1]);
         }
         char* tw = tiles + (t & 1) * 16384 + trow * 128;
 #pragma unroll
@@ -632,7 +613,7 @@ __global__ __launch_bounds__(512) void stem3p_wgrad_roles_kernel(const bf16* __r
         for (int s = 0; s < 8; ++s) {                               // 16 pixels per step: this lane's 8 = rows 2 g, 2 g + 1 x 4 columns
           if (s < nst) {
             const char* db = tb + (16 * s) * 128;
-            const chunk16 fb0 = s3p_tr8(db + offb[0][0], db + offb[0][1]), fb1 = s3p_tr8(db + offb[1][0], db + offb[1][1]);
+            const chunk16 fb0 = lds_tr8(db + offb[0][0], db + offb[0][1]), fb1 = lds_tr8(db + offb[1][0], db + offb[1][1]);
             if (s + 1 < 8 && s + 1 < nst) gather(s + 1, gl[(s + 1) & 1]);
             asm volatile("" ::: "memory");
 #pragma unroll
@@ -644,7 +625,7 @@ __global__ __launch_bounds__(512) void stem3p_wgrad_roles_kernel(const bf16* __r
               chunk16 fa2;
 #pragma unroll
               for (int e = 0; e < 8; e += 2) fa2.w[e >> 1] = gl[s & 1][tg][e] | (gl[s & 1][tg][e + 1] << 16);
-              acc[tg][0] = s3p_mma(fa2, fb0, acc[tg][0]); acc[tg][1] = s3p_mma(fa2, fb1, acc[tg][1]);
+              acc[tg][0] = mma16(fa2, fb0, acc[tg][0]); acc[tg][1] = mma16(fa2, fb1, acc[tg][1]);
             }
           }
         }

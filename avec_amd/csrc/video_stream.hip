@@ -13,9 +13,7 @@
 #include <type_traits>
 #include "vec.h"
 #include "avec_hip.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 vs_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float vs_f32x16;
+#include "wave_prims.h"
 
 static constexpr int VS_C = 64;
 
@@ -49,9 +47,6 @@ __device__ __forceinline__ VsSlot vs_slot(const VsState& st, const long long* n_
   return s;
 }
 
-__device__ __forceinline__ vs_f32x16 vs_mma(const chunk16& a, const chunk16& b, vs_f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(vs_bf16x8, a), __builtin_bit_cast(vs_bf16x8, b), c, 0, 0, 0);
-}
 // four consecutive pixels of one channel into the conv tile (p is a multiple of 4, CS is even for bf16: 4-byte aligned)
 __device__ __forceinline__ void vs_put4(bf16* p, float v0, float v1, float v2, float v3) { ((uint32_t*)p)[0] = f32x2_to_bf16x2(v0, v1); ((uint32_t*)p)[1] = f32x2_to_bf16x2(v2, v3); }
 __device__ __forceinline__ void vs_put4(float* p, float v0, float v1, float v2, float v3) { p[0] = v0; p[1] = v1; p[2] = v2; p[3] = v3; }
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void video_stem_stream_kernel(const float* 
       const int p = t0 + 32 * wave + pl; const int pc = p < npx ? p : 0;
       const int ohl = pc / G.OW, ow = pc - ohl * G.OW;
       const char* pix = (const char*)slab + (2 * ohl) * pitch + 4 * ow + 8;
-      vs_f32x16 acc[2];
+      f32x16 acc[2];
 #pragma unroll
       for (int q = 0; q < 16; ++q) { acc[0][q] = 0.f; acc[1][q] = 0.f; }
 #pragma unroll
@@ -126,8 +121,8 @@ __global__ __launch_bounds__(256, 2) void video_stem_stream_kernel(const float* 
         const int offA = rowoff[2 * k > 34 ? 34 : 2 * k], offB = rowoff[2 * k + 1 > 34 ? 34 : 2 * k + 1];
         const uint32_t* rp = (const uint32_t*)(pix + (g ? offB : offA));
         chunk16 fa; fa.w[0] = rp[0]; fa.w[1] = rp[1]; fa.w[2] = rp[2]; fa.w[3] = rp[3];
-        acc[0] = vs_mma(fa, wf[k][0], acc[0]);
-        acc[1] = vs_mma(fa, wf[k][1], acc[1]);
+        acc[0] = mma16(fa, wf[k][0], acc[0]);
+        acc[1] = mma16(fa, wf[k][1], acc[1]);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {

@@ -16,32 +16,23 @@
 // Workgroup = 8 waves = 64 output channels x 128 input channels x 9 taps (wave: one 32 x 32 block, nine accumulator tiles), a slice of the image rows; LDS = a ring of
 // two stages of KS K-steps (dy rows [r, r + 16 KS) x 64 channels, x rows [r - 1, r + 16 KS + 1) x 128 channels) fed by LDS-DMA; fp32 atomics at the end, several
 // layers per launch (avec_wgrad3x3_c128_grouped).
-#include "common.h"
+#include "wave_prims.h"
 #include "vec.h"
 #include "avec_hip.h"
 
 #ifndef WP_ABL
 #define WP_ABL 0          // timing experiments: 1 no LDS-DMA after the first stage, 2 no MFMA, 4 no final atomics, 8 no row masks
 #endif
-typedef __attribute__((ext_vector_type(16))) float wp_f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 wp_bf16x8;
-typedef short wp_v4s __attribute__((ext_vector_type(4)));
 
-__device__ __attribute__((aligned(64))) unsigned char wp_zero16[64];
-
-__device__ __forceinline__ void wp_glds16(const void* gsrc, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
 __device__ __forceinline__ uint2 wp_tr(const char* p) {
-  typedef __attribute__((address_space(3))) wp_v4s* lp_t;
+  typedef __attribute__((address_space(3))) v4s_t* lp_t;
   return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)p));
 }
 struct WpFrag { uint2 lo, hi; };      // k-elements 0..3 | 4..7 of the lane's eight
-__device__ __forceinline__ wp_f32x16 wp_mma(const WpFrag& a, const WpFrag& b, wp_f32x16 c) {
+__device__ __forceinline__ f32x16 wp_mma(const WpFrag& a, const WpFrag& b, f32x16 c) {
   chunk16 fa, fb; fa.w[0] = a.lo.x; fa.w[1] = a.lo.y; fa.w[2] = a.hi.x; fa.w[3] = a.hi.y; fb.w[0] = b.lo.x; fb.w[1] = b.lo.y; fb.w[2] = b.hi.x; fb.w[3] = b.hi.y;
   if (WP_ABL & 2) { asm volatile("" :: "v"(fa.w[0]), "v"(fa.w[1]), "v"(fa.w[2]), "v"(fa.w[3]), "v"(fb.w[0]), "v"(fb.w[1]), "v"(fb.w[2]), "v"(fb.w[3])); return c; }
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wp_bf16x8, fa), __builtin_bit_cast(wp_bf16x8, fb), c, 0, 0, 0);
+  return mma16(fa, fb, c);
 }
 
 struct WpArgs { const bf16* x; const bf16* dy; float* dw; int N, C, H, W; };
@@ -58,11 +49,6 @@ template <int H_, int W_, int KS_> struct WpGeom {
   static constexpr int PAIRS = 3 * (3 * W - 2);           // MFMAs per wave and K-step
 };
 
-// LDS-DMA with a scalar base and a per-lane 32-bit byte offset (no VALU on the issue path)
-__device__ __forceinline__ void wp_glds16_s(unsigned voff, const void* sbase, unsigned lds_dst_uniform) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst_uniform) : "memory");
-}
 template <int OFF> __device__ __forceinline__ uint2 wp_tr_o(unsigned addr) {
   static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
   uint2 v; asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory"); return v;
@@ -94,7 +80,7 @@ template <typename G, int I> struct WpIt {
 };
 
 template <typename G, int I>
-__device__ __forceinline__ void wp_iter(WpRegs& R, wp_f32x16 (&acc)[9], unsigned (&m0)[4], unsigned (&m2)[4], const int oyb, const bool hi_half, const unsigned (&aA)[2], const unsigned (&aB)[3][2]) {
+__device__ __forceinline__ void wp_iter(WpRegs& R, f32x16 (&acc)[9], unsigned (&m0)[4], unsigned (&m2)[4], const int oyb, const bool hi_half, const unsigned (&aA)[2], const unsigned (&aB)[3][2]) {
   typedef WpIt<G, I> It;
   constexpr int H = G::H, W = G::W, NIT = G::KS * W, g = It::g;
   constexpr bool more = I + 1 < NIT;
@@ -164,7 +150,6 @@ __device__ __attribute__((noinline)) void wp_body(const WpArgs a_, char* const s
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int C = a.C;
   const int nci = C >> 7, cog = kind / nci, cig = kind - cog * nci;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t)smem;
   const int NR = a.N * H;                                  // image rows in the tensor
 
@@ -193,21 +178,21 @@ __device__ __attribute__((noinline)) void wp_body(const WpArgs a_, char* const s
     const char* dyb = (const char*)(a.dy + (long long)rs * W * C); const char* xb = (const char*)(a.x + (long long)(rs - 1) * W * C);
     if (rs >= 1 && rs + ROWS + 1 <= NR) {                                         // every row of both slabs is inside the tensor (all stages but the first and the last)
 #pragma unroll
-      for (int k = 0; k < G::DPL; ++k) { if (wave + 8 * k >= G::DYI) break; wp_glds16_s(dpl[k], dyb, d0 + (wave + 8 * k) * 1024); }      // (wave-uniform)
+      for (int k = 0; k < G::DPL; ++k) { if (wave + 8 * k >= G::DYI) break; glds16_s(dyb, dpl[k], d0 + (wave + 8 * k) * 1024); }      // (wave-uniform)
 #pragma unroll
-      for (int k = 0; k < G::XPL; ++k) { if (wave + 8 * k >= G::XI) break; wp_glds16_s(xpl[k], xb, x0 + (wave + 8 * k) * 1024); }
+      for (int k = 0; k < G::XPL; ++k) { if (wave + 8 * k >= G::XI) break; glds16_s(xb, xpl[k], x0 + (wave + 8 * k) * 1024); }
     } else {                                                                      // rows outside the tensor come from the zero page
 #pragma unroll
       for (int k = 0; k < G::DPL; ++k) {
         if (wave + 8 * k >= G::DYI) break;
         int rr; bool u; const unsigned o = dslot(k, rr, u);
-        wp_glds16((u && rs + rr < NR) ? (const void*)(dyb + o) : (const void*)wp_zero16, d0 + (wave + 8 * k) * 1024);
+        glds16((u && rs + rr < NR) ? (const void*)(dyb + o) : (const void*)avec_zero16, d0 + (wave + 8 * k) * 1024);
       }
 #pragma unroll
       for (int k = 0; k < G::XPL; ++k) {
         if (wave + 8 * k >= G::XI) break;
         int rr; bool u; const unsigned o = xslot(k, rr, u); const int r = rs - 1 + rr;
-        wp_glds16((u && r >= 0 && r < NR) ? (const void*)(xb + o) : (const void*)wp_zero16, x0 + (wave + 8 * k) * 1024);
+        glds16((u && r >= 0 && r < NR) ? (const void*)(xb + o) : (const void*)avec_zero16, x0 + (wave + 8 * k) * 1024);
       }
     }
   };
@@ -226,7 +211,7 @@ __device__ __attribute__((noinline)) void wp_body(const WpArgs a_, char* const s
       aB[kh][h] = lds0 + G::DYI * 1024 + rr * RWX * 256 + (((2 * ciq + (g4 & 1)) ^ (2 * (rr & 3))) << 5) + (t & 3) * 8;
     }
   }
-  wp_f32x16 acc[9];
+  f32x16 acc[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j)
 #pragma unroll
