@@ -429,3 +429,135 @@ extern "C" int avec_relpos_attention_stream(int dtype, const void* q, const void
   else { if (int r = avec_lds_optin(attn_stream_kernel<float>, lds)) return r; hipLaunchKernelGGL((attn_stream_kernel<float>), grid, dim3(256), lds, st, a); }
   AVEC_LAUNCH_CHECK(); return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Streaming form with look-ahead (nnet.ConformerLookaheadStreamSession): per slot a WINDOW of Wq rows, of which the first n = ceil(nvalid / div) hold frames and the
+// first c = ncommit / div (<= min(n, Tq)) are final; the Wq queries attend over the two-sided band  -R <= p_i - p_j <= L,
+//     scores[i][j] = scale * q_i . (k_j + E[p_i - p_j + R]),      E [L + R + 1][lde]: row delta + R = pos_layer(PE(delta)), delta = -R .. L.
+// Keys and values: the last L ring frames before p0 = reset[b] ? 0 : pos[b] / div, then the window rows < n, read from the fused q | k | v rows and never from the ring.
+// Column c (0 <= c < L + Wq) is the frame at position p0 - L + c; query i keeps it iff -R <= i + L - c <= L, the position is >= 0 and, for a window row, c - L < n: a row at
+// or past n is left out whatever it holds.  A query that keeps no key (possible only at or past n) writes zeros.  Only the rows i < c are appended to the ring (cap = L + Tq
+// rows, frame p in row p mod cap): frame p0 + i lands on the row that held frame p0 + i - cap < p0 - L, which no query of this launch reads, so the query tiles of a
+// (slot, head) need no synchronisation, as in attn_stream_kernel; the rows c .. n - 1 come back, recomputed, in the next window.
+// grid (ceil(Wq / 32), B * H); the arithmetic is attn_stream_kernel's.
+// ------------------------------------------------------------------------------------------------
+struct AttnStreamLa {
+  const void *q, *k, *v; long long ld; const void* e; long long lde; void *kc, *vc;
+  const long long* pos; const unsigned char* reset; const long long *nvalid, *ncommit; int div;
+  void* o; long long ldo; int B, H, Wq, Tq, d, L, R; float scale;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void attn_stream_la_kernel(AttnStreamLa a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int d = a.d, DP = d | 1, Wq = a.Wq, L = a.L, R = a.R, cap = L + a.Tq;
+  float* Ks = sm; float* Vs = Ks + TK * DP; float* Es = Vs + TK * DP; float* Qs = Es + (TQ + TK - 1) * DP; float* Ps = Qs + TQ * DP;      // Ps [TQ][64]
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
+  const int i0 = blockIdx.x * TQ;
+  long long p0 = (a.reset && a.reset[b]) ? 0 : a.pos[b] / a.div; if (p0 < 0) p0 = 0;
+  const long long nv = (a.nvalid[b] + a.div - 1) / a.div; const int n = nv < 0 ? 0 : (nv > Wq ? Wq : (int)nv);
+  const long long nc = a.ncommit[b] / a.div; const int cmax = n < a.Tq ? n : a.Tq; const int c_ = nc < 0 ? 0 : (nc > cmax ? cmax : (int)nc);
+  const long long ldc = (long long)a.H * d;
+  const T* qp = (const T*)a.q + (long long)b * Wq * a.ld + h * d;
+  const T* kp = (const T*)a.k + (long long)b * Wq * a.ld + h * d;
+  const T* vp = (const T*)a.v + (long long)b * Wq * a.ld + h * d;
+  T* kcb = (T*)a.kc + (long long)b * cap * ldc + h * d;
+  T* vcb = (T*)a.vc + (long long)b * cap * ldc + h * d;
+  const T* ep = (const T*)a.e + h * d;
+  for (int r = w; r < TQ; r += 4) {
+    const int i = i0 + r; const bool ok = i < Wq;
+    for (int c = lane; c < d; c += 64) Qs[r * DP + c] = ok ? ldf(qp + (long long)i * a.ld + c) : 0.f;
+    if (i < c_) {
+      const long long crow = (p0 + i) % cap;
+      for (int c = lane; c < d; c += 64) { kcb[crow * ldc + c] = kp[(long long)i * a.ld + c]; vcb[crow * ldc + c] = vp[(long long)i * a.ld + c]; }
+    }
+  }
+  float m_run[RPW], l_run[RPW], acc[RPW][NCS];
+#pragma unroll
+  for (int rr = 0; rr < RPW; ++rr) { m_run[rr] = -INFINITY; l_run[rr] = 0.f; for (int u = 0; u < NCS; ++u) acc[rr][u] = 0.f; }
+  const int i_last = min(i0 + TQ, Wq) - 1;
+  const int c_end = min(i_last + L + R, L + n - 1);             // the last column any query of the tile may keep
+  const bool wave_live = i0 + w * RPW < Wq;
+  for (int c0 = i0; c0 <= c_end; c0 += TK) {
+    __syncthreads();
+    for (int r = w; r < TK; r += 4) {
+      const int c = c0 + r; bool ok = c <= c_end; const T *kr = kp, *vr = vp;
+      if (c < L) { const long long p = p0 - L + c; ok = ok && p >= 0; const long long row = ok ? p % cap : 0; kr = kcb + row * ldc; vr = vcb + row * ldc; }
+      else { const int ci = c - L; ok = ok && ci < n; const long long row = ok ? ci : 0; kr = kp + row * a.ld; vr = vp + row * a.ld; }
+      for (int ch = lane; ch < d; ch += 64) { Ks[r * DP + ch] = ok ? ldf(kr + ch) : 0.f; Vs[r * DP + ch] = ok ? ldf(vr + ch) : 0.f; }
+    }
+    const int dmin = i0 + L + R - c0 - (TK - 1);                // Es row r holds E[dmin + r]
+    for (int r = w; r < TQ + TK - 1; r += 4) {
+      const int dl = dmin + r; const bool ok = dl >= 0 && dl <= L + R; const T* er = ep + (long long)(ok ? dl : 0) * a.lde;
+      for (int ch = lane; ch < d; ch += 64) Es[r * DP + ch] = ok ? ldf(er + ch) : 0.f;
+    }
+    __syncthreads();
+    if (wave_live) {
+      const int c = c0 + lane;
+#pragma unroll
+      for (int rr = 0; rr < RPW; ++rr) {
+        const int ri = w * RPW + rr, i = i0 + ri; const int dl = i + L - c;
+        const bool keep = i < Wq && dl >= -R && dl <= L && (c >= L ? c - L < n : p0 - L + c >= 0);
+        const float* qrow = Qs + ri * DP; const float* krow = Ks + lane * DP; const float* erow = Es + (ri + TK - 1 - lane) * DP;
+        float s = 0.f;
+        for (int ch = 0; ch < d; ++ch) s += qrow[ch] * (krow[ch] + erow[ch]);
+        s *= a.scale;
+        const float tmax = wave_max(keep ? s : -INFINITY);
+        const float m_new = fmaxf(m_run[rr], tmax);
+        float pval = 0.f;
+        if (m_new != -INFINITY) {                               // (no kept key so far in this row: nothing to rescale, nothing to add)
+          const float alpha = (m_run[rr] == -INFINITY) ? 0.f : __expf(m_run[rr] - m_new);
+          pval = keep ? __expf(s - m_new) : 0.f;
+          l_run[rr] = l_run[rr] * alpha + wave_sum(pval);
+          for (int u = 0; u < NCS; ++u) acc[rr][u] *= alpha;
+          m_run[rr] = m_new;
+        }
+        Ps[ri * 64 + lane] = pval;
+      }
+    }
+    __syncthreads();
+    if (wave_live) {
+#pragma unroll
+      for (int rr = 0; rr < RPW; ++rr) {
+        const float* prow = Ps + (w * RPW + rr) * 64;
+        for (int jj = 0; jj < TK; ++jj) {
+          const float pj = prow[jj];
+#pragma unroll
+          for (int u = 0; u < NCS; ++u) if (lane + 64 * u < d) acc[rr][u] += pj * Vs[jj * DP + lane + 64 * u];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < RPW; ++rr) {
+    const int i = i0 + w * RPW + rr;
+    if (i >= Wq) continue;
+    const float inv = l_run[rr] > 0.f ? 1.f / l_run[rr] : 0.f;  // a row that kept no key (at or past n only): zeros, not 0 / 0
+    T* op = (T*)a.o + ((long long)b * Wq + i) * a.ldo + h * d;
+#pragma unroll
+    for (int u = 0; u < NCS; ++u) if (lane + 64 * u < d) stf(op + lane + 64 * u, acc[rr][u] * inv);
+  }
+}
+
+extern "C" int avec_relpos_attention_stream_la(int dtype, const void* q, const void* k, const void* v, long long ld, const void* e, long long lde, void* kcache, void* vcache,
+                                               long long cache_bytes, const long long* pos, const unsigned char* reset, const long long* nvalid, const long long* ncommit,
+                                               int div, void* o, long long ldo, int B, int H, int Wq, int Tq, int d, int L, int R, float scale, hipStream_t st) {
+  AVEC_CHECK_ARG(q && k && v && e && kcache && vcache && pos && nvalid && ncommit && o,
+                 "relpos_attention_stream_la: null pointer (q, k, v, e, kcache, vcache, pos, nvalid, ncommit and o are required)");
+  AVEC_CHECK_ARG(B > 0 && H > 0 && Tq > 0 && Wq >= Tq && L >= 0 && R >= 0 && div > 0 && d > 0 && d <= 64 * NCS,
+                 "relpos_attention_stream_la: bad dims B=%d H=%d Wq=%d Tq=%d d=%d L=%d R=%d div=%d (Wq >= Tq, d <= %d)", B, H, Wq, Tq, d, L, R, div, 64 * NCS);
+  AVEC_CHECK_ARG(ld >= (long long)H * d && ldo >= (long long)H * d && lde >= (long long)H * d, "relpos_attention_stream_la: row strides ld=%lld ldo=%lld lde=%lld below H * d = %d", ld, ldo, lde, H * d);
+  const long long need = avec_relpos_attention_stream_state_bytes(dtype, B, H, d, L, Tq);
+  AVEC_CHECK_ARG(cache_bytes >= need, "relpos_attention_stream_la: key / value rings of %lld bytes each, %lld needed (avec_relpos_attention_stream_state_bytes)", cache_bytes, need);
+  const uintptr_t em = dtype == AVEC_BF16 ? 1 : 3;             // element accesses only (odd head widths): element alignment
+  AVEC_CHECK_ARG(!(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)e | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)o) & em) &&
+                 !(((uintptr_t)pos | (uintptr_t)nvalid | (uintptr_t)ncommit) & 7), "relpos_attention_stream_la: misaligned pointer (tensors: element size, pos / nvalid / ncommit: 8 bytes)");
+  AVEC_CHECK_ARG(kcache != vcache, "relpos_attention_stream_la: kcache and vcache must be two buffers");
+  AttnStreamLa a{q, k, v, ld, e, lde, kcache, vcache, pos, reset, nvalid, ncommit, div, o, ldo, B, H, Wq, Tq, d, L, R, scale};
+  const int DP = d | 1; const size_t lds = (size_t)(2 * TK + (TQ + TK - 1) + TQ) * DP * 4 + (size_t)TQ * 64 * 4;
+  dim3 grid((Wq + TQ - 1) / TQ, B * H);
+  avec_note_kernel("attn_stream_la<%s>", dtype == AVEC_BF16 ? "bf16" : "f32");
+  if (dtype == AVEC_BF16) { if (int r = avec_lds_optin(attn_stream_la_kernel<bf16>, lds)) return r; hipLaunchKernelGGL((attn_stream_la_kernel<bf16>), grid, dim3(256), lds, st, a); }
+  else { if (int r = avec_lds_optin(attn_stream_la_kernel<float>, lds)) return r; hipLaunchKernelGGL((attn_stream_la_kernel<float>), grid, dim3(256), lds, st, a); }
+  AVEC_LAUNCH_CHECK(); return 0;
+}

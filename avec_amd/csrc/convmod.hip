@@ -395,16 +395,13 @@ extern "C" int avec_dwconv_glu_bwd(int dtype, const void* dc, const void* u, con
 // pass and the rows that move up into the new context, kept in registers) happens BEFORE the workgroup barrier, every write of the new context AFTER it, and no
 // other workgroup touches these columns of this slot: in place without a race.
 // ================================================================================================================================================================
+// the body of both streaming kernels: the slot starts at stage position p0, all Tq rows are convolved, the first n enter the carried context
 template <typename T>
-__global__ __launch_bounds__(256) void glu_dwconv_stream_kernel(const T* __restrict__ u, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ ss,
-                                                                T* __restrict__ out, T* state, const long long* __restrict__ pos, const unsigned char* __restrict__ reset,
-                                                                const long long* __restrict__ clen, int div, int Tq, int C, int K, int stride, int To) {
+__device__ __forceinline__ void glu_dwconv_stream_body(const T* __restrict__ u, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ ss,
+                                                       T* __restrict__ out, T* state, long long p0, int n, int Tq, int C, int K, int stride, int To) {
   extern __shared__ __attribute__((aligned(16))) float gs[];         // [(K - 1) + Tq][128] GLU outputs, row r = chunk position r - (K - 1)
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5; const int col = (blockIdx.x * 32 + tx) * 4; const int b = blockIdx.y;
   const int Hn = K - 1;
-  long long p0 = (reset && reset[b]) ? 0 : pos[b] / div; if (p0 < 0) p0 = 0;
-  int n = Tq;
-  if (clen) { long long c = (clen[b] + div - 1) / div; n = c < 0 ? 0 : (c > Tq ? Tq : (int)c); }
   const bool live = col < C; const int cc = live ? col : 0;
   float ww[KMAX][4], bb[4] = {0.f, 0.f, 0.f, 0.f}, sc[4], sh[4];
 #pragma unroll
@@ -450,6 +447,27 @@ __global__ __launch_bounds__(256) void glu_dwconv_stream_kernel(const T* __restr
     st4<T>(out + ((long long)b * To + o) * C + col, acc);
   }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void glu_dwconv_stream_kernel(const T* __restrict__ u, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ ss,
+                                                                T* __restrict__ out, T* state, const long long* __restrict__ pos, const unsigned char* __restrict__ reset,
+                                                                const long long* __restrict__ clen, int div, int Tq, int C, int K, int stride, int To) {
+  const int b = blockIdx.y;
+  long long p0 = (reset && reset[b]) ? 0 : pos[b] / div; if (p0 < 0) p0 = 0;
+  int n = Tq;
+  if (clen) { long long c = (clen[b] + div - 1) / div; n = c < 0 ? 0 : (c > Tq ? Tq : (int)c); }
+  glu_dwconv_stream_body<T>(u, w, bias, ss, out, state, p0, n, Tq, C, K, stride, To);
+}
+// Look-ahead form (nnet.ConformerLookaheadStreamSession): a window of Wq rows per slot, all convolved; only the first c = ncommit / div are final and enter the context
+// (the others come back, recomputed, in the next window).
+template <typename T>
+__global__ __launch_bounds__(256) void glu_dwconv_stream_la_kernel(const T* __restrict__ u, const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ ss,
+                                                                   T* __restrict__ out, T* state, const long long* __restrict__ pos, const unsigned char* __restrict__ reset,
+                                                                   const long long* __restrict__ ncommit, int div, int Wq, int C, int K, int stride, int To) {
+  const int b = blockIdx.y;
+  long long p0 = (reset && reset[b]) ? 0 : pos[b] / div; if (p0 < 0) p0 = 0;
+  const long long c = ncommit[b] / div;
+  glu_dwconv_stream_body<T>(u, w, bias, ss, out, state, p0, c < 0 ? 0 : (c > Wq ? Wq : (int)c), Wq, C, K, stride, To);
+}
 
 extern "C" long long avec_glu_dwconv_stream_state_bytes(int dtype, int B, int C, int K) {
   if (B <= 0 || C <= 0 || K <= 0) return 0;
@@ -475,6 +493,25 @@ extern "C" int avec_glu_dwconv_stream(int dtype, const void* u, const float* w, 
   AVEC_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int avec_glu_dwconv_stream_la(int dtype, const void* u, const float* w, const float* bias, const float* ss, void* out, void* state, long long state_bytes,
+                                         const long long* pos, const unsigned char* reset, const long long* ncommit, int div, int B, int Wq, int C, int K, int stride, hipStream_t st) {
+  AVEC_CHECK_ARG(u && w && ss && out && pos && ncommit, "glu_dwconv_stream_la: null pointer (u, w, ss, out, pos and ncommit are required)");
+  AVEC_CHECK_ARG(B > 0 && Wq > 0 && div > 0 && stride > 0 && Wq % stride == 0, "glu_dwconv_stream_la: bad dims B=%d Wq=%d div=%d stride=%d (Wq must be a multiple of the stride)", B, Wq, div, stride);
+  AVEC_CHECK_ARG(C > 0 && C % 4 == 0, "glu_dwconv_stream_la: C=%d must be a positive multiple of 4 (4-channel vector accesses)", C);
+  AVEC_CHECK_ARG(K > 0 && K <= KMAX, "glu_dwconv_stream_la: kernel size K=%d outside 1..%d", K, KMAX);
+  AVEC_CHECK_ARG(K == 1 || state, "glu_dwconv_stream_la: null state (K=%d needs %d context rows per slot)", K, K - 1);
+  AVEC_CHECK_ARG(state_bytes >= avec_glu_dwconv_stream_state_bytes(dtype, B, C, K), "glu_dwconv_stream_la: state of %lld bytes, %lld needed (avec_glu_dwconv_stream_state_bytes)",
+                 state_bytes, avec_glu_dwconv_stream_state_bytes(dtype, B, C, K));
+  AVEC_CHECK_ARG(avec_aligned16(u) && avec_aligned16(w) && avec_aligned16(bias) && avec_aligned16(ss) && avec_aligned16(out) && avec_aligned16(state),
+                 "glu_dwconv_stream_la: u, w, bias, ss, out and state must be 16-byte aligned");
+  AVEC_CHECK_ARG((((uintptr_t)pos) & 7) == 0 && (((uintptr_t)ncommit) & 7) == 0, "glu_dwconv_stream_la: pos and ncommit must be 8-byte aligned (int64)");
+  const size_t lds = (size_t)(K - 1 + Wq) * 128 * sizeof(float);
+  AVEC_CHECK_ARG(lds <= 48 * 1024, "glu_dwconv_stream_la: window of %d frames too long (K - 1 + Wq <= 96)", Wq);
+  dim3 grid((unsigned)((C / 4 + 31) / 32), (unsigned)B);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(glu_dwconv_stream_la_kernel<T>, grid, dim3(256), lds, st, (const T*)u, w, bias, ss, (T*)out, (T*)state, pos, reset, ncommit, div, Wq, C, K, stride, Wq / stride));
+  AVEC_LAUNCH_CHECK();
+  return 0;
+}
 // end of a push: pos[b] = (reset[b] ? 0 : pos[b]) + min(chunk_len[b], full)   (chunk_len NULL: full), then reset[b] = 0: the flags are consumed, the caller sets only
 // those of the next push (no clearing copy or memset after a restart).  One launch per push whether or not a slot restarts; the last reader of pos / reset in the push.
 __global__ void stream_advance_kernel(long long* pos, unsigned char* reset, const long long* clen, long long full, int B) {
@@ -487,6 +524,80 @@ __global__ void stream_advance_kernel(long long* pos, unsigned char* reset, cons
 extern "C" int avec_stream_advance(long long* pos, unsigned char* reset, const long long* chunk_len, long long full, int B, hipStream_t st) {
   AVEC_CHECK_ARG(pos && B > 0 && full > 0 && (((uintptr_t)pos) & 7) == 0 && (((uintptr_t)chunk_len) & 7) == 0, "stream_advance: bad arguments (B=%d full=%lld)", B, full);
   hipLaunchKernelGGL(stream_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, pos, reset, chunk_len, full, B);
+  AVEC_LAUNCH_CHECK();
+  return 0;
+}
+
+// ================================================================================================================================================================
+// Window control of the look-ahead session (nnet.ConformerLookaheadStreamSession): two launches around a push.  Per slot the session carries a tail of pend <= LAe
+// input frames that were heard and are not final yet, pos (committed input frames) and an `ended` flag.
+//   avec_stream_window, the first launch: the window X [B][W = Tc + LAe][D] = [tail[:pend] | x_new[:n_new] | zeros], n = pend + n_new valid frames, and what the
+//     stack's kernels read:  nvalid = n;  ncommit = c = max(0, n - LAe) rounded down to a multiple of S for a running slot, 0 for a slot that ends (`last`: nothing after
+//     this push reads its state);  emit = c for a running slot, n for one that ends.  A restarted slot has pend = 0 and is not ended; an ended slot takes no frame.
+//   avec_stream_window_advance, the last launch: tail <- X[c : n] (from X, never in place), pend = n - c (0 for a slot that ends), pos = (reset ? 0 : pos) + c,
+//     ended = (reset ? 0 : ended) | last, and the reset / last flags are cleared (consumed, as avec_stream_advance does).  The copying workgroups read nvalid / ncommit
+//     only, which this launch does not write; one thread per slot owns the counters and flags.
+// grid (rows, B), one workgroup per row.
+// ================================================================================================================================================================
+__global__ __launch_bounds__(256) void stream_window_kernel(const float* __restrict__ x_new, const float* __restrict__ tail, float* __restrict__ X, const long long* __restrict__ pend,
+                                                            const long long* __restrict__ n_new, const unsigned char* __restrict__ last, const unsigned char* __restrict__ reset,
+                                                            const unsigned char* __restrict__ ended, long long* __restrict__ nvalid, long long* __restrict__ ncommit,
+                                                            long long* __restrict__ emit, int Tc, int LAe, int D, int S) {
+  const int r = blockIdx.x, b = blockIdx.y;
+  const bool rs = reset && reset[b];
+  long long pe = rs ? 0 : pend[b]; pe = pe < 0 ? 0 : (pe > LAe ? LAe : pe);
+  long long nn = n_new ? n_new[b] : Tc; nn = nn < 0 ? 0 : (nn > Tc ? Tc : nn);
+  if (!rs && ended[b]) { pe = 0; nn = 0; }
+  const long long n = pe + nn;
+  const float* src = r < pe ? tail + ((long long)b * LAe + r) * D : (r < n ? x_new + ((long long)b * Tc + (r - pe)) * D : nullptr);
+  float* dst = X + ((long long)b * (Tc + LAe) + r) * D;
+  for (int c = threadIdx.x; c < D; c += 256) dst[c] = src ? src[c] : 0.f;
+  if (r == 0 && threadIdx.x == 0) {
+    const bool ends = last && last[b];
+    long long c = n - LAe; c = c < 0 ? 0 : c - c % S;
+    nvalid[b] = n; ncommit[b] = ends ? 0 : c; emit[b] = ends ? n : c;
+  }
+}
+extern "C" int avec_stream_window(const float* x_new, const float* tail, float* X, const long long* pend, const long long* n_new, const unsigned char* last, const unsigned char* reset,
+                                  const unsigned char* ended, long long* nvalid, long long* ncommit, long long* emit, int B, int Tc, int LAe, int D, int S, hipStream_t st) {
+  AVEC_CHECK_ARG(x_new && X && pend && ended && nvalid && ncommit && emit && (tail || LAe == 0),
+                 "stream_window: null pointer (x_new, tail, X, pend, ended, nvalid, ncommit and emit are required)");
+  AVEC_CHECK_ARG(B > 0 && Tc > 0 && LAe >= 0 && D > 0 && S > 0 && Tc % S == 0 && LAe % S == 0, "stream_window: bad dims B=%d Tc=%d LAe=%d D=%d S=%d (Tc and LAe must be multiples of S)", B, Tc, LAe, D, S);
+  AVEC_CHECK_ARG(!(((uintptr_t)x_new | (uintptr_t)tail | (uintptr_t)X) & 3) && !(((uintptr_t)pend | (uintptr_t)n_new | (uintptr_t)nvalid | (uintptr_t)ncommit | (uintptr_t)emit) & 7),
+                 "stream_window: misaligned pointer (x_new / tail / X: 4 bytes, the int64 vectors: 8 bytes)");
+  AVEC_CHECK_ARG(X != x_new && X != tail, "stream_window: X must be a buffer of its own");
+  hipLaunchKernelGGL(stream_window_kernel, dim3((unsigned)(Tc + LAe), (unsigned)B), dim3(256), 0, st, x_new, tail, X, pend, n_new, last, reset, ended, nvalid, ncommit, emit, Tc, LAe, D, S);
+  AVEC_LAUNCH_CHECK();
+  return 0;
+}
+__global__ __launch_bounds__(256) void stream_window_advance_kernel(const float* __restrict__ X, float* __restrict__ tail, long long* pend, long long* pos, const long long* __restrict__ nvalid,
+                                                                    const long long* __restrict__ ncommit, unsigned char* last, unsigned char* reset, unsigned char* ended,
+                                                                    int W, int LAe, int D) {
+  const int r = blockIdx.x, b = blockIdx.y;
+  long long n = nvalid[b], c = ncommit[b];
+  n = n < 0 ? 0 : (n > W ? W : n); c = c < 0 ? 0 : (c > n ? n : c);
+  if (r < LAe && c + r < n) {
+    const float* src = X + ((long long)b * W + c + r) * D; float* dst = tail + ((long long)b * LAe + r) * D;
+    for (int ch = threadIdx.x; ch < D; ch += 256) dst[ch] = src[ch];
+  }
+  if (r == 0 && threadIdx.x == 0) {
+    const bool rs = reset && reset[b], ends = last && last[b];
+    long long left = n - c; left = left > LAe ? LAe : left;
+    pend[b] = ends ? 0 : left;
+    pos[b] = (rs ? 0 : pos[b]) + c;
+    ended[b] = ((rs ? 0 : ended[b]) || ends) ? 1 : 0;
+    if (reset) reset[b] = 0;
+    if (last) last[b] = 0;
+  }
+}
+extern "C" int avec_stream_window_advance(const float* X, float* tail, long long* pend, long long* pos, const long long* nvalid, const long long* ncommit, unsigned char* last,
+                                          unsigned char* reset, unsigned char* ended, int B, int W, int LAe, int D, hipStream_t st) {
+  AVEC_CHECK_ARG(X && pend && pos && nvalid && ncommit && ended && (tail || LAe == 0), "stream_window_advance: null pointer (X, tail, pend, pos, nvalid, ncommit and ended are required)");
+  AVEC_CHECK_ARG(B > 0 && LAe >= 0 && W > LAe && D > 0, "stream_window_advance: bad dims B=%d W=%d LAe=%d D=%d (W = Tc + LAe)", B, W, LAe, D);
+  AVEC_CHECK_ARG(!(((uintptr_t)X | (uintptr_t)tail) & 3) && !(((uintptr_t)pend | (uintptr_t)pos | (uintptr_t)nvalid | (uintptr_t)ncommit) & 7),
+                 "stream_window_advance: misaligned pointer (X / tail: 4 bytes, the int64 vectors: 8 bytes)");
+  AVEC_CHECK_ARG((const float*)tail != X, "stream_window_advance: the tail must be a buffer of its own (it is read from X, not in place)");
+  hipLaunchKernelGGL(stream_window_advance_kernel, dim3((unsigned)(LAe > 0 ? LAe : 1), (unsigned)B), dim3(256), 0, st, X, tail, pend, pos, nvalid, ncommit, last, reset, ended, W, LAe, D);
   AVEC_LAUNCH_CHECK();
   return 0;
 }

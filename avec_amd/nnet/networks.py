@@ -7,7 +7,7 @@ import torch.nn as nn
 from .. import ops
 from .. import runtime as rt
 from . import attentions, blocks, layers, modules, preprocessing, transforms
-from .streaming import AudioFrontStreamSession, AudioStreamSession, AudioVisualStreamSession, ConformerStreamSession, VisualFrontStreamSession, VisualStreamSession
+from .streaming import AudioFrontStreamSession, AudioStreamSession, AudioVisualStreamSession, ConformerLookaheadStreamSession, ConformerStreamSession, VisualFrontStreamSession, VisualStreamSession
 
 
 class ResNet(nn.Module):
@@ -158,8 +158,11 @@ class ConformerInterCTC(nn.Module):
                 inter[self.loss_prefix + "_" + str(i)] = [logits, lengths]
         return x, lengths, inter
 
-    def stream(self, batch_size, chunk_frames):
-        """A ConformerStreamSession over this (causal, eval-mode) stack: the encoder-side counterpart of CTCBeamSearchDecoder.stream()."""
+    def stream(self, batch_size, chunk_frames, lookahead=False):
+        """A ConformerStreamSession over this (causal, eval-mode) stack: the encoder-side counterpart of CTCBeamSearchDecoder.stream().  lookahead=True: a stack whose
+        Mask has right_context > 0 gets a ConformerLookaheadStreamSession (its rows trail the input by ses.lookahead frames); without it such a stack is refused."""
+        if lookahead and getattr(self.mask, "right_context", 0) not in (0, None):
+            return ConformerLookaheadStreamSession(self, batch_size, chunk_frames)
         return ConformerStreamSession(self, batch_size, chunk_frames)
 
 

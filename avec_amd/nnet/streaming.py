@@ -5,6 +5,7 @@ a module tree or a state_dict.
     _StreamSession                      B slots, `_first`, flag vectors uploaded only when a flag is set
       _CapturableSession                a push is a fixed sequence of launches: the device side of push, capture()
         ConformerStreamSession          a causal Conformer stack
+          ConformerLookaheadStreamSession a stack with right_context > 0: a window of chunk + look-ahead per push, only the final frames are committed
         _FrontStreamSession             a front-end: count / last / reset controls, their host mirror, the schedule rules (_controls) and _commit
           AudioFrontStreamSession       waveform chunks -> stem frames
           VisualFrontStreamSession      video chunks -> ResNet features
@@ -20,7 +21,7 @@ from .. import runtime as rt
 from . import attentions, normalizations
 from .captured import CapturedStep
 
-__all__ = ["slot_mask", "ConformerStreamSession", "AudioFrontStreamSession", "AudioStreamSession", "VisualFrontStreamSession", "VisualStreamSession",
+__all__ = ["slot_mask", "ConformerStreamSession", "ConformerLookaheadStreamSession", "AudioFrontStreamSession", "AudioStreamSession", "VisualFrontStreamSession", "VisualStreamSession",
            "AudioVisualStreamSession", "CTCBeamStreamSession"]
 
 
@@ -120,10 +121,12 @@ class ConformerStreamSession(_CapturableSession):
     buffers this object owns.  Per slot a frame counter lives on the device; a restart only sets a flag that the kernels read: whatever the buffers hold from
     before the restart is older than the counter and counts as absent."""
 
+    LOOKAHEAD = False                      # what _check is told: a right_context > 0 is refused
+
     def __init__(self, stack, batch_size, chunk_frames):
         super().__init__(stack, batch_size)
         self.stack, self.Tc = stack, int(chunk_frames)
-        self.plan = self._check(stack)
+        self.plan = self._check(stack, self.LOOKAHEAD)
         self.S = 1
         for p in self.plan:
             self.S *= p["stride"]
@@ -139,8 +142,8 @@ class ConformerStreamSession(_CapturableSession):
         self._short = [False] * self.B     # host mirror of "this slot's last chunk was short" (the contract check of host-list chunk lengths: no sync)
 
     @staticmethod
-    def _check(stack):
-        """-> per block {div, stride, L, K}; raises before anything is launched"""
+    def _check(stack, lookahead=False):
+        """-> per block {div, stride, L, R, K}; raises before anything is launched"""
         if stack.training:
             raise RuntimeError("stream: the stack is in training mode (BatchNorm batch statistics and dropout are not functions of the past): call .eval() first")
         m = stack.mask
@@ -150,8 +153,10 @@ class ConformerStreamSession(_CapturableSession):
             raise NotImplementedError("stream: left_context=None would need an unbounded key/value cache; give the Mask an integer left_context")
         if not isinstance(m.left_context, int) or m.left_context < 0:
             raise NotImplementedError("stream: left_context=%r must be an integer >= 0" % (m.left_context,))
-        if m.right_context != 0:
+        if m.right_context != 0 and not lookahead:
             raise NotImplementedError("stream: right_context=%r needs look-ahead buffering (only right_context=0 is streamed)" % (m.right_context,))
+        if not isinstance(m.right_context, int) or m.right_context < 0:
+            raise NotImplementedError("stream: right_context=%r must be an integer >= 0" % (m.right_context,))
         if (m.mask_start or 0) > 1:
             raise NotImplementedError("stream: mask_start=%r opens a block of future keys at the start of the utterance (only mask_start <= 1 is causal)" % (m.mask_start,))
         plan, div = [], 1
@@ -171,25 +176,35 @@ class ConformerStreamSession(_CapturableSession):
                 raise NotImplementedError("stream: block %d depthwise conv has padding=%r: only padding='causal' depends on the past alone" % (i, getattr(dw, "padding_type", "same")))
             if not (bn.track_running_stats and bn.running_mean is not None):
                 raise NotImplementedError("stream: block %d BatchNorm keeps no running statistics" % i)
-            plan.append({"div": div, "stride": blk.stride, "L": m.left_context // div, "K": dw.kernel_size[0]})
+            if lookahead and getattr(att, "causal", False):
+                raise NotImplementedError("stream: block %d attention is causal=True, whose position table has no row for a future key (the stack's constructor refuses it "
+                                          "with right_context > 0)" % i)
+            plan.append({"div": div, "stride": blk.stride, "L": m.left_context // div, "R": m.right_context // div, "K": dw.kernel_size[0]})
             div *= blk.stride
         return plan
 
     # ---- device state ----------------------------------------------------------------------------------------------------------------------------------------------
+    def _allocate_controls(self, dev):
+        self.pos = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        self.reset_flags = self._flags(dev)
+        self.clen = torch.full((self.B,), self.Tc, dtype=torch.int64, device=dev)
+        self._clen_full = True
+
+    @staticmethod
+    def _pos_rows(p, D, dev):
+        """the sinusoid rows of E[delta], delta = 0 .. L: the first L + 1 rows of the offline table are the positions L .. 0, the same for every T"""
+        return ops.rel_pos_table(p["L"] + 1, D, dev)[:p["L"] + 1].flip(0)
+
     def _allocate(self, dev):
         B = self.B
-        self.pos = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.reset_flags = self._flags(dev)
-        self.clen = torch.full((B,), self.Tc, dtype=torch.int64, device=dev)
-        self._clen_full = True
+        self._allocate_controls(dev)
         self.state = []                    # per block: E table, key / value rings, conv context, BatchNorm scale | shift
         for p, blk in zip(self.plan, self.stack.conformer_blocks):
             att, dw, bn = blk.self_att_module.attention, blk.conv_module.layers[3], blk.conv_module.layers[4]
             D, H, L, Tq = att.dim_model, att.num_heads, p["L"], self.Tc // p["div"]
             C = dw.weight.shape[0]
-            # E[delta] = pos_layer(PE(delta)), delta = 0 .. L: the first L + 1 rows of the offline table are the positions L .. 0, the same for every T
-            pe = ops.rel_pos_table(L + 1, D, dev)[:L + 1].flip(0)
-            e = ops.linear_fwd(pe, att.pos_layer.weight, att.pos_layer.bias, L + 1, in_f32=False, out_f32=False)
+            pe = self._pos_rows(p, D, dev)                 # E = pos_layer(PE(delta)), projected once
+            e = ops.linear_fwd(pe, att.pos_layer.weight, att.pos_layer.bias, pe.shape[0], in_f32=False, out_f32=False)
             kc, vc = ops.relpos_attention_stream_state(B, H, D // H, L, Tq, dev)
             st = ops.BNState(C, pe)
             ops.bn_finalize(bn, st, 1, False)              # eval mode: scale | shift from the running statistics
@@ -205,7 +220,7 @@ class ConformerStreamSession(_CapturableSession):
         h, _, _ = ops.layernorm_fwd(x2, ln.weight, ln.bias, M, D, False, ln.eps)
         q, k, v = att.query_layer, att.key_layer, att.value_layer
         qkv = ops.qkv_project(h, ((q.weight, k.weight, v.weight), (q.bias, k.bias, v.bias)), M, D)
-        o = ops.relpos_attention_stream(qkv, st["e"], st["kc"], st["vc"], self.pos, self.reset_flags, self.clen, p["div"], B=B, H=att.num_heads, L=p["L"])
+        o = self._attend(p, st, qkv, B, att.num_heads)
         return ops.linear_fwd(o, att.output_layer.weight, att.output_layer.bias, M, in_f32=False, out_f32=True, res=x2, alpha=1.0).view(B, Tq, D)
 
     def _conv(self, p, st, blk, x):
@@ -219,7 +234,7 @@ class ConformerStreamSession(_CapturableSession):
         x2 = ops._f32c(x.reshape(M, D))
         h, _, _ = ops.layernorm_fwd(x2, ln.weight, ln.bias, M, D, False, ln.eps)
         u = ops.linear_fwd(h, pw1.weight, pw1.bias, M, in_f32=False, out_f32=False)
-        a = ops.glu_dwconv_stream(u.view(B, Tq, 2 * Dp), dw.weight, dw.bias, st["ss"], st["ctx"], self.pos, self.reset_flags, self.clen, p["div"], s)
+        a = self._dwconv(p, st, u.view(B, Tq, 2 * Dp), dw, s)
         if res_conv is not None:
             rs = res_conv.stride[0]
             R = ops.linear_fwd(x2, res_conv.weight, res_conv.bias, Mo, in_f32=(adt != torch.float32), out_f32=True, rows=ops.rows_plain(D, To, Tq, rs) if rs > 1 else None)
@@ -227,9 +242,24 @@ class ConformerStreamSession(_CapturableSession):
             R = x2
         return ops.linear_fwd(a.view(Mo, Dp), pw2.weight, pw2.bias, Mo, in_f32=False, out_f32=True, res=R, alpha=1.0).view(B, To, Dp)
 
+    # the two stateful launches and the two ends of a push: what the look-ahead session replaces
+    def _attend(self, p, st, qkv, B, H):
+        return ops.relpos_attention_stream(qkv, st["e"], st["kc"], st["vc"], self.pos, self.reset_flags, self.clen, p["div"], B=B, H=H, L=p["L"])
+
+    def _dwconv(self, p, st, u, dw, s):
+        return ops.glu_dwconv_stream(u, dw.weight, dw.bias, st["ss"], st["ctx"], self.pos, self.reset_flags, self.clen, p["div"], s)
+
+    def _begin(self, x):
+        """-> (the rows every block runs on, the input-rate count per slot that becomes out_len)"""
+        return x, self.clen
+
+    def _end(self, x):
+        ops.stream_advance(self.pos, self.reset_flags, self.clen, self.Tc)
+
     def _run(self, x):
         stack = self.stack
-        lengths, inter, j = self.clen, {}, 0
+        x, first = self._begin(x)
+        x0, lengths, inter, j = x, first, {}, 0
         for i, (p, st, blk) in enumerate(zip(self.plan, self.state, stack.conformer_blocks)):
             x = blk.ff_module1.residual_forward(x, 0.5)
             x = self._attention(p, st, blk, x)
@@ -245,9 +275,9 @@ class ConformerStreamSession(_CapturableSession):
                 lengths = ops.len_affine(lengths, 1, p["stride"], 1)
             if logits is not None:
                 inter[stack.loss_prefix + "_" + str(i)] = [logits, lengths]
-        if lengths is self.clen:
+        if lengths is first:
             lengths = lengths.clone()
-        ops.stream_advance(self.pos, self.reset_flags, self.clen, self.Tc)
+        self._end(x0)
         return x, lengths, inter
 
     # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
@@ -299,13 +329,145 @@ class ConformerStreamSession(_CapturableSession):
         chunk_len are computed from whatever was passed and never reach the carried state.  reset: slots to restart before this chunk, a list of indices or a host
         bool mask [B]; the first push restarts every slot.  No host synchronisation after the first push; after capture() the results are static tensors that the
         next push overwrites."""
+        self._check_chunk(x_chunk)
+        mask, host_len = self._controls(chunk_len, reset)
+        return self._push(x_chunk, mask, host_len, chunk_len)
+
+    def _check_chunk(self, x_chunk):
         if x_chunk.dim() != 3 or x_chunk.shape[0] != self.B or x_chunk.shape[1] != self.Tc:
             raise ValueError("push: chunk %s for a session of %d slots x %d frames" % (tuple(x_chunk.shape), self.B, self.Tc))
         rt.require_gpu(x_chunk)
         if self.stack.training:
             raise RuntimeError("push: the stack went back to training mode; call .eval()")
-        mask, host_len = self._controls(chunk_len, reset)
-        return self._push(x_chunk, mask, host_len, chunk_len)
+
+
+class ConformerLookaheadStreamSession(ConformerStreamSession):
+    """ConformerInterCTC.stream(lookahead=True): a stack with Mask(left_context=L, right_context=R > 0) run chunk by chunk.  The attention of a block behind total
+    stride div sees R // div future frames at its own rate, R // div * div input frames; nothing else in a block looks ahead.  With LA the sum of these over the blocks,
+    the stack's rows for input frames < n - LA depend on input frames < n alone.  `lookahead` = LAe is LA rounded up to the total stride, `window` = W = Tc + LAe.
+    Every push runs the stack on a window per slot: the pend <= LAe frames carried from earlier pushes, then the new chunk, n valid frames in all.  A running slot
+    commits c = max(0, n - LAe) of them: the first c / div key / value rows of each attention go to its ring, the first c / div pre-GLU rows of each convolution to its
+    context, the first c / S output rows are emitted, and the other n - c frames stay in the carried tail and are computed again in the next push.  A slot flagged
+    `last` emits all ceil(n / S) rows (offline the key-padding mask hides what lies past the length: there is no future) and then idles until it is restarted.  The
+    rows a slot has emitted equal the offline forward's, which they trail by LAe input frames; shapes and launches are fixed, so capture() works as on the plain
+    session.  ops.stream_window / stream_window_advance build and advance the window; pend, pos and `ended` live on the device with a host mirror for the
+    contract check of host-list counts."""
+
+    LOOKAHEAD = True
+
+    def __init__(self, stack, batch_size, chunk_frames):
+        super().__init__(stack, batch_size, chunk_frames)
+        la = sum(p["R"] * p["div"] for p in self.plan)
+        self.lookahead = -(-la // self.S) * self.S
+        self.window = self.Tc + self.lookahead
+        for i, p in enumerate(self.plan):
+            if p["K"] - 1 + self.window // p["div"] > 96:
+                raise ValueError("stream: block %d (total stride %d): the window of %d + %d frames is %d rows there and its %d-tap convolution holds context + window in "
+                                 "LDS: at most %d rows" % (i, p["div"], self.Tc, self.lookahead, self.window // p["div"], p["K"], 97 - p["K"]))
+        self._up = None                            # what self._count holds
+        self._forget()
+
+    def _forget(self):
+        B = self.B
+        self._pend, self._pos, self._ended = [0] * B, [0] * B, [False] * B      # host mirror of the device counters (None: unknown after device-tensor counts)
+
+    # ---- device state ----------------------------------------------------------------------------------------------------------------------------------------------
+    def _allocate_controls(self, dev):
+        D0 = self.stack.conformer_blocks[0].ff_module1.layers[0].normalized_shape[0]
+        self.win = ops.StreamWindowState(self.B, self.Tc, self.lookahead, D0, self.S, dev)
+        self.pos = self.win.pos
+        self.reset_flags, self.last_flags = self._flags(dev), self._flags(dev)
+        self._count = torch.zeros(self.B, dtype=torch.int64, device=dev)
+
+    @staticmethod
+    def _pos_rows(p, D, dev):
+        """the sinusoid rows of E[delta + R], delta = -R .. L: row T - 1 - delta of the offline table of any T > max(L, R)"""
+        L, R = p["L"], p["R"]
+        T = max(L, R) + 1
+        return ops.rel_pos_table(T, D, dev)[T - 1 - L:T + R].flip(0)
+
+    # ---- one push --------------------------------------------------------------------------------------------------------------------------------------------------
+    def _attend(self, p, st, qkv, B, H):
+        w = self.win
+        return ops.relpos_attention_stream_la(qkv, st["e"], st["kc"], st["vc"], w.pos, self.reset_flags, w.nvalid, w.ncommit, p["div"], B=B, H=H, L=p["L"], R=p["R"])
+
+    def _dwconv(self, p, st, u, dw, s):
+        return ops.glu_dwconv_stream_la(u, dw.weight, dw.bias, st["ss"], st["ctx"], self.win.pos, self.reset_flags, self.win.ncommit, p["div"], s)
+
+    def _begin(self, x):
+        if not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.float().contiguous()
+        return ops.stream_window(self.win, x, self._count, self.last_flags, self.reset_flags), self.win.emit
+
+    def _end(self, x):
+        ops.stream_window_advance(self.win, x, self.last_flags, self.reset_flags)
+
+    # ---- host side of a push -----------------------------------------------------------------------------------------------------------------------------------------
+    def _controls(self, chunk_len, last, reset):
+        """-> (reset mask, last mask, host counts or None for a device tensor): checks a host-list push against the contract, changes nothing"""
+        B, Tc = self.B, self.Tc
+        rmask = self._reset_mask(reset) or [False] * B
+        lmask = slot_mask(last, B)
+        if torch.is_tensor(chunk_len):
+            return rmask, lmask, None
+        if chunk_len is not None and len(chunk_len) != B:
+            raise ValueError("push: chunk_len %r for %d slots" % (list(chunk_len), B))
+        counts = []
+        for b in range(B):
+            ended = False if rmask[b] else self._ended[b]
+            if ended is None:
+                raise RuntimeError("push: slot %d was last pushed with device-tensor counts, which the host does not mirror: go on with a tensor, or reset the slot" % b)
+            c = (0 if ended else Tc) if chunk_len is None else int(chunk_len[b])
+            if c < 0 or c > Tc:
+                raise ValueError("push: chunk_len[%d] = %d outside 0 .. %d" % (b, c, Tc))
+            if ended and c > 0:
+                raise RuntimeError("push: slot %d has ended (last) and was not reset: it takes no frames until reset=[%d] starts the next utterance" % (b, b))
+            if not ended and not lmask[b] and c != Tc:
+                raise ValueError("push: slot %d is running and takes exactly chunk_frames = %d frames, got %d: fewer only with last (the commit rule keeps whole "
+                                 "output frames at every stage)" % (b, Tc, c))
+            counts.append(c)
+        return rmask, lmask, counts
+
+    def _upload(self, rmask, lmask, counts, dev_counts):
+        self._raise_flags(self.reset_flags, rmask)
+        self._raise_flags(self.last_flags, lmask)
+        if counts is None:
+            self._count.copy_(dev_counts.view(self.B), non_blocking=True)
+            self._up = None
+        elif counts != self._up:
+            self._count.copy_(torch.tensor(counts, dtype=torch.int64), non_blocking=True)
+            self._up = list(counts)
+        self._commit(rmask, lmask, counts)
+
+    def _commit(self, rmask, lmask, counts):
+        """the host mirror after a push of these controls: the arithmetic of the two control launches (counts None: device-tensor counts, the caller's contract)"""
+        B, LAe, S = self.B, self.lookahead, self.S
+        if counts is None:
+            self._pend, self._pos, self._ended = [None] * B, [None] * B, [None] * B
+            return
+        for b in range(B):
+            pend, pos, ended = (0, 0, False) if rmask[b] else (self._pend[b], self._pos[b], self._ended[b])
+            if not ended:
+                n = pend + counts[b]
+                c = 0 if lmask[b] else max(0, n - LAe) // S * S
+                pend, pos, ended = (0 if lmask[b] else n - c), pos + c, lmask[b]
+            self._pend[b], self._pos[b], self._ended[b] = pend, pos, ended
+
+    def _static_input(self, dev):
+        D0 = self.stack.conformer_blocks[0].ff_module1.layers[0].normalized_shape[0]
+        B = self.B
+        return torch.zeros(B, self.Tc, D0, dtype=torch.float32, device=dev), ([True] * B, [False] * B, [self.Tc] * B, None)
+
+    def push(self, x_chunk, chunk_len=None, last=None, reset=None):
+        """x_chunk [B, Tc, D] -> (y [B, W / S, D_out] fp32, out_len [B] int64 on the device, inter as offline).  Slot b takes the first chunk_len[b] frames (a Python
+        list or an int64 device tensor [B]; default Tc, 0 for an ended slot) and yields out_len[b] rows: those of the frames that became final in this push, which
+        trail the input by `lookahead` frames, or every remaining row for a slot in `last`.  last: slots whose utterance ends with these frames; reset: slots to
+        restart before them (each a list of indices or a host bool mask [B]); the first push restarts every slot.  With host counts the contract is checked on the
+        host, without a synchronisation: a running slot takes exactly Tc frames, a slot in `last` any 0 .. Tc, an ended slot none until it is reset.  With a device
+        tensor it is the caller's.  No host synchronisation after the first push; after capture() the results are static tensors that the next push overwrites."""
+        self._check_chunk(x_chunk)
+        rmask, lmask, counts = self._controls(chunk_len, last, reset)
+        return self._push(x_chunk, rmask, lmask, counts, chunk_len)
 
 
 class _FrontStreamSession(_CapturableSession):

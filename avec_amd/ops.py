@@ -2249,6 +2249,84 @@ def stream_advance(pos, reset, chunk_len, full):
     return pos
 
 
+# ---- with look-ahead (nnet.ConformerLookaheadStreamSession): a window of W = Tc + LAe frames per push, of which only the committed ones reach the state --------------
+class StreamWindowState:
+    """What the look-ahead session carries per slot, on the device: the tail of input frames heard and not final yet [B, LAe, D] fp32, pend (frames in it), pos
+    (committed input frames), the `ended` flag, and the counts a push's first launch writes for the others: nvalid, ncommit, emit (include/avec_hip.h).  Never cleared:
+    the first push restarts every slot."""
+
+    def __init__(self, B, Tc, LAe, D, S, device):
+        self.B, self.Tc, self.LAe, self.D, self.S = int(B), int(Tc), int(LAe), int(D), int(S)
+        self.tail = torch.zeros(B, max(LAe, 1), D, dtype=torch.float32, device=device)
+        self.pend, self.pos, self.nvalid, self.ncommit, self.emit = (torch.zeros(B, dtype=torch.int64, device=device) for _ in range(5))
+        self.ended = torch.zeros(B, dtype=torch.uint8, device=device)
+
+
+def stream_window(st, x_new, n_new=None, last=None, reset=None):
+    """first launch of a push: x_new [B, Tc, D] fp32 -> the window X [B, Tc + LAe, D] fp32 = [tail[:pend] | x_new[:n_new] | zeros]; st.nvalid / ncommit / emit are written"""
+    rt.require_gpu(x_new)
+    if not (x_new.dtype == torch.float32 and x_new.is_contiguous() and tuple(x_new.shape) == (st.B, st.Tc, st.D)):
+        raise ValueError("stream_window: x_new fp32 contiguous [%d, %d, %d] (got %s %s)" % (st.B, st.Tc, st.D, tuple(x_new.shape), x_new.dtype))
+    dev = st.pend.device
+    _slot_vec("stream_window", "n_new", n_new, st.B, dev)
+    _slot_vec("stream_window", "last", last, st.B, dev, mask=True)
+    _slot_vec("stream_window", "reset", reset, st.B, dev, mask=True)
+    X = empty((st.B, st.Tc + st.LAe, st.D), torch.float32, x_new)
+    lib.stream_window(x_new.data_ptr(), st.tail.data_ptr(), X.data_ptr(), st.pend.data_ptr(), _p(n_new), _p(last), _p(reset), st.ended.data_ptr(), st.nvalid.data_ptr(),
+                      st.ncommit.data_ptr(), st.emit.data_ptr(), st.B, st.Tc, st.LAe, st.D, st.S, rt.stream())
+    return X
+
+
+def stream_window_advance(st, X, last=None, reset=None):
+    """last launch of a push: tail <- X[ncommit : nvalid], pend, pos and `ended` move on, the reset / last flags are cleared (consumed)"""
+    dev = st.pend.device
+    _slot_vec("stream_window_advance", "last", last, st.B, dev, mask=True)
+    _slot_vec("stream_window_advance", "reset", reset, st.B, dev, mask=True)
+    if not (X.dtype == torch.float32 and X.is_contiguous() and tuple(X.shape) == (st.B, st.Tc + st.LAe, st.D)):
+        raise ValueError("stream_window_advance: X fp32 contiguous [%d, %d, %d] (got %s %s)" % (st.B, st.Tc + st.LAe, st.D, tuple(X.shape), X.dtype))
+    lib.stream_window_advance(X.data_ptr(), st.tail.data_ptr(), st.pend.data_ptr(), st.pos.data_ptr(), st.nvalid.data_ptr(), st.ncommit.data_ptr(), _p(last), _p(reset),
+                              st.ended.data_ptr(), st.B, st.Tc + st.LAe, st.LAe, st.D, rt.stream())
+
+
+def glu_dwconv_stream_la(u, w, bias, ss, state, pos, reset, ncommit, div=1, stride=1):
+    """ops.glu_dwconv_stream on a window u [B, Wq, 2C]: every row is convolved, the first ncommit / div enter the carried context.  Returns [B, Wq / stride, C] act."""
+    rt.require_gpu(u)
+    B, Wq, C2 = u.shape
+    C, K = C2 // 2, w.shape[-1]
+    adt = rt.act_dtype()
+    if not (u.dtype == adt and u.is_contiguous() and state.dtype == adt and state.is_contiguous() and ss.dtype == torch.float32 and ss.numel() >= 2 * C):
+        raise ValueError("glu_dwconv_stream_la: u and state contiguous in the activation dtype %s, ss fp32 [>= 2C] (got %s, %s, %s)" % (adt, u.dtype, state.dtype, ss.dtype))
+    _stream_ctl("glu_dwconv_stream_la", pos, reset, ncommit, B)
+    if Wq % stride:
+        raise ValueError("glu_dwconv_stream_la: %d window rows is not a multiple of the stride %d" % (Wq, stride))
+    out = empty((B * (Wq // stride), C), adt, u)
+    lib.glu_dwconv_stream_la(rt.dt(), u.data_ptr(), w.data_ptr(), _p(bias), ss.data_ptr(), out.data_ptr(), state.data_ptr() if state.numel() else None,
+                             state.numel() * state.element_size(), pos.data_ptr(), _p(reset), _p(ncommit), int(div), B, Wq, C, K, int(stride), rt.stream())
+    return out.view(B, Wq // stride, C)
+
+
+def relpos_attention_stream_la(qkv, e, kcache, vcache, pos, reset, nvalid, ncommit, div=1, *, B, H, L, R):
+    """Relative-position attention of a window over the band -R <= p_i - p_j <= L.  qkv [B * Wq, 3D] act, e [L + R + 1, D] act (row delta + R = pos_layer(PE(delta))),
+    kcache / vcache [B, L + Tq, D] act rings of ops.relpos_attention_stream_state (the first ncommit / div rows are appended).  Returns o [B * Wq, D] act."""
+    rt.require_gpu(qkv)
+    M, D3 = qkv.shape
+    D, Wq = D3 // 3, M // B
+    d, adt = D // H, rt.act_dtype()
+    Tq = kcache.shape[1] - L if kcache.dim() == 3 else 0
+    if not (qkv.dtype == adt and qkv.is_contiguous() and e.dtype == adt and e.shape[0] == L + R + 1 and e.stride(1) == 1 and kcache.dtype == adt and vcache.dtype == adt
+            and kcache.is_contiguous() and vcache.is_contiguous() and tuple(kcache.shape) == tuple(vcache.shape) == (B, L + Tq, D) and 0 < Tq <= Wq and B * Wq == M and H * d == D):
+        raise ValueError("relpos_attention_stream_la: qkv [B Wq, 3D], e [L + R + 1, D], kcache / vcache [B, L + Tq, D] (Tq <= Wq) in the activation dtype %s (got %s %s, %s %s, %s %s)"
+                         % (adt, tuple(qkv.shape), qkv.dtype, tuple(e.shape), e.dtype, tuple(kcache.shape), kcache.dtype))
+    _stream_ctl("relpos_attention_stream_la", pos, reset, nvalid, B)
+    _slot_vec("relpos_attention_stream_la", "ncommit", ncommit, B, pos.device)
+    o = empty((M, D), adt, qkv)
+    esz = qkv.element_size()
+    lib.relpos_attention_stream_la(rt.dt(), qkv.data_ptr(), qkv.data_ptr() + D * esz, qkv.data_ptr() + 2 * D * esz, 3 * D, e.data_ptr(), e.stride(0), kcache.data_ptr(),
+                                   vcache.data_ptr(), kcache.numel() * esz, pos.data_ptr(), _p(reset), _p(nvalid), _p(ncommit), int(div), o.data_ptr(), D, B, H, Wq, Tq, d, L, R,
+                                   1.0 / d ** 0.5, rt.stream())
+    return o
+
+
 # ============================================================================================
 # Streamed audio front-end (nnet.AudioFrontStreamSession): waveform chunks -> the stem's rows with the offline arithmetic (include/avec_hip.h, csrc/audio_stream.hip)
 # ============================================================================================

@@ -333,6 +333,33 @@ int avec_relpos_attention_stream(int dtype, const void* q, const void* k, const 
                                  int B, int H, int Tq, int d, int L, float scale, hipStream_t stream);
 int avec_stream_advance(long long* pos, unsigned char* reset, const long long* chunk_len, long long full, int B, hipStream_t stream);
 
+/* ---- streaming encoder with look-ahead (nnet.ConformerLookaheadStreamSession; avec_amd/csrc/convmod.hip, attention.hip) ---------------------------------------
+ * A stack with Mask(left_context=L, right_context=R > 0) run chunk by chunk: every push runs the stack on a WINDOW of W = Tc + LAe input frames per slot, the
+ * pend <= LAe frames carried from earlier pushes followed by the new chunk, n = pend + n_new of them valid.  Only c = max(0, n - LAe) frames are final (committed):
+ * they reach the carried state and are emitted; the others come back, recomputed, in the next window.  A slot that ends (`last`) emits all n and commits nothing.
+ * pos [B] int64 = COMMITTED input frames since the restart; reset as above; nvalid / ncommit [B] int64 = n and c at the input rate (a stage behind total stride div
+ * sees ceil(nvalid / div) valid and ncommit / div committed rows of its Wq = W / div).
+ *
+ * avec_stream_window: X [B][W][D] fp32 = [tail[:pend] | x_new[:n_new] | zeros] (x_new [B][Tc][D], tail [B][LAe][D]; n_new NULL: Tc), nvalid = n, ncommit = c rounded
+ *   down to a multiple of S (0 for a slot that ends), emit = c (n for a slot that ends).  A restarted slot has pend = 0 and is not ended; an ended slot takes no frame.
+ * avec_stream_window_advance ends the push: tail <- X[c : n], pend = n - c (0 for a slot that ends), pos = (reset ? 0 : pos) + c, ended = (reset ? 0 : ended) | last,
+ *   and the reset / last flags are cleared (consumed).
+ * avec_glu_dwconv_stream_la: avec_glu_dwconv_stream on the Wq window rows; the new context is the last K - 1 rows of [old context | first ncommit / div rows].
+ *   K - 1 + Wq <= 96.
+ * avec_relpos_attention_stream_la: the Wq queries over the band -R <= p_i - p_j <= L: scores = scale * q_i . (k_j + E[p_i - p_j + R]), E [L + R + 1][lde] (row
+ *   delta + R = pos_layer(PE(delta))).  Keys / values: the last L ring frames before pos / div, then the window rows below ceil(nvalid / div) (a row at or past it is
+ *   left out whatever it holds); rings as avec_relpos_attention_stream's (L + Tq rows, Tq = Tc / div), only the first ncommit / div <= Tq rows are appended.  A query
+ *   that keeps no key writes zeros. */
+int avec_stream_window(const float* x_new, const float* tail, float* X, const long long* pend, const long long* n_new, const unsigned char* last, const unsigned char* reset,
+                       const unsigned char* ended, long long* nvalid, long long* ncommit, long long* emit, int B, int Tc, int LAe, int D, int S, hipStream_t stream);
+int avec_stream_window_advance(const float* X, float* tail, long long* pend, long long* pos, const long long* nvalid, const long long* ncommit, unsigned char* last,
+                               unsigned char* reset, unsigned char* ended, int B, int W, int LAe, int D, hipStream_t stream);
+int avec_glu_dwconv_stream_la(int dtype, const void* u, const float* w, const float* bias, const float* ss, void* out, void* state, long long state_bytes,
+                              const long long* pos, const unsigned char* reset, const long long* ncommit, int div, int B, int Wq, int C, int K, int stride, hipStream_t stream);
+int avec_relpos_attention_stream_la(int dtype, const void* q, const void* k, const void* v, long long ld, const void* e, long long lde, void* kcache, void* vcache,
+                                    long long cache_bytes, const long long* pos, const unsigned char* reset, const long long* nvalid, const long long* ncommit, int div,
+                                    void* o, long long ldo, int B, int H, int Wq, int Tq, int d, int L, int R, float scale, hipStream_t stream);
+
 /* ---- streamed audio front-end (nnet.AudioFrontStreamSession; avec_amd/csrc/audio_stream.hip) -------------------------------------------------------------------
  * Waveform chunks -> the audio stem's rows, with the offline arithmetic (avec_mel_frames -> DFT GEMM -> avec_mel_power_log -> stem).  Mel frame f reads samples
  * [hop f - win/2, hop f + win/2), reflected at both ends of the utterance; stem frame t reads mel frames 2t - 1, 2t, 2t + 1 (frame -1 and frames past the utterance's
