@@ -14,10 +14,17 @@
 // A prefix is identified by a 64-bit rolling hash; an extension (i, c) re-creates beam j when hash(j's parent) = hash(i), len(j) = len(i) + 1 and
 // last(j) = c (node ids would not do: a prefix can be dropped and created again later).
 //
-// Streaming (avec_ctc_beam_stream): the same kernel with STREAM set.  Everything a frame hands to the next one is the current Beams buffer, n_live and the
+// Streaming (avec_ctc_beam_stream): the same kernel with MODE = STREAMING.  Everything a frame hands to the next one is the current Beams buffer, n_live and the
 // backpointer rows, so a launch that loads the buffer from a caller-owned state at its start and stores it at its end can stop after any frame and go on in a
 // later launch: per utterance the state is the W * BEAM_BYTES_PER_SLOT bytes of the buffer (always loaded into st0) plus a 16-byte header {n_live, frames
 // consumed, tag of (W, LM order), Tcap}.  The frame body is this one loop for both, so chunked and offline searches do the same arithmetic in the same order.
+//
+// Ring (avec_ctc_beam_stream_ring): the third mode, a stream without a frame limit.  The backpointer workspace holds `window` rows (row t at t % window) and the
+// state header grows by {base, ccount, dropped, commits}.  Immediately before the frame loop consumes absolute frame t with t - base == window, wave 0 runs the
+// commit step (ring_commit below): with h = window / 2 and f = base + h - 1, every live beam walks rows t-1 .. f+1 to the slot it descends from after frame f; the
+// tokens on the best beam's path through rows f .. base go to the commit log with their frames; the beams that descend from another slot are dropped, the others
+// compacted in place (row t-1 with them); base = f + 1.  The step depends on the frame index alone, so any split into pushes gives the same bits, and until frame
+// `window` the search is the offline one.  An emitting push walks rows t-1 .. base only and writes the tails [W][window] with their emission frames.
 #include "common.h"
 #include "avec_hip.h"
 
@@ -135,7 +142,7 @@ __host__ __device__ inline Lay lay(int W, int V, bool lm) {
   L.logp = o; o = a16(o + (size_t)V * 4); L.rows = o; o = a16(o + (lm ? (size_t)NW * V * 4 : 0));
   L.selk = o; o = a16(o + (size_t)W * 8); L.selp = o; o = a16(o + (size_t)W * 4);
   L.st0 = o; o = a16(o + (size_t)W * BEAM_BYTES_PER_SLOT); L.st1 = o; o = a16(o + (size_t)W * BEAM_BYTES_PER_SLOT);
-  L.misc = o; o += 16; L.total = o;
+  L.misc = o; o += 32; L.total = o;                    // {n_live, common prefix, -, -} and the ring mode's {-, ccount, dropped, commits}
   return L;
 }
 
@@ -145,12 +152,77 @@ struct BeamArgs {
   int* bp; int* tokens; int* out_len; float* score; float* ctc_logp;
   // streaming only: lengths = frames of this chunk per utterance (null: T), T = frames per utterance in `logits`, Tcap = rows of bp and of tokens
   int Tcap, emit; const unsigned char* reset; unsigned char* state; int* stable_len;
+  // ring only (Tcap = window): the commit log [B][log_frames] of (token, frame), the tails' emission frames [B][W][window], info [B][4] = {base, ccount, dropped, commits}
+  int2* log; int log_frames; int* frames; int* info;
 };
-constexpr int STATE_TAG = 0x43544342;
+constexpr int STATE_TAG = 0x43544342, RING_TAG = 0x43544352;
+constexpr int OFFLINE = 0, STREAMING = 1, RING = 2;
 __host__ __device__ inline size_t state_stride(int W) { return a16((size_t)W * BEAM_BYTES_PER_SLOT) + 16; }
+__host__ __device__ inline size_t ring_state_stride(int W) { return a16((size_t)W * BEAM_BYTES_PER_SLOT) + 32; }
 
-template <bool LM, bool STREAM>
+// The commit step of the ring mode (wave 0, one lane per beam), run before absolute frame t is consumed when t - base == window.  rg = {-, ccount, dropped, commits}
+// in LDS.  Every walk is bounded by `window` rows; rows are taken % window, slots clamped to W and log positions taken % log_frames before use.
+template <bool LM>
+__device__ __forceinline__ void ring_commit(const Beams& S, int* n_live, int* rg, int* bp, int2* log, int log_frames, int W, int K, int window, int base, int t, int lane) {
+  const int nl = *n_live, f = base + (window >> 1) - 1;
+  int anc = lane;                                      // 1. the slot beam `lane` descends from after frame f
+  if (lane < nl)
+    for (int r = t - 1; r > f; --r) {
+      anc = bp[(size_t)(r % window) * W + anc] & 255;
+      if (anc >= W) anc = 0;
+    }
+  const int a = __shfl(anc, 0, 64);                    // slot 0 is the best beam: the buffer is ranked best first
+  const int cc = rg[1];
+  int n = 0;                                           // 2. the tokens on a's path through rows f .. base: counted, then logged in forward order
+  if (nl > 0) {                                        // (every lane walks the same addresses: one request per row)
+    int s = a;
+    for (int r = f; r >= base; --r) {
+      const int code = bp[(size_t)(r % window) * W + s];
+      n += (code >> 8) != 0;
+      s = code & 255;
+      if (s >= W) s = 0;
+    }
+    s = a;
+    int k = n;
+    for (int r = f; r >= base && k > 0; --r) {
+      const int code = bp[(size_t)(r % window) * W + s];
+      if (code >> 8) {
+        --k;
+        if (lane == 0) log[(unsigned)(cc + k) % (unsigned)log_frames] = make_int2((code >> 8) - 1, r);
+      }
+      s = code & 255;
+      if (s >= W) s = 0;
+    }
+  }
+  const bool keep = lane < nl && anc == a;             // 3. drop the beams of other ancestors, compact the rest in their order
+  const u64 m = __ballot(keep);
+  const int p = __popcll(m & lanemask_lt(lane)), ns = __popcll(m);
+  int* last_row = bp + (size_t)((t - 1) % window) * W;
+  u64 hs = 0, ph = 0; float pb = 0.f, pnb = 0.f, lmv = 0.f; int last = 0, len = 0, clen = 0, code = 0;
+  [[maybe_unused]] int cx[KMAX];
+  if (keep) {                                          // every source field into registers before any is written
+    hs = S.hash[lane]; ph = S.phash[lane]; pb = S.pb[lane]; pnb = S.pnb[lane]; lmv = S.lm[lane]; last = S.last[lane]; len = S.len[lane]; clen = S.clen[lane];
+    if constexpr (LM) {
+#pragma unroll
+      for (int q = 0; q < KMAX; ++q) cx[q] = q < K ? S.ctx[q * W + lane] : 0;
+    }
+    code = last_row[lane];
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (keep) {
+    S.hash[p] = hs; S.phash[p] = ph; S.pb[p] = pb; S.pnb[p] = pnb; S.lm[p] = lmv; S.last[p] = last; S.len[p] = len; S.clen[p] = clen;
+    if constexpr (LM) {
+#pragma unroll
+      for (int q = 0; q < KMAX; ++q) if (q < K) S.ctx[q * W + p] = cx[q];
+    }
+    last_row[p] = code;                                // later walks through row t-1 land on the survivors' new slots
+  }
+  if (lane == 0) { *n_live = ns; rg[1] = cc + n; rg[2] += nl - ns; rg[3] += 1; }
+}
+
+template <bool LM, int MODE>
 __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
+  constexpr bool STREAM = MODE != OFFLINE;
   extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int W = a.W, V = a.V, T = a.T, K = LM ? a.lm.order - 1 : 0, nk = (V + 63) >> 6;
@@ -165,7 +237,23 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
   int* bp = a.bp + (size_t)b * TO * W;
   int t0 = 0;                                          // frames consumed by earlier launches
   bool fresh = true;
-  if constexpr (STREAM) {
+  [[maybe_unused]] int base = 0;                       // ring: the oldest frame whose backpointer row is held (the same value in every thread)
+  [[maybe_unused]] int* rg = n_live + 4;               // ring: {-, ccount, dropped, commits}
+  if constexpr (MODE == RING) {
+    const int* st = (const int*)(a.state + (size_t)b * ring_state_stride(W));
+    const int* hdr = st + a16((size_t)W * BEAM_BYTES_PER_SLOT) / 4;
+    // as below, with a tag of its own; a header is taken only when base, the window it implies and ccount (at most one token per committed frame) are consistent
+    fresh = (a.reset && a.reset[b]) || hdr[2] != (RING_TAG ^ (W | K << 8)) || hdr[3] != TO || hdr[0] < 0 || hdr[0] > W || hdr[1] < 0 || hdr[4] < 0 ||
+            hdr[4] > hdr[1] || hdr[1] - hdr[4] > TO || hdr[5] < 0 || hdr[5] > hdr[4];
+    if (!fresh) {
+      t0 = hdr[1]; base = hdr[4];
+      int* dst = (int*)(sm + L.st0);
+      for (int q = tid; q < W * (BEAM_BYTES_PER_SLOT / 4); q += NT) dst[q] = st[q];
+      if (tid == 0) { *n_live = hdr[0]; rg[1] = hdr[5]; rg[2] = hdr[6]; rg[3] = hdr[7]; }
+    } else if (tid == 0) {
+      rg[1] = 0; rg[2] = 0; rg[3] = 0;
+    }
+  } else if constexpr (STREAM) {
     const int* st = (const int*)(a.state + (size_t)b * state_stride(W));
     const int* hdr = st + a16((size_t)W * BEAM_BYTES_PER_SLOT) / 4;
     // a state this kernel did not write for the same W, LM order and Tcap (zeroed memory, say) starts from the empty prefix: its fields index LDS and bp
@@ -189,6 +277,13 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
   int cur = 0;
   for (int t = 0; t < len; ++t) {
     const Beams S = carve(sm + (cur ? L.st1 : L.st0), W), N = carve(sm + (cur ? L.st0 : L.st1), W);
+    if constexpr (MODE == RING) {
+      if (t0 + t - base == TO) {                       // the same in every thread: `base` is a register that every thread advances alike
+        if (wv == 0) ring_commit<LM>(S, n_live, rg, bp, a.log + (size_t)b * a.log_frames, a.log_frames, W, K, TO, base, t0 + t, lane);
+        base += TO >> 1;
+        __syncthreads();
+      }
+    }
     const int nl = *n_live;
     float lp[NPL];
     {
@@ -305,7 +400,7 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
           code = i | ((c + 1) << 8);
         }
         N.pnb[r] = cpnb[p]; N.lm[r] = clm[p];
-        bp[(size_t)(t0 + t) * W + r] = code;
+        bp[(size_t)(MODE == RING ? (t0 + t) % TO : t0 + t) * W + r] = code;
       }
       if (lane == 0) *n_live = ns;
     }
@@ -314,26 +409,33 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
   }
   const Beams S = carve(sm + (cur ? L.st1 : L.st0), W);
   const int nl = *n_live;
+  const int cc = MODE == RING ? rg[1] : 0;             // ring: tokens already committed; the outputs below are the tails after them
   if constexpr (STREAM) {
-    int* st = (int*)(a.state + (size_t)b * state_stride(W));
+    int* st = (int*)(a.state + (size_t)b * (MODE == RING ? ring_state_stride(W) : state_stride(W)));
     const int* src = (const int*)(sm + (cur ? L.st1 : L.st0));
     for (int q = tid; q < W * (BEAM_BYTES_PER_SLOT / 4); q += NT) st[q] = src[q];
     if (tid == 0) {
       int* hdr = st + a16((size_t)W * BEAM_BYTES_PER_SLOT) / 4;
-      hdr[0] = nl; hdr[1] = t0 + len; hdr[2] = STATE_TAG ^ (W | K << 8); hdr[3] = TO;
+      hdr[0] = nl; hdr[1] = t0 + len; hdr[2] = (MODE == RING ? RING_TAG : STATE_TAG) ^ (W | K << 8); hdr[3] = TO;
+      if constexpr (MODE == RING) { hdr[4] = base; hdr[5] = cc; hdr[6] = rg[2]; hdr[7] = rg[3]; }
     }
     if (!a.emit) return;
   }
   int* tok = a.tokens + (size_t)b * W * TO;
+  [[maybe_unused]] int* frm = MODE == RING ? a.frames + (size_t)b * W * TO : nullptr;
   if (tid < W) {
     const int w = tid;
     float sc = -INFINITY, cl = -INFINITY; int ol = 0;
     if (w < nl) {
-      cl = lse2(S.pb[w], S.pnb[w]); sc = cl + S.lm[w]; ol = S.len[w];
+      cl = lse2(S.pb[w], S.pnb[w]); sc = cl + S.lm[w]; ol = S.len[w] - cc;
+      if constexpr (MODE == RING) ol = ol < 0 ? 0 : (ol > TO ? TO : ol);      // at most one token per held row
       int slot = w, pos = ol - 1;
-      for (int t = t0 + len - 1; t >= 0 && pos >= 0; --t) {   // walk the backpointers (streaming: through every frame so far)
-        const int code = bp[(size_t)t * W + slot];
-        if (code >> 8) tok[(size_t)w * TO + pos--] = (code >> 8) - 1;
+      for (int t = t0 + len - 1; t >= base && pos >= 0; --t) {   // walk the backpointers (streaming: through every frame so far; ring: down to base)
+        const int code = bp[(size_t)(MODE == RING ? t % TO : t) * W + slot];
+        if (code >> 8) {
+          if constexpr (MODE == RING) frm[(size_t)w * TO + pos] = t;
+          tok[(size_t)w * TO + pos--] = (code >> 8) - 1;
+        }
         slot = code & 255;
         if (STREAM && slot >= W) slot = 0;               // (rows a caller swapped under the state: stay inside the buffer)
       }
@@ -342,13 +444,17 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
   }
   for (int q = tid; q < W * TO; q += NT) {
     const int w = q / TO, k = q - w * TO;
-    if (k >= (w < nl ? S.len[w] : 0)) tok[q] = 0;
+    if (k >= (w < nl ? S.len[w] - cc : 0)) {
+      tok[q] = 0;
+      if constexpr (MODE == RING) frm[q] = 0;
+    }
   }
   if constexpr (STREAM) {                              // the longest common prefix of the live beams: every later hypothesis extends one of them
     int* common = n_live + 1;
     if (tid == 0) {
       int m = nl > 0 ? S.len[0] : 0;
       for (int w = 1; w < nl; ++w) m = m < S.len[w] ? m : S.len[w];
+      if constexpr (MODE == RING) { m -= cc; m = m < 0 ? 0 : (m > TO ? TO : m); }
       *common = m;
     }
     __syncthreads();                                   // tokens of all beams written, *common set
@@ -360,7 +466,10 @@ __global__ __launch_bounds__(NT) void ctc_beam_kernel(BeamArgs a) {
       if (!same) atomicMin(common, k);
     }
     __syncthreads();
-    if (tid == 0) a.stable_len[b] = *common;
+    if (tid == 0) {
+      a.stable_len[b] = *common + cc;
+      if constexpr (MODE == RING) { int* info = a.info + 4 * b; info[0] = base; info[1] = cc; info[2] = rg[2]; info[3] = rg[3]; }
+    }
   }
 }
 
@@ -381,6 +490,19 @@ int check_lm(const avec_ngram_t* lm, int V) {
   AVEC_CHECK_ARG(lm->ctx_cap == 0 || (lm->ctx_key && lm->ctx_bo && lm->ctx_off && lm->ctx_cnt && lm->cont_tok && lm->cont_lp), "ctc_beam: null LM table");
   return 0;
 }
+
+template <int MODE>
+int launch_beam(const BeamArgs& a, bool lm, int B, hipStream_t st) {
+  const size_t bytes = lay(a.W, a.V, lm).total;
+  if (lm) {
+    if (int r = avec_lds_optin(ctc_beam_kernel<true, MODE>, bytes)) return r;
+    hipLaunchKernelGGL((ctc_beam_kernel<true, MODE>), dim3(B), dim3(NT), bytes, st, a);
+  } else {
+    if (int r = avec_lds_optin(ctc_beam_kernel<false, MODE>, bytes)) return r;
+    hipLaunchKernelGGL((ctc_beam_kernel<false, MODE>), dim3(B), dim3(NT), bytes, st, a);
+  }
+  AVEC_LAUNCH_CHECK(); return 0;
+}
 }  // namespace
 
 extern "C" long long avec_ctc_beam_workspace_bytes(int B, int T, int W) { return (long long)B * T * W * 4; }
@@ -399,15 +521,8 @@ extern "C" int avec_ctc_beam_search(const float* logits, const long long* length
   a.bp = (int*)workspace; a.tokens = tokens; a.out_len = out_len; a.score = score; a.ctc_logp = ctc_logp;
   if (lm) { if (int r = check_lm(lm, V)) return r; a.lm = *lm; }
   a.Tcap = T; a.emit = 1; a.reset = nullptr; a.state = nullptr; a.stable_len = nullptr;
-  const size_t bytes = lay(W, V, lm != nullptr).total;
-  if (lm) {
-    if (int r = avec_lds_optin(ctc_beam_kernel<true, false>, bytes)) return r;
-    hipLaunchKernelGGL((ctc_beam_kernel<true, false>), dim3(B), dim3(NT), bytes, st, a);
-  } else {
-    if (int r = avec_lds_optin(ctc_beam_kernel<false, false>, bytes)) return r;
-    hipLaunchKernelGGL((ctc_beam_kernel<false, false>), dim3(B), dim3(NT), bytes, st, a);
-  }
-  AVEC_LAUNCH_CHECK(); return 0;
+  a.log = nullptr; a.log_frames = 0; a.frames = nullptr; a.info = nullptr;
+  return launch_beam<OFFLINE>(a, lm != nullptr, B, st);
 }
 
 extern "C" long long avec_ctc_beam_state_bytes(int B, int W) { return (long long)B * (long long)state_stride(W); }
@@ -429,16 +544,39 @@ extern "C" int avec_ctc_beam_stream(const float* logits, const long long* chunk_
   a.lm = avec_ngram_t{}; a.alpha = alpha; a.beta = beta; a.oov = oov_logprob;
   a.bp = (int*)backptr; a.tokens = tokens; a.out_len = out_len; a.score = score; a.ctc_logp = ctc_logp;
   a.Tcap = Tcap; a.emit = emit; a.reset = reset; a.state = (unsigned char*)state; a.stable_len = stable_len;
+  a.log = nullptr; a.log_frames = 0; a.frames = nullptr; a.info = nullptr;
   if (lm) { if (int r = check_lm(lm, V)) return r; a.lm = *lm; }
-  const size_t bytes = lay(W, V, lm != nullptr).total;
-  if (lm) {
-    if (int r = avec_lds_optin(ctc_beam_kernel<true, true>, bytes)) return r;
-    hipLaunchKernelGGL((ctc_beam_kernel<true, true>), dim3(B), dim3(NT), bytes, st, a);
-  } else {
-    if (int r = avec_lds_optin(ctc_beam_kernel<false, true>, bytes)) return r;
-    hipLaunchKernelGGL((ctc_beam_kernel<false, true>), dim3(B), dim3(NT), bytes, st, a);
-  }
-  AVEC_LAUNCH_CHECK(); return 0;
+  return launch_beam<STREAMING>(a, lm != nullptr, B, st);
+}
+
+extern "C" long long avec_ctc_beam_ring_state_bytes(int B, int W) { return (long long)B * (long long)ring_state_stride(W); }
+extern "C" long long avec_ctc_beam_ring_workspace_bytes(int B, int window, int W) { return (long long)B * window * W * 4; }
+
+extern "C" int avec_ctc_beam_stream_ring(const float* logits, const long long* chunk_len, const unsigned char* reset, int B, int Tc, int V, int W, int window, int log_frames,
+                                         float inv_tmp, const avec_ngram_t* lm, float alpha, float beta, float oov_logprob, void* state, long long state_bytes, void* backptr,
+                                         long long backptr_bytes, void* log, long long log_bytes, int* tokens, int* frames, int* out_len, float* score, float* ctc_logp,
+                                         int* stable_len, int* info, int emit, hipStream_t st) {
+  AVEC_CHECK_ARG(logits && state && backptr && log, "ctc_beam_stream_ring: null pointer");
+  AVEC_CHECK_ARG(!emit || (tokens && frames && out_len && score && ctc_logp && stable_len && info), "ctc_beam_stream_ring: null output with emit set");
+  AVEC_CHECK_ARG(B >= 1 && Tc >= 1 && window >= 2 && log_frames >= 1 && V >= 2 && V <= MAXV && W >= 1 && W <= MAXW,
+                 "ctc_beam_stream_ring: bad dims B=%d Tc=%d window=%d log_frames=%d V=%d W=%d (Tc >= 1, window >= 2, log_frames >= 1, V <= %d, W <= %d)", B, Tc, window,
+                 log_frames, V, W, MAXV, MAXW);
+  AVEC_CHECK_ARG(state_bytes >= avec_ctc_beam_ring_state_bytes(B, W), "ctc_beam_stream_ring: state of %lld bytes, need %lld", state_bytes,
+                 avec_ctc_beam_ring_state_bytes(B, W));
+  AVEC_CHECK_ARG(backptr_bytes >= avec_ctc_beam_ring_workspace_bytes(B, window, W), "ctc_beam_stream_ring: backpointers of %lld bytes, need %lld", backptr_bytes,
+                 avec_ctc_beam_ring_workspace_bytes(B, window, W));
+  AVEC_CHECK_ARG(log_bytes >= (long long)B * log_frames * 8, "ctc_beam_stream_ring: commit log of %lld bytes, need %lld", log_bytes, (long long)B * log_frames * 8);
+  AVEC_CHECK_ARG(((size_t)state & 15) == 0, "ctc_beam_stream_ring: the state must be 16-byte aligned");
+  AVEC_CHECK_ARG(((size_t)log & 7) == 0, "ctc_beam_stream_ring: the commit log must be 8-byte aligned");
+  AVEC_CHECK_ARG(inv_tmp > 0.f, "ctc_beam_stream_ring: 1/tmp must be > 0");
+  BeamArgs a;
+  a.logits = logits; a.lengths = chunk_len; a.T = Tc; a.V = V; a.W = W; a.inv_tmp = inv_tmp;
+  a.lm = avec_ngram_t{}; a.alpha = alpha; a.beta = beta; a.oov = oov_logprob;
+  a.bp = (int*)backptr; a.tokens = tokens; a.out_len = out_len; a.score = score; a.ctc_logp = ctc_logp;
+  a.Tcap = window; a.emit = emit; a.reset = reset; a.state = (unsigned char*)state; a.stable_len = stable_len;
+  a.log = (int2*)log; a.log_frames = log_frames; a.frames = frames; a.info = info;
+  if (lm) { if (int r = check_lm(lm, V)) return r; a.lm = *lm; }
+  return launch_beam<RING>(a, lm != nullptr, B, st);
 }
 
 extern "C" int avec_ngram_rows(const avec_ngram_t* lm, const int* ctx, const int* ctx_len, int n, int max_len, float oov_logprob, float* rows, hipStream_t st) {

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .streaming import CTCBeamStreamSession
+from .streaming import CTCBeamRingStreamSession, CTCBeamStreamSession
 
 
 def ctc_collapse(tokens, length, blank=0):
@@ -275,13 +275,24 @@ class CTCBeamSearchDecoder(CTCGreedySearchDecoder):
         hyps = [r["ids"] for r in records]
         return (self.tokenizer.decode(hyps) if self.tokenizer is not None else hyps), records
 
-    def stream(self, batch_size, max_frames):
-        """A streaming session (CTCBeamStreamSession) over batch_size utterance slots of at most max_frames frames each: push logits chunk by chunk as the
-        encoder emits them, read the partial and the final part of the transcript after every chunk, finish() for what beam_search gives on the whole."""
+    def stream(self, batch_size, max_frames=None, window=None, log_frames=None):
+        """A streaming session over batch_size utterance slots: push logits chunk by chunk as the encoder emits them, read the partial and the final part of the
+        transcript after every chunk, finish() for the winning hypotheses.
+        window=None: a CTCBeamStreamSession of at most max_frames frames per slot, whose finish() is what beam_search gives on the whole.
+        window=N (>= 2, max_frames must be None): a CTCBeamRingStreamSession without a frame limit: history older than N frames is committed N // 2 frames at a time
+        (the beams that disagree with the best beam on it are dropped) and reported as final; log_frames (default max(4 N, 256)) sizes the device's commit log."""
         if self.test_time_aug:
             raise NotImplementedError("CTCBeamSearchDecoder.stream with test_time_aug=True: the augmentations of an utterance would have to be pushed in step, at "
                                       "twice the encoder cost per chunk; decode_augmented covers whole utterances")
-        return CTCBeamStreamSession(self, batch_size, max_frames)
+        if window is None:
+            if max_frames is None:
+                raise ValueError("CTCBeamSearchDecoder.stream: max_frames is needed (or window=N for a session without a frame limit)")
+            if log_frames is not None:
+                raise ValueError("CTCBeamSearchDecoder.stream: log_frames belongs to window=N")
+            return CTCBeamStreamSession(self, batch_size, max_frames)
+        if max_frames is not None:
+            raise ValueError("CTCBeamSearchDecoder.stream: window=%r together with max_frames=%r: a ring session has no frame limit" % (window, max_frames))
+        return CTCBeamRingStreamSession(self, batch_size, window, log_frames)
 
     def _decode_ids(self, logits, logits_len):
         return self.beam_search(logits, logits_len)

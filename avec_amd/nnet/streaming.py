@@ -10,7 +10,8 @@ a module tree or a state_dict.
           AudioFrontStreamSession       waveform chunks -> stem frames
           VisualFrontStreamSession      video chunks -> ResNet features
       AudioVisualStreamSession          both branch sessions -> row pairing -> the fusion stack
-      CTCBeamStreamSession              the beam search over logit chunks
+      CTCBeamStreamSession              the beam search over logit chunks, up to max_frames per slot
+      CTCBeamRingStreamSession          the beam search over logit chunks without a frame limit: a window of backpointer rows, older history committed
     _BranchStreamSession                a front session -> the stack -> the head; a last push's tail of up to TAIL frames goes through _push_again
       AudioStreamSession (TAIL 1), VisualStreamSession (TAIL 2)"""
 import torch
@@ -22,7 +23,7 @@ from . import attentions, normalizations
 from .captured import CapturedStep
 
 __all__ = ["slot_mask", "ConformerStreamSession", "ConformerLookaheadStreamSession", "AudioFrontStreamSession", "AudioStreamSession", "VisualFrontStreamSession", "VisualStreamSession",
-           "AudioVisualStreamSession", "CTCBeamStreamSession"]
+           "AudioVisualStreamSession", "CTCBeamStreamSession", "CTCBeamRingStreamSession"]
 
 
 def slot_mask(flags, B):
@@ -1060,3 +1061,136 @@ class CTCBeamStreamSession(_StreamSession):
             return self.dec._rescore(st.tokens, st.out_len, st.score, self.B, 1)
         tok0, len0 = st.tokens[:, 0].cpu(), st.out_len[:, 0].cpu().tolist()
         return [tok0[b, :len0[b]].tolist() for b in range(self.B)]
+
+
+class CTCBeamRingStreamSession(_StreamSession):
+    """CTCBeamSearchDecoder.stream(window=N): the window-limited beam search of avec_amd/csrc/ctc_beam.hip (avec_ctc_beam_stream_ring), a stream without a frame
+    limit.  The device keeps `window` backpointer rows per slot; whenever a slot holds `window` frames, the older window // 2 of them are committed: the best beam's
+    tokens on them become final, go to the device's commit log with the frame that emitted each, and the beams that descend from another hypothesis on those frames are
+    dropped.  The commit depends on the frame count alone, so the results do not depend on how the stream is cut into pushes, and up to frame `window` the search is
+    the offline one.  What is committed never changes; the final best hypothesis can differ from an unlimited search's when the two disagree on committed frames.
+    Host memory: one int per committed token and one per emission frame, per slot, until the slot is reset.
+    The commit log holds log_frames entries per slot (default max(4 * window, 256); more than `window` are needed).  Between two reads a slot logs at most the frames
+    pushed in between plus `window` tokens, so the session counts, on the host, the frames every slot was pushed since its log was last read, and reads the logs (one
+    synchronisation and one device-to-host copy) before any push after which that count plus `window` would pass log_frames, with fetch=False too; a chunk longer than
+    log_frames - window frames is consumed in pieces for the same reason.  A fetching push reads the logs anyway.  Not capturable."""
+
+    def __init__(self, decoder, batch_size, window, log_frames=None):
+        super().__init__(batch_size)
+        self.dec, self.window = decoder, int(window)
+        self.log_frames = max(4 * self.window, 256) if log_frames is None else int(log_frames)
+        if self.B < 1 or self.window < 2:
+            raise ValueError("stream: batch_size %d, window %d (>= 2)" % (self.B, self.window))
+        if self.log_frames <= self.window:
+            raise ValueError("stream: log_frames %d for window %d: the commit log must hold more than a window" % (self.log_frames, self.window))
+        self._since = [0] * self.B                       # per slot, an upper bound of the frames pushed since its log was read (Tc per push): no sync to know it
+        self._ids = [[] for _ in range(self.B)]          # committed since the slot's reset
+        self._frames = [[] for _ in range(self.B)]
+        self._reported = [0] * self.B                    # how many of them a fetch has returned
+        self._emitted = False
+
+    def _allocate(self, dev):
+        self.state = ops.CTCBeamRingState(self.B, self.dec.beam_size, self.window, self.log_frames, dev)
+        self.reset_flags = self.state.reset_flags
+
+    def _launch(self, chunk, chunk_len, reset, emit):
+        d = self.dec
+        out = ops.ctc_beam_stream_ring(self.state, chunk, chunk_len, reset, d.ngram_tmp, d.lm(chunk.shape[-1]), d.ngram_alpha, d.ngram_beta, emit=emit)
+        self._emitted = emit
+        return out
+
+    def _drain(self, extra=()):
+        """read every slot's new log entries, with `extra` int32 device tensors in the same copy -> the host lists of `extra`"""
+        st = self.state
+        parts = [st.header()[:, 5].contiguous(), st.log] + list(extra)
+        host = torch.cat([p.reshape(-1) for p in parts]).cpu()           # the one synchronisation
+        cc, log = host[:self.B].tolist(), host[self.B:self.B + st.log.numel()].view(self.B, self.log_frames, 2).tolist()
+        for b in range(self.B):
+            for k in range(len(self._ids[b]), cc[b]):
+                tok, frame = log[b][k % self.log_frames]
+                self._ids[b].append(tok)
+                self._frames[b].append(frame)
+        self._since = [0] * self.B
+        out, at = [], self.B + st.log.numel()
+        for p in extra:
+            out.append(host[at:at + p.numel()].view(p.shape).tolist())
+            at += p.numel()
+        return out
+
+    def push(self, logits_chunk, chunk_len=None, reset=None, fetch=True):
+        """Consume logits_chunk [B, Tc, V]; slot b takes chunk_len[b] frames of it (int64 tensor; default: all Tc).  reset: slots to restart from the empty
+        transcript before this chunk (list of indices or host bool mask [B]); what such a slot had committed and no fetch had returned is dropped with it.  No push is
+        refused for its length.  fetch=True returns one record per slot:
+            committed_ids, committed_frames   everything committed since the slot's reset with the frame that emitted each token: final, it never changes
+            n_new                             how many of them are new since the last fetch
+            partial_ids, partial_frames       committed ++ the best beam's tail: the best hypothesis so far
+            stable_ids                        its leading tokens that every live beam shares (at least the committed ones)
+            dropped                           beams dropped by commits since the slot's reset
+        and with a tokenizer "committed", "partial" and "stable", the text of the three id lists (final token by token, not character by character).
+        fetch=False skips the traceback and copies nothing, except that the commit log is read first (one synchronisation) when the frames pushed to some slot since
+        the last read, plus this chunk, plus `window` would pass log_frames."""
+        B, Tc, self._V = logits_chunk.shape
+        if B != self.B:
+            raise ValueError("push: chunk of %d utterances for a session of %d" % (B, self.B))
+        mask = self._reset_mask(reset)
+        self._ensure_state(logits_chunk.device)
+        piece = self.log_frames - self.window
+        for off in range(0, Tc, piece):
+            n = min(piece, Tc - off)
+            if not self._first and max(self._since) + n + self.window > self.log_frames:
+                self._drain()
+            if off == 0 and mask is not None:
+                for b in range(B):
+                    if mask[b]:
+                        self._ids[b], self._frames[b], self._reported[b], self._since[b] = [], [], 0, 0
+            self._first = False
+            self._since = [s + n for s in self._since]
+            whole = off == 0 and n == Tc
+            part = logits_chunk if whole else logits_chunk[:, off:off + n]
+            part_len = chunk_len if whole or chunk_len is None else (chunk_len.to(torch.int64) - off).clamp(0, n)
+            self._launch(part, part_len, self._raise_flags(self.reset_flags, mask) if off == 0 else None, fetch and off + n == Tc)
+        if not fetch:
+            return None
+        st = self.state
+        tok0, frm0, len0, stable, info = self._drain((st.tokens[:, 0], st.frames[:, 0], st.out_len[:, 0], st.stable_len, st.info))
+        tk = self.dec.tokenizer
+        recs = []
+        for b in range(B):
+            ids, frames = list(self._ids[b]), list(self._frames[b])
+            rec = {"committed_ids": ids, "committed_frames": frames, "n_new": len(ids) - self._reported[b],
+                   "partial_ids": ids + tok0[b][:len0[b]], "partial_frames": frames + frm0[b][:len0[b]], "dropped": info[b][2]}
+            rec["stable_ids"] = rec["partial_ids"][:stable[b]]
+            self._reported[b] = len(ids)
+            if tk is not None:
+                rec["committed"], rec["partial"], rec["stable"] = tk.decode(ids), tk.decode(rec["partial_ids"]), tk.decode(rec["stable_ids"])
+            recs.append(rec)
+        return recs
+
+    def hypotheses(self):
+        """after an emitting push: (tokens [B, W, L] int32 and out_len [B, W] int32 on the host: committed ++ tail of every beam, zero past out_len; score [B, W] on
+        the device) -- the layout decoder._rescore takes"""
+        st = self.state
+        tails, lens = self._drain((st.tokens, st.out_len))
+        alive = (st.score > float("-inf")).cpu().tolist()
+        W = st.W
+        hyps = [[(self._ids[b] + tails[b][w][:lens[b][w]]) if alive[b][w] else [] for w in range(W)] for b in range(self.B)]
+        L = max(1, max(len(h) for hb in hyps for h in hb))
+        tokens, out_len = torch.zeros(self.B, W, L, dtype=torch.int32), torch.zeros(self.B, W, dtype=torch.int32)
+        for b in range(self.B):
+            for w in range(W):
+                out_len[b, w] = len(hyps[b][w])
+                tokens[b, w, :len(hyps[b][w])] = torch.tensor(hyps[b][w], dtype=torch.int32)
+        return tokens, out_len, st.score
+
+    def finish(self):
+        """Per slot the winning token list: committed ++ tail of every beam goes through the decoder's neural rescoring when a neural LM is loaded (the committed part
+        is shared, so only the tails compete); otherwise committed ++ the best beam's tail."""
+        if self.state is None:
+            raise RuntimeError("finish: nothing was pushed")
+        dev = self.state.state.device
+        if not self._emitted:                            # one launch that consumes no frame and emits
+            self._launch(torch.zeros(self.B, 1, self._V, device=dev), torch.zeros(self.B, dtype=torch.int64, device=dev), None, True)
+        tokens, out_len, score = self.hypotheses()
+        if self.dec.neural_rescorer is not None:
+            return self.dec._rescore(tokens, out_len, score, self.B, 1)
+        return [tokens[b, 0, :int(out_len[b, 0])].tolist() for b in range(self.B)]

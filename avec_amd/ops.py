@@ -1981,6 +1981,59 @@ def ctc_beam_stream(st, logits, chunk_len=None, reset=None, tmp=1.0, lm=None, al
     return (st.tokens, st.out_len, st.score, st.ctc_logp, st.stable_len) if emit else None
 
 
+class CTCBeamRingState:
+    """Everything an endless streaming beam search keeps between pushes (ops.ctc_beam_stream_ring), allocated once: the beam state, the `window` backpointer rows and
+    the commit log of avec_ctc_beam_stream_ring, the outputs it writes when it emits, and a reset flag buffer.  batch utterance slots, `beam` beams, a commit log of
+    log_frames (token, frame) entries per slot.  A zero-filled state is a reset one."""
+
+    def __init__(self, batch, beam, window, log_frames, device=None):
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.B, self.W, self.window, self.log_frames = int(batch), int(beam), int(window), int(log_frames)
+        if self.B < 1 or self.window < 2 or self.log_frames < 1 or not 1 <= self.W <= 64:
+            raise ValueError("CTCBeamRingState: batch %d, beam %d (1..64), window %d (>= 2), log_frames %d" % (self.B, self.W, self.window, self.log_frames))
+        self.state = torch.zeros(lib.raw("avec_ctc_beam_ring_state_bytes")(self.B, self.W), dtype=torch.uint8, device=dev)
+        self.backptr = torch.empty(lib.raw("avec_ctc_beam_ring_workspace_bytes")(self.B, self.window, self.W), dtype=torch.uint8, device=dev)
+        self.log = torch.zeros(self.B, self.log_frames, 2, dtype=torch.int32, device=dev)
+        self.tokens = torch.zeros(self.B, self.W, self.window, dtype=torch.int32, device=dev)
+        self.frames = torch.zeros(self.B, self.W, self.window, dtype=torch.int32, device=dev)
+        self.out_len = torch.zeros(self.B, self.W, dtype=torch.int32, device=dev)
+        self.score = torch.full((self.B, self.W), float("-inf"), dtype=torch.float32, device=dev)
+        self.ctc_logp = torch.full((self.B, self.W), float("-inf"), dtype=torch.float32, device=dev)
+        self.stable_len = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.info = torch.zeros(self.B, 4, dtype=torch.int32, device=dev)
+        self.reset_flags = torch.zeros(self.B, dtype=torch.uint8, device=dev)
+
+    def header(self):
+        """[B, 8] int32 view of the state: {live beams, frames consumed, tag, window, base, ccount, dropped, commits} as the last push left them"""
+        return self.state.view(torch.int32).view(self.B, -1)[:, -8:]
+
+
+def ctc_beam_stream_ring(st, logits, chunk_len=None, reset=None, tmp=1.0, lm=None, alpha=0.6, beta=1.0, emit=True):
+    """One push of the endless streaming CTC prefix beam search (window-limited: include/avec_hip.h, avec_ctc_beam_stream_ring): `st` (a CTCBeamRingState) consumes the
+    chunk logits [B, Tc, V]; utterance b takes chunk_len[b] frames (int64 [B] on the device; None: all Tc) and no push is ever too long.  reset, tmp, lm, alpha, beta as
+    ops.ctc_beam_stream.  History older than the window is committed to st.log as the frames pass (entry k % log_frames = committed token k and its frame).  With emit
+    the state's tokens and frames [B, W, window] hold every beam's tail after the committed tokens and the frame that emitted each, out_len the tail lengths, score
+    and ctc_logp the beams' scores, stable_len [B] = committed tokens + the common prefix of the tails, info [B, 4] = {base, ccount, dropped, commits}; they are returned
+    (views of st, overwritten by the next emitting push).  One launch, no host synchronisation, no allocation beyond the fp32 conversion of the chunk."""
+    B, Tc, V = logits.shape
+    if B != st.B:
+        raise ValueError("ctc_beam_stream_ring: chunk of %d utterances for a state of %d" % (B, st.B))
+    lg = _f32c(logits)
+    dev = st.state.device
+    if lg.device != dev:
+        raise ValueError("ctc_beam_stream_ring: chunk on %s, state on %s" % (lg.device, dev))
+    chunk_len = _slot_vec("ctc_beam_stream_ring", "chunk_len", chunk_len, B, dev, convert=True)
+    _slot_vec("ctc_beam_stream_ring", "reset", reset, B, dev, mask=True)
+    use_lm = lm is not None and lm.usable
+    lm_arg = _byref(lm.device_struct(dev)) if use_lm else None
+    oov = lm.oov_logprob if use_lm else 0.0
+    lib.ctc_beam_stream_ring(lg.data_ptr(), _p(chunk_len), _p(reset), B, Tc, V, st.W, st.window, st.log_frames, 1.0 / tmp, lm_arg, alpha if use_lm else 0.0,
+                             beta if use_lm else 0.0, oov, st.state.data_ptr(), st.state.numel(), st.backptr.data_ptr(), st.backptr.numel(), st.log.data_ptr(),
+                             st.log.numel() * 4, st.tokens.data_ptr(), st.frames.data_ptr(), st.out_len.data_ptr(), st.score.data_ptr(), st.ctc_logp.data_ptr(),
+                             st.stable_len.data_ptr(), st.info.data_ptr(), 1 if emit else 0, rt.stream())
+    return (st.tokens, st.frames, st.out_len, st.score, st.ctc_logp, st.stable_len, st.info) if emit else None
+
+
 def ctc_align(logits, logits_len, targets, target_len, blank=0, tier=0):
     """CTC forced alignment (Viterbi) of targets [B, Lmax] (target_len [B]) to logits [B, T, V] (logits_len [B]): one launch for the whole batch, no host
     synchronisation.  Returns path [B, T] int32 (the token of every frame, -1 past logits_len), spans [B, Lmax, 2] int32 ((first frame, last frame + 1) of every

@@ -605,6 +605,31 @@ long long avec_ctc_beam_state_bytes(int B, int W);
 int avec_ctc_beam_stream(const float* logits, const long long* chunk_len, const unsigned char* reset, int B, int Tc, int V, int W, int Tcap, float inv_tmp,
                          const avec_ngram_t* lm, float alpha, float beta, float oov_logprob, void* state, long long state_bytes, void* backptr, long long backptr_bytes,
                          int* tokens, int* out_len, float* score, float* ctc_logp, int* stable_len, int emit, hipStream_t stream);
+/* Ring form of avec_ctc_beam_stream: a stream without a frame limit (window-limited prefix beam search).  The backpointer workspace holds `window` rows per
+ * utterance (absolute frame t at row t % window), and per utterance the state also keeps base (the oldest frame whose row is held), ccount (tokens committed since
+ * the reset), dropped and commits.  Immediately before the search consumes absolute frame t with t - base == window it runs the commit step, with h = window / 2 and
+ * f = base + h - 1: (1) every live beam walks rows t-1 .. f+1 to the slot it descends from after frame f; a = that slot of beam 0, the best beam; (2) the tokens on
+ * a's path through rows f .. base are appended, oldest first, to the commit log with the frame that emitted each; (3) the beams that descend from another slot are
+ * dropped and the others compacted in their order, every field and their entries of row t-1 with them; (4) base = f + 1.  Scores and absolute prefix lengths are not
+ * touched.  The step depends on the frame index alone, so any split of the frames into pushes gives the same bits; while t <= window nothing was committed and the
+ * search is avec_ctc_beam_search's bit for bit.  t - base <= window holds after every push.
+ * state: avec_ctc_beam_ring_state_bytes(B, W) bytes, 16-byte aligned; a state not written by this entry point with the same W, LM order and window (zero-filled
+ * memory, a state of avec_ctc_beam_stream) and a slot with reset[b] != 0 start from the empty prefix with base = ccount = dropped = commits = 0.  backptr:
+ * avec_ctc_beam_ring_workspace_bytes(B, window, W) bytes.  log: [B][log_frames] pairs of int32 (token, frame), 8-byte aligned; committed token k of an utterance
+ * (counted from its reset) is entry k % log_frames.  At most one token is committed per frame and the tokens logged between two reads are those of the frames
+ * between the two values of base, at most the frames pushed in between plus window: a host that reads the log whenever (frames pushed since the last read) + window
+ * would pass log_frames loses nothing, and it can count pushed frames without a synchronisation.  chunk_len is clamped to [0, Tc] only.  The counters and frame
+ * indices are int32.
+ * emit != 0 writes the tails: tokens and frames [B][W][window] int32 (the tokens of every beam after the committed ones and the absolute frame that emitted each, zero
+ * past out_len), out_len [B][W] = the tail length, score and ctc_logp as avec_ctc_beam_search, stable_len [B] = ccount + the common prefix of the live tails, and
+ * info [B][4] = {base, ccount, dropped, commits}; a hypothesis is the committed tokens followed by its tail.  The traceback walks rows t-1 .. base only.
+ * emit == 0 writes no output (the seven pointers may be NULL).  Limits: W <= 64, V <= 1024, order <= 8; Tc >= 1, window >= 2, log_frames >= 1. */
+long long avec_ctc_beam_ring_state_bytes(int B, int W);
+long long avec_ctc_beam_ring_workspace_bytes(int B, int window, int W);
+int avec_ctc_beam_stream_ring(const float* logits, const long long* chunk_len, const unsigned char* reset, int B, int Tc, int V, int W, int window, int log_frames,
+                              float inv_tmp, const avec_ngram_t* lm, float alpha, float beta, float oov_logprob, void* state, long long state_bytes, void* backptr,
+                              long long backptr_bytes, void* log, long long log_bytes, int* tokens, int* frames, int* out_len, float* score, float* ctc_logp,
+                              int* stable_len, int* info, int emit, hipStream_t stream);
 /* rows[i][c] = ln P(c | ctx_i) as the beam search sees it: ctx [n][max_len] int32 tokens oldest first (-1 = <s>), ctx_len [n]; only the last order-1
  * tokens of a context are used.  Test and documentation aid for the table layout above. */
 int avec_ngram_rows(const avec_ngram_t* lm, const int* ctx, const int* ctx_len, int n, int max_len, float oov_logprob, float* rows, hipStream_t stream);
